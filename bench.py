@@ -303,6 +303,24 @@ def roofline_block(ctx, capi, p, tag, solo, timed, layout_name, traffic=None, tr
     return out
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(outdir, film):
+    """--dump-outputs: the film of the last timed step (float32 [height, width, channels], what mer_render leaves in the caller's buffer)
+    as outdir/film.npy; a film above DUMP_MAX_BYTES is written as a fixed, seeded sample of its pixels (outdir/film_sample.npy,
+    [pixels, channels] in ascending pixel order), the same pixels for the same film size from run to run."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    if film.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(outdir, "film.npy"), film)
+        return
+    px = film.reshape(-1, film.shape[-1])
+    k = (DUMP_MAX_BYTES - 4096) // px[0].nbytes          # 4096: room for the .npy header
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(os.path.join(outdir, "film_sample.npy"), np.ascontiguousarray(px[idx]))
+
+
 def spawn_ranks(args):
     """plain `python bench.py --gpus N`: start N ranks with torch.distributed.run before this process touches a GPU, relay rank 0."""
     port = 29500 + (os.getpid() % 2000)
@@ -333,7 +351,11 @@ def main():
     ap.add_argument("--no-solo-step", action="store_true", help="skip the extra single-pipeline step (profiled runs)")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not take the roofline's counter passes (child rocprofv3 runs) inside this run; fall back to the committed pass")
     ap.add_argument("--options", default="", help="mer_context_set_option pairs, e.g. pipes=1,ksteps=96")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the film of the last timed step to DIR/film.npy (float32; a seeded pixel sample above 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -412,6 +434,8 @@ def main():
         passes.append(n_); march_ms.append(m_); event_ms.append(e_)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, film.cpu().numpy())
     tl = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     per_rank_ms = [elapsed / max(args.steps, 1) * 1e3]
     # ranks that joined the RCCL communicator (backend "nccl" is RCCL on ROCm); null under any other backend -- a gloo rehearsal says so
