@@ -252,6 +252,9 @@ int  mer_lookup_trilinear_rgb(mer_context *ctx, mer_volume v, const float *pts, 
 /* VolumeDataSource::valueAndGradient (splinevolume.cpp:354-360) for rif_interp in {TRILINEAR,BSPLINE3} */
 int  mer_rif_value_grad(mer_context *ctx, mer_volume v, int32_t rif_interp, const float *pts, int64_t n,
                         float *out_val, float *out_grad);
+/* AcousticRIFVolume::valueAndGradient (acousticrifvolume.cpp:224-342) of the scene's analytic field (rif_mode = acoustic) */
+int  mer_acoustic_value_grad(mer_context *ctx, const mer_scene_desc *scene, const float *pts, int64_t n,
+                             float *out_val, float *out_grad);
 /* HeterogeneousRefractiveMedium::trace / traceTillBoundary (heterogeneousrefractive.cpp:671-691,742-776);
    dist[i] = +inf selects traceTillBoundary */
 int  mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0, const float *d0, const float *dist,

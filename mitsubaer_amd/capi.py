@@ -21,7 +21,7 @@ SYMBOLS = [
     "mer_volume_download_spline", "mer_volume_destroy", "mer_film_channels", "mer_film_alloc_n", "mer_film_zero_n",
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
-    "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_er_trace",
+    "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
     "mer_sample_distance", "mer_connect", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_camera_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
@@ -380,6 +380,13 @@ class Context:
         pts = _f32(pts); n = pts.shape[0]
         val = np.empty(n, np.float32); grad = np.empty((n, 3), np.float32)
         self._check(self.lib.mer_rif_value_grad(self.h, C.c_int32(vol.handle), C.c_int32(interp), _fp(pts), C.c_int64(n), _fp(val), _fp(grad)))
+        return val, grad
+
+    def acoustic_value_grad(self, scene, pts):
+        """the scene's analytic acoustic RIF (rif_mode = RIF_ACOUSTIC) and its gradient at pts"""
+        pts = _f32(pts); n = pts.shape[0]
+        val = np.empty(n, np.float32); grad = np.empty((n, 3), np.float32)
+        self._check(self.lib.mer_acoustic_value_grad(self.h, C.byref(scene), _fp(pts), C.c_int64(n), _fp(val), _fp(grad)))
         return val, grad
 
     def er_trace(self, scene, p0, d0, dist):

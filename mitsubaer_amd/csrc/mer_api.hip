@@ -840,6 +840,20 @@ int mer_rif_value_grad(mer_context *ctx, mer_volume h, int32_t interp, const flo
     return dg.download(out_grad, n * 12);
 }
 
+int mer_acoustic_value_grad(mer_context *ctx, const mer_scene_desc *scene, const float *pts, int64_t n, float *out_val, float *out_grad) {
+    MER_USE_DEVICE(ctx);
+    if (scene->rif_mode != MER_RIF_ACOUSTIC) return fail(ctx, "mer_acoustic_value_grad needs rif_mode = acoustic");
+    Params P;
+    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.albedo_mode = MER_ALBEDO_CONST;
+    if (make_params(ctx, &sc, P)) return 1;
+    DevBuf dp(ctx), dv(ctx), dg(ctx);
+    if (dp.upload(pts, n * 12) || dv.alloc(n * 4) || dg.alloc(n * 12)) return 1;
+    hipLaunchKernelGGL(acoustic_value_grad_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.rif, dp.as<float>(), n, dv.as<float>(), dg.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    if (dv.download(out_val, n * 4)) return 1;
+    return dg.download(out_grad, n * 12);
+}
+
 int mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0, const float *d0, const float *dist, int64_t n,
                  float *out_p, float *out_v, float *out_dist_surf, float *out_opt, int32_t *out_success) {
     MER_USE_DEVICE(ctx);

@@ -84,7 +84,7 @@ __device__ __forceinline__ void rif_value_grad_hess_vol(const DGrid &g, CellCach
         const float phi = atan2f(py, pz);
         if (r < MER_EPSILON_RIF) { py = MER_EPSILON_RIF; pz = MER_EPSILON_RIF; r = MER_EPSILON_RIF; }
         const float kr = g.ac_k_r, krr = kr * r, m = (float) g.ac_mode, nmax = g.ac_n_max;
-        const float j0 = jnf(g.ac_mode, krr), j1 = jnf(g.ac_mode + 1, krr), j2 = jnf(g.ac_mode + 2, krr);
+        const float j0 = bessel_jn(g.ac_mode, krr), j1 = bessel_jn(g.ac_mode + 1, krr), j2 = bessel_jn(g.ac_mode + 2, krr);
         const float d0 = m / krr * j0 - j1, d1 = (m + 1.0f) / krr * j1 - j2;
         const float invr = 1.0f / r, invr2 = invr * invr;
         const float cosp = cosf(phi), sinp = sinf(phi), cosmp = cosf(m * phi), sinmp = sinf(m * phi);

@@ -515,15 +515,27 @@ __device__ __forceinline__ bool inside_volume_limits(const DGrid &g, f3 p) {   /
 }
 
 // AcousticRIFVolume::valueAndGradient / gradientAndHessian (src/volume/acousticrifvolume.cpp:224-342): n = n_o + n_max J_m(k_r r) cos(m phi)
-// in the (y, z) plane, r clamped at EpsilonRIF = 1e-8 (:15, :235-239); single precision, jnf / atan2f of the device library.
+// in the (y, z) plane, r clamped at EpsilonRIF = 1e-8 (:15, :235-239); single precision, bessel_jn / atan2f.
 #define MER_EPSILON_RIF 1e-8f
+// J_n(x) for 0 <= x: below x = 1 by its power series (x/2)^n / n! sum_k (-x^2/4)^k / (k! (n+1)_k), 8 terms (< 1e-12 relative), above it
+// the device library's jnf.  That jnf loses its relative accuracy for x << n, and the gradient below multiplies J_m by 1/x and 1/r^2:
+// on the axis clamp (r = 1e-8, m = 3) it gave a gradient off by 3/sqrt(2) n_max k_r (tests/test_gpu_closed_form.py).
+__device__ __forceinline__ float bessel_jn(int n, float x) {
+    if (!(x < 1.0f)) return jnf(n, x);
+    const float h = 0.5f * x, q = -h * h;
+    float lead = 1.0f;
+    for (int i = 1; i <= n; i++) lead *= h / (float) i;
+    float term = 1.0f, sum = 1.0f;
+    for (int k = 1; k <= 8; k++) { term *= q / (float) (k * (n + k)); sum += term; }
+    return lead * sum;
+}
 __device__ __forceinline__ void acoustic_value_grad(const DGrid &g, f3 pc, float &n, f3 &gr) {
     float py = pc.y, pz = pc.z;
     float r = sqrtf(py * py + pz * pz);
     const float phi = atan2f(py, pz);
     if (r < MER_EPSILON_RIF) { py = MER_EPSILON_RIF; pz = MER_EPSILON_RIF; r = MER_EPSILON_RIF; }
     const float kr = g.ac_k_r, krr = kr * r, m = (float) g.ac_mode;
-    const float bj = jnf(g.ac_mode, krr), dbj = m / krr * bj - jnf(g.ac_mode + 1, krr);
+    const float bj = bessel_jn(g.ac_mode, krr), dbj = m / krr * bj - bessel_jn(g.ac_mode + 1, krr);
     const float invr = 1.0f / r, invr2 = invr * invr;
     const float cosmp = cosf(m * phi), sinmp = sinf(m * phi);
     n = g.ac_n_o + g.ac_n_max * bj * cosmp;

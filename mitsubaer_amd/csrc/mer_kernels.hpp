@@ -21,6 +21,14 @@ __global__ void lookup_rgb_kernel(DGrid g, const float *pts, int64_t n, float *o
     const f3 v = lookup_spectrum(g, f3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]));
     out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
 }
+// the analytic acoustic RIF (RIFK_ACOUSTIC) at arbitrary points: the same acoustic_value_grad the walks evaluate
+__global__ void acoustic_value_grad_kernel(DGrid g, const float *pts, int64_t n, float *val, float *grad) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v; f3 gr;
+    acoustic_value_grad(g, f3(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]), v, gr);
+    val[i] = v; grad[3 * i] = gr.x; grad[3 * i + 1] = gr.y; grad[3 * i + 2] = gr.z;
+}
 __global__ void rif_value_grad_kernel(DGrid g, int interp, const float *pts, int64_t n, float *val, float *grad) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
