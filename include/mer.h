@@ -101,8 +101,9 @@ typedef struct {
        modulation the film has one frame and every contribution is weighted by correlationFunction(pathLength)
        (src/integrators/bdpt/bdpt_proc.cpp:446-447; src/librender/film.cpp:76-78). */
     int32_t modulation; float mod_lambda, mod_phase_deg; int32_t mod_P, mod_neighbors;
-    /* BSDF of the medium's boundary shape: MER_BSDF_NULL (index-matched, src/librender/shape.cpp:48-70) or MER_BSDF_HDIELECTRIC
-       (src/bsdfs/hdielectric.cpp: smooth dielectric whose eta is the RIF at the hit point, exterior index 1) */
+    /* BSDF of the medium's boundary shape: MER_BSDF_NULL (index-matched, src/librender/shape.cpp:48-70), MER_BSDF_HDIELECTRIC
+       (src/bsdfs/hdielectric.cpp: smooth dielectric whose eta is the RIF at the hit point, exterior index 1) or
+       MER_BSDF_HROUGHDIELECTRIC (its microfacet form: the rough_* fields at the end of this struct) */
     int32_t boundary_bsdf;
     /* boundary = MER_BOUNDARY_SDF: the medium shape is the negative region of this signed-distance grid (1-channel float32 volume,
        trilinear; the reference's `sdf` child of heterogeneousrefractive, src/medium/heterogeneousrefractive.cpp:366-375, negative
@@ -133,9 +134,17 @@ typedef struct {
        MIS partner (volpath.cpp:120-173,370-428).  All-zero radiance = none.  The rectangle lies outside the medium shape.  Straight rays
        (rif_mode = MER_RIF_CONST), index-matched cube / sphere boundary. */
     float   area_to_world[12], area_radiance[3];
+    /* boundary_bsdf = MER_BSDF_HROUGHDIELECTRIC (src/bsdfs/hroughdielectric.cpp: microfacet dielectric whose eta is the RIF at the hit point,
+       exterior index 1, eta taken as for hdielectric): MER_MICROFACET_* distribution, one isotropic roughness alpha (the XML default is 0.1;
+       clamped to >= 1e-4 as src/bsdfs/microfacet.h:131-136), and visible-normal sampling (Heitz & d'Eon 2014) or the full distribution with
+       Walter's alpha scaling 1.2 - 0.2 sqrt|cos theta_i| (0; always 0 for phong).  The surface vertex samples a point emitter that lies
+       outside the medium shape (volpath.cpp:230-262); interior vertices then do no emitter sampling toward it.  Refused: a point emitter inside the
+       shape, the area emitter.  All zero (with another boundary_bsdf): ignored. */
+    int32_t rough_distribution; float rough_alpha; int32_t rough_sample_visible;
 } mer_scene_desc;
 enum { MER_METHOD_WOODCOCK = 0, MER_METHOD_SIMPSON = 1 };
-enum { MER_BSDF_NULL = 0, MER_BSDF_HDIELECTRIC = 1 };
+enum { MER_BSDF_NULL = 0, MER_BSDF_HDIELECTRIC = 1, MER_BSDF_HROUGHDIELECTRIC = 2 };
+enum { MER_MICROFACET_BECKMANN = 0, MER_MICROFACET_GGX = 1, MER_MICROFACET_PHONG = 2 };   /* MicrofacetDistribution::EType order (microfacet.h) */
 enum { MER_MODULATION_NONE = 0, MER_MODULATION_SINE, MER_MODULATION_SQUARE, MER_MODULATION_HAMILTONIAN, MER_MODULATION_MSEQ,
        MER_MODULATION_DEPTHSELECTIVE };
 enum { MER_DECOMPOSITION_NONE = 0, MER_DECOMPOSITION_TRANSIENT = 1, MER_DECOMPOSITION_BOUNCE = 2 };
@@ -274,6 +283,13 @@ int  mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1,
 /* PhaseFunction::sample / eval (src/phase/hg.cpp:74-110, src/phase/isotropic.cpp:62-78) */
 int  mer_phase_sample(mer_context *ctx, int32_t phase, float g, const float *wi, const float *u2, int64_t n, float *wo, float *pdf);
 int  mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, const float *wo, int64_t n, float *val);
+/* RoughDielectric::eval / pdf and sample (src/bsdfs/hroughdielectric.cpp:131-289,383-507) of the scene's rough_* parameters, ERadiance, for
+   per-item eta (interior / exterior index).  Vectors in the local shading frame (z = the outward normal), wi pointing away from the surface.
+   out_val = f |cos theta_o|.  sample: u3[3*i..] = the microfacet sample (2D) and the reflect / refract choice; weight = eval / pdf (0: no sample) */
+int  mer_rough_dielectric_eval(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *wo, int64_t n,
+                               float *out_val, float *out_pdf);
+int  mer_rough_dielectric_sample(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *u3, int64_t n,
+                                 float *wo, float *weight, float *pdf);
 /* PerspectiveCamera::sampleRay (src/sensors/perspective.cpp:247-269) */
 int  mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, int64_t n, float *o, float *d);
 /* PathLengthSampler::correlationFunction for the scene's modulation (src/librender/pathlengthsampler.cpp:68-114) */

@@ -22,7 +22,8 @@ SYMBOLS = [
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
-    "mer_sample_distance", "mer_connect", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_camera_rays",
+    "mer_sample_distance", "mer_connect", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
+    "mer_rough_dielectric_sample", "mer_camera_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
@@ -66,7 +67,59 @@ class SceneDesc(C.Structure):
         ("ac_n_o", C.c_float), ("ac_n_max", C.c_float), ("ac_k_r", C.c_float), ("ac_mode", C.c_int32),
         ("method", C.c_int32), ("het_stepsize", C.c_float),
         ("area_to_world", C.c_float * 12), ("area_radiance", C.c_float * 3),
+        ("rough_distribution", C.c_int32), ("rough_alpha", C.c_float), ("rough_sample_visible", C.c_int32),
     ]
+
+
+def _sdf_value(p, x):
+    """the signed-distance grid of p at the world point x (trilinear, as the kernels look it up); off the grid: +inf (outside)"""
+    g = np.asarray(p.sdf, np.float64)
+    if g.ndim == 4:
+        g = g[..., 0]
+    if p.sdf_to_world is not None:
+        m = P.world_to_volume(p.sdf_to_world).astype(np.float64)
+        x = m[:, :3] @ x + m[:, 3]
+    lo, hi = np.asarray(p.sdf_aabb[0], np.float64), np.asarray(p.sdf_aabb[1], np.float64)
+    res = np.array(g.shape[::-1])                         # grids are [z][y][x]
+    c = (x - lo) * (res - 1) / (hi - lo)
+    i = np.floor(c).astype(int)
+    if np.any(i < 0) or np.any(i >= res - 1):
+        return np.inf
+    f = c - i
+    v = 0.0
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                w = (f[0] if dx else 1 - f[0]) * (f[1] if dy else 1 - f[1]) * (f[2] if dz else 1 - f[2])
+                v += w * g[i[2] + dz, i[1] + dy, i[0] + dx]
+    return v
+
+
+def validate_rough(p):
+    """The refusals of a rough dielectric boundary (mer_render / the host parser): MerError.  No GPU needed."""
+    if p.boundary_bsdf not in (P.BSDF_NULL, P.BSDF_HDIELECTRIC, P.BSDF_HROUGHDIELECTRIC):
+        raise MerError("boundary BSDF must be null, hdielectric or hroughdielectric")
+    if p.boundary_bsdf != P.BSDF_HROUGHDIELECTRIC:
+        return
+    if p.rough_distribution not in (P.MICROFACET_BECKMANN, P.MICROFACET_GGX, P.MICROFACET_PHONG):
+        raise MerError("hroughdielectric: distribution must be beckmann, ggx or phong")
+    if not (np.isfinite(p.rough_alpha) and p.rough_alpha >= 0):
+        raise MerError("hroughdielectric: alpha must be finite and >= 0")
+    if any(v != 0 for v in p.area_radiance):
+        raise MerError("hroughdielectric: the area emitter needs an index-matched (null) boundary")
+    if any(v != 0 for v in p.point_intensity):
+        x = np.asarray(p.point_position, np.float64)
+        if p.boundary == P.BOUNDARY_AABB:
+            inside = bool(np.all(x >= np.asarray(p.bmin)) and np.all(x <= np.asarray(p.bmax)))
+        elif p.boundary == P.BOUNDARY_SPHERE:
+            inside = float(np.sum((x - np.asarray(p.sph_center)) ** 2)) < p.sph_radius ** 2
+        elif p.sdf is not None:
+            inside = _sdf_value(p, x) < 0
+        else:
+            inside = False
+        if inside:
+            raise MerError("hroughdielectric: the point emitter must lie outside the medium shape "
+                           "(a curved connection that starts on the boundary is not built)")
 
 
 class Shard(C.Structure):
@@ -279,6 +332,11 @@ class Context:
         m = np.eye(4); t = np.asarray(p.area_to_world if p.area_to_world is not None else np.eye(4), np.float64); m[:t.shape[0], :4] = t
         s.area_to_world[:] = [float(v) for v in m[:3, :4].astype(np.float32).reshape(-1)]
         s.area_radiance[:] = p.area_radiance
+        validate_rough(p)
+        rough = p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC
+        s.rough_distribution = p.rough_distribution if rough else 0
+        s.rough_alpha = max(float(p.rough_alpha), 1e-4) if rough else 0.0
+        s.rough_sample_visible = int(bool(p.rough_sample_visible) and p.rough_distribution != P.MICROFACET_PHONG) if rough else 0
         return s
 
     def upload_scene(self, p, layout=LAYOUT_DENSE, rif_layout=None):
@@ -426,6 +484,20 @@ class Context:
         val = np.empty(n, np.float32)
         self._check(self.lib.mer_phase_eval(self.h, C.c_int32(kind), C.c_float(g), _fp(wi), _fp(wo), C.c_int64(n), _fp(val)))
         return val
+
+    def rough_eval(self, scene, eta, wi, wo):
+        """mer_rough_dielectric_eval: f |cos theta_o| and pdf of the scene's rough_* microfacet dielectric, local frame, eta per item"""
+        wi = _f32(wi); wo = _f32(wo); n = wi.shape[0]; eta = _f32(np.broadcast_to(np.asarray(eta, np.float32), (n,)))
+        val = np.empty(n, np.float32); pdf = np.empty(n, np.float32)
+        self._check(self.lib.mer_rough_dielectric_eval(self.h, C.byref(scene), _fp(eta), _fp(wi), _fp(wo), C.c_int64(n), _fp(val), _fp(pdf)))
+        return val, pdf
+
+    def rough_sample(self, scene, eta, wi, u3):
+        """mer_rough_dielectric_sample: wo, weight = eval / pdf (0: no sample), pdf; u3 = microfacet 2D + reflect / refract choice"""
+        wi = _f32(wi); u3 = _f32(u3); n = wi.shape[0]; eta = _f32(np.broadcast_to(np.asarray(eta, np.float32), (n,)))
+        wo = np.empty((n, 3), np.float32); w = np.empty(n, np.float32); pdf = np.empty(n, np.float32)
+        self._check(self.lib.mer_rough_dielectric_sample(self.h, C.byref(scene), _fp(eta), _fp(wi), _fp(u3), C.c_int64(n), _fp(wo), _fp(w), _fp(pdf)))
+        return wo, w, pdf
 
     def camera_rays(self, scene, pos2):
         pos2 = _f32(pos2); n = pos2.shape[0]

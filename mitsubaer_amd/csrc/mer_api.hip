@@ -115,6 +115,14 @@ static int film_frames(mer_context *ctx, const mer_scene_desc *sc, int &frames) 
     frames = (int) f;
     return 0;
 }
+// the microfacet parameters of MER_BSDF_HROUGHDIELECTRIC (microfacet.h:100-142: one isotropic alpha, clamped to >= 1e-4 on the device)
+static int check_rough(mer_context *ctx, const mer_scene_desc *sc) {
+    if (sc->rough_distribution < MER_MICROFACET_BECKMANN || sc->rough_distribution > MER_MICROFACET_PHONG)
+        return fail(ctx, "hroughdielectric: distribution must be beckmann, ggx or phong");
+    if (!(sc->rough_alpha >= 0) || !std::isfinite(sc->rough_alpha)) return fail(ctx, "hroughdielectric: alpha must be finite and >= 0");
+    if (sc->rough_sample_visible != 0 && sc->rough_sample_visible != 1) return fail(ctx, "hroughdielectric: sampleVisible must be 0 or 1");
+    return 0;
+}
 int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf) {
     std::memset(&P, 0, sizeof(P));
     P.sc = *sc;
@@ -251,7 +259,17 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         P.ftable = ctx->ftable;
     }
     if (P.fradius > 7.0f) return fail(ctx, "reconstruction filter radius too large");
-    if (sc->boundary_bsdf != MER_BSDF_NULL && sc->boundary_bsdf != MER_BSDF_HDIELECTRIC) return fail(ctx, "boundary BSDF must be null or hdielectric");
+    if (sc->boundary_bsdf != MER_BSDF_NULL && sc->boundary_bsdf != MER_BSDF_HDIELECTRIC && sc->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC)
+        return fail(ctx, "boundary BSDF must be null, hdielectric or hroughdielectric");
+    if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {
+        if (check_rough(ctx, sc)) return 1;
+        const bool point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
+        bool inside = false;
+        if (sc->boundary == MER_BOUNDARY_AABB) { inside = true; for (int i = 0; i < 3; i++) inside = inside && sc->point_position[i] >= sc->bmin[i] && sc->point_position[i] <= sc->bmax[i]; }
+        else if (sc->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (sc->point_position[i] - sc->sph_center[i]) * (sc->point_position[i] - sc->sph_center[i]); inside = d2 < sc->sph_radius * sc->sph_radius; }
+        // (a signed-distance shape: tested below, where its grid is known)
+        if (point && inside) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+    }
     P.has_area = (sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0) ? 1 : 0;
     if (P.has_area) {               // Rectangle::configure (src/shapes/rectangle.cpp:99-110)
         if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, "the area emitter is built for straight rays (rif_mode = CONST)");
@@ -299,6 +317,24 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         fill_dgrid(ctx, it->second, P.sdf);
         float d2 = 0; for (int i = 0; i < 3; i++) d2 += (P.sdf.bmax[i] - P.sdf.bmin[i]) * (P.sdf.bmax[i] - P.sdf.bmin[i]);
         P.sdf_eps = 1e-4f * std::sqrt(d2);
+        const bool point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
+        if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point) {      // the emitter inside the signed-distance shape: the grid's value there (sdf_value)
+            const DGrid &g = P.sdf; const float *q = sc->point_position;
+            float c[3];
+            for (int i = 0; i < 3; i++) c[i] = g.m[4 * i] * q[0] + g.m[4 * i + 1] * q[1] + g.m[4 * i + 2] * q[2] + g.m[4 * i + 3];
+            const int x1 = (int) std::floor(c[0]), y1 = (int) std::floor(c[1]), z1 = (int) std::floor(c[2]);
+            if (x1 >= 0 && y1 >= 0 && z1 >= 0 && x1 < g.res[0] - 1 && y1 < g.res[1] - 1 && z1 < g.res[2] - 1) {     // off the grid: outside
+                float v = 0;
+                for (int k = 0; k < 8; k++) {
+                    const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
+                    float corner;
+                    HIP_CHECK(ctx, hipMemcpy(&corner, (const float *) g.data + ((size_t) (z1 + dz) * g.res[1] + (y1 + dy)) * g.res[0] + (x1 + dx), 4, hipMemcpyDeviceToHost));
+                    const float fx = c[0] - x1, fy = c[1] - y1, fz = c[2] - z1;
+                    v += (dx ? fx : 1 - fx) * (dy ? fy : 1 - fy) * (dz ? fz : 1 - fz) * corner;
+                }
+                if (v < 0) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+            }
+        }
     } else return fail(ctx, "unknown medium boundary");
     if (sc->aggressive_tracing) {
         if (sc->boundary != MER_BOUNDARY_SDF) return fail(ctx, "aggressivetracing needs the signed-distance boundary (the medium's sdf volume)");
@@ -964,6 +1000,30 @@ int mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, co
     hipLaunchKernelGGL(phase_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, phase, g, a.as<float>(), b.as<float>(), n, c.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
     return c.download(val, n * 4);
+}
+int mer_rough_dielectric_eval(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *wo, int64_t n,
+                              float *out_val, float *out_pdf) {
+    MER_USE_DEVICE(ctx);
+    if (check_rough(ctx, scene)) return 1;
+    DevBuf a(ctx), b(ctx), c(ctx), e(ctx), f(ctx);
+    if (a.upload(eta, n * 4) || b.upload(wi, n * 12) || c.upload(wo, n * 12) || e.alloc(n * 4) || f.alloc(n * 4)) return 1;
+    hipLaunchKernelGGL(rough_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, scene->rough_distribution, scene->rough_alpha,
+                       scene->rough_sample_visible, a.as<float>(), b.as<float>(), c.as<float>(), n, e.as<float>(), f.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    if (e.download(out_val, n * 4)) return 1;
+    return f.download(out_pdf, n * 4);
+}
+int mer_rough_dielectric_sample(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *u3, int64_t n,
+                                float *wo, float *weight, float *pdf) {
+    MER_USE_DEVICE(ctx);
+    if (check_rough(ctx, scene)) return 1;
+    DevBuf a(ctx), b(ctx), c(ctx), e(ctx), f(ctx), g(ctx);
+    if (a.upload(eta, n * 4) || b.upload(wi, n * 12) || c.upload(u3, n * 12) || e.alloc(n * 12) || f.alloc(n * 4) || g.alloc(n * 4)) return 1;
+    hipLaunchKernelGGL(rough_sample_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, scene->rough_distribution, scene->rough_alpha,
+                       scene->rough_sample_visible, a.as<float>(), b.as<float>(), c.as<float>(), n, e.as<float>(), f.as<float>(), g.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    if (e.download(wo, n * 12) || f.download(weight, n * 4)) return 1;
+    return g.download(pdf, n * 4);
 }
 int mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, int64_t n, float *o, float *d) {
     MER_USE_DEVICE(ctx);

@@ -919,17 +919,10 @@ __device__ __forceinline__ float fresnel_dielectric_ext(float cosThetaI_, float 
     cosThetaT_ = (cosThetaI_ > 0) ? -cosThetaT : cosThetaT;
     return 0.5f * (Rs * Rs + Rp * Rp);
 }
-// HDielectric::sample (src/bsdfs/hdielectric.cpp:183-242, ERadiance) at the boundary point ro + rd*t of the medium shape; eta is the
-// RIF there (:115-118).  Returns true when the sampled direction wo stays in / enters the medium.
-template <bool CURVED, int RIF, int BND = 0>
-__device__ __forceinline__ bool dielectric_event(const Params &P, Rng &rng, f3 ro, f3 rd, float t, bool from_inside, f3 &T, float &etaPath,
-                                                 f3 &x, f3 &wo) {
-    const mer_scene_desc &S = P.sc;
-    const float u1 = rng.next1D(); (void) rng.next1D();          // only sample.x is used (:196)
-    x = ro + rd * t;
-    const f3 n = shape_normal_b<BND>(P, x);
-    const float cosI = dot(-rd, n);                              // Frame::cosTheta(wi), wi = -ray.d
-    float etaB = S.rif_const;
+// eta of the dielectric boundary at its point x: the RIF there (hdielectric.cpp:115-118, hroughdielectric.cpp:509-512)
+template <bool CURVED, int RIF>
+__device__ __forceinline__ float boundary_eta(const Params &P, f3 x) {
+    float etaB = P.sc.rif_const;
     if (CURVED) {
         f3 q = x; f3 g; CellCache cc; cc.reset();
         if (RIF != RIFK_ACOUSTIC && !P.rif.affine) {             // the analytic field has no grid to stay inside of; a transformed one clamps its cell
@@ -938,6 +931,18 @@ __device__ __forceinline__ bool dielectric_event(const Params &P, Rng &rng, f3 r
         }
         rif_value_grad<RIF>(P.rif, cc, q, etaB, g);
     }
+    return etaB;
+}
+// HDielectric::sample (src/bsdfs/hdielectric.cpp:183-242, ERadiance) at the boundary point ro + rd*t of the medium shape; eta is the
+// RIF there (:115-118).  Returns true when the sampled direction wo stays in / enters the medium.
+template <bool CURVED, int RIF, int BND = 0>
+__device__ __forceinline__ bool dielectric_event(const Params &P, Rng &rng, f3 ro, f3 rd, float t, bool from_inside, f3 &T, float &etaPath,
+                                                 f3 &x, f3 &wo) {
+    const float u1 = rng.next1D(); (void) rng.next1D();          // only sample.x is used (:196)
+    x = ro + rd * t;
+    const f3 n = shape_normal_b<BND>(P, x);
+    const float cosI = dot(-rd, n);                              // Frame::cosTheta(wi), wi = -ray.d
+    const float etaB = boundary_eta<CURVED, RIF>(P, x);
     const float invEtaB = 1 / etaB;
     float cosT; const float F = fresnel_dielectric_ext(cosI, cosT, etaB);
     if (u1 <= F) { wo = rd + n * (2 * cosI); return from_inside; }                   // reflect(wi): 2 (wi.n) n - wi

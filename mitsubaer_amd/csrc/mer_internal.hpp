@@ -112,7 +112,7 @@ struct Run {
 // the kernels of one (CURVED, RIF, STEPPER, SIGMA, BND) combination, as launchable function pointers
 typedef void (*GenKernel)(const Params);
 typedef void (*PassKernel)(const Params, uint32_t);
-struct KernelSet { GenKernel gen; PassKernel event, march, connect, connect_cross, march_lds, event_inline; };   // event_inline: K_event that runs straight walks itself (or null)   // connect_cross: the point emitter lies outside the medium shape;
+struct KernelSet { GenKernel gen; PassKernel event, march, connect, connect_cross, march_lds, event_inline, event_rough, event_inline_rough; };   // event_rough / event_inline_rough: the K_event instances of a rough dielectric boundary   // event_inline: K_event that runs straight walks itself (or null)   // connect_cross: the point emitter lies outside the medium shape;
                                                                                                     // march_lds: K_march with LDS-staged BRICK27 records (or null)
 // each mer_render_<group>.hip answers for the combinations it instantiates (returns false if the combination is not in its group)
 bool kernels_straight(int sigma, int bnd, bool extra, KernelSet &k);

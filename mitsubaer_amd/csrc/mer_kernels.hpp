@@ -3,6 +3,7 @@
 #pragma once
 #include "mer_walk.hpp"
 #include "mer_connect.hpp"
+#include "mer_microfacet.hpp"
 
 namespace mer {
 
@@ -146,6 +147,23 @@ __global__ void phase_eval_kernel(int kind, float g, const float *wi, const floa
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     val[i] = phase_eval(kind, g, f3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]));
+}
+__global__ void rough_eval_kernel(int type, float alpha, int visible, const float *eta, const float *wi, const float *wo, int64_t n, float *val, float *pdf) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Microfacet d = microfacet_make(type, alpha, visible);
+    float p;
+    val[i] = rough_dielectric_eval(d, eta[i], f3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), p);
+    pdf[i] = p;
+}
+__global__ void rough_sample_kernel(int type, float alpha, int visible, const float *eta, const float *wi, const float *u3, int64_t n, float *wo,
+                                    float *weight, float *pdf) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Microfacet d = microfacet_make(type, alpha, visible);
+    f3 o; float p, e;
+    weight[i] = rough_dielectric_sample(d, eta[i], f3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), u3[3 * i], u3[3 * i + 1], u3[3 * i + 2], o, p, e);
+    wo[3 * i] = o.x; wo[3 * i + 1] = o.y; wo[3 * i + 2] = o.z; pdf[i] = p;
 }
 __global__ void camera_rays_kernel(const Params P, const float *pos2, int64_t n, float *o, float *d) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;

@@ -149,8 +149,10 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     }
     // straight rays through a gridded sigma_t: K_event runs every walk itself (a walk is ~3 tentative collisions: the hand-over to K_march costs
     // more than the walk).  K_march is still launched: its list is empty, and it is where the hit ring's head is clamped between passes.
-    if (opt.inline_walks && ks.event_inline && !curved && scene->method != MER_METHOD_SIMPSON) ks.event = ks.event_inline;
-    const bool connect_stage = has_point && curved;
+    const bool inline_walks = opt.inline_walks && ks.event_inline && !curved && scene->method != MER_METHOD_SIMPSON;
+    if (inline_walks) ks.event = ks.event_inline;
+    if (scene->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) ks.event = inline_walks ? ks.event_inline_rough : ks.event_rough;   // its own instances (mer_wavefront.hpp)
+    const bool connect_stage = has_point && curved && scene->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC;   // a rough boundary: the surface vertex samples the emitter
     if (connect_stage) {            // an emitter outside the shape is reached through the boundary: the kernel that carries the refraction code
         bool inside = false;        // (signed-distance shapes: the plain kernel carries it too, the side is tested per connection)
         if (scene->boundary == MER_BOUNDARY_AABB) { inside = true; for (int i = 0; i < 3; i++) inside = inside && scene->point_position[i] >= scene->bmin[i] && scene->point_position[i] <= scene->bmax[i]; }

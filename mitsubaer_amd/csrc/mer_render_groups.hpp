@@ -21,6 +21,9 @@ static inline void fill_kernels(bool extra, KernelSet &k) {
         if (extra || X) k.event_inline = event_kernel<CURVED, RIF, STEPPER, SIGMA, true, BND, true>;
         else k.event_inline = event_kernel<CURVED, RIF, STEPPER, SIGMA, X, BND, true>;
     }
+    k.event_rough = event_kernel<CURVED, RIF, STEPPER, SIGMA, true, BND, false, true>;
+    k.event_inline_rough = nullptr;
+    if constexpr (!CURVED && SIGMA == MER_SIGMA_GRID) k.event_inline_rough = event_kernel<CURVED, RIF, STEPPER, SIGMA, true, BND, true, true>;
     k.march = march_kernel<CURVED, RIF, STEPPER, SIGMA, BND>;
     if constexpr (RIF == RIFK_BRICK27_BUF) k.march_lds = march_kernel<CURVED, RIFK_BRICK27_LDS, STEPPER, SIGMA, BND>;
     else k.march_lds = nullptr;

@@ -11,6 +11,7 @@
 #pragma once
 #include "mer_walk.hpp"
 #include "mer_connect.hpp"
+#include "mer_microfacet.hpp"
 
 namespace mer {
 
@@ -211,7 +212,7 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                 if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P, d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
                 else if (itsT < 0) { if (!S.hide_emitters) L = env; }
                 else if (1 >= maxDepth && maxDepth != -1) { }
-                else if (EXTRA && S.boundary_bsdf == MER_BSDF_HDIELECTRIC) hit = true;      // Fresnel sampling at the surface: K_event
+                else if (EXTRA && S.boundary_bsdf != MER_BSDF_NULL) hit = true;      // Fresnel / microfacet sampling at the surface: K_event
                 else {
                     bool medium = true;
                     if (!CURVED) { const f3 ro = o + d * itsT; medium = intersect_shape_b<BND>(P, ro, d, MER_EPSILON, MER_INF) >= 0; }
@@ -561,8 +562,11 @@ static __device__ unsigned long long mer_prof[256 * 16];      // 256 replicas (b
 #ifndef MER_INLINE_EVENT_WAVES
 #define MER_INLINE_EVENT_WAVES 1
 #endif
-template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool EXTRA, int BND = 0, bool INLINE = false>
+// ROUGH (EXTRA only): the instance for a rough dielectric boundary (hroughdielectric).  Its surface branch is an instantiation of its own so that the
+// other EXTRA instances carry none of its registers (the B-spline one was at the 256-VGPR limit): mer_render selects it for such scenes only.
+template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool EXTRA, int BND = 0, bool INLINE = false, bool ROUGH = false>
 __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : MER_EVENT_WAVES) event_kernel(const Params P, uint32_t pass) {
+    static_assert(!ROUGH || EXTRA, "the rough boundary lives in the EXTRA kernels");
     typedef Walk<CURVED, RIF, STEPPER, SIGMA, BND> WalkT;
     const uint32_t j = blockIdx.x * MER_BLOCK + threadIdx.x;
     if (j >= P.nslots_all) return;
@@ -585,7 +589,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
 
     const mer_scene_desc &S = P.sc;
     const f3 env(S.env_radiance[0], S.env_radiance[1], S.env_radiance[2]);
-    const bool dielectric = EXTRA && S.boundary_bsdf == MER_BSDF_HDIELECTRIC;
+    constexpr bool rough = ROUGH;                 // hroughdielectric (the host selects this instance for it): the surface vertex samples the point emitter
+    const bool dielectric = EXTRA && (rough || S.boundary_bsdf == MER_BSDF_HDIELECTRIC);
     // a dielectric boundary blocks emitter sampling and look-ups from inside: the environment is reached by refracting out
     const bool hasEnv = !is_zero(env) && !dielectric;
     const bool hasEmission = S.emission[0] != 0 || S.emission[1] != 0 || S.emission[2] != 0;
@@ -687,10 +692,16 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 ev = EV_PATH_DONE;
             } else if (depth >= maxDepth && maxDepth != -1) ev = EV_PATH_DONE;
             else if (dielectric) {
-                // hdielectric boundary (N2): reflect away (the ray escapes: environment, weight 1) or refract into the medium
+                // hdielectric / hroughdielectric boundary (N2): reflect away (the ray escapes: environment, weight 1) or refract into the medium
                 if (camera_edge_counts(P)) plen += edge_length(P, itsT);
                 f3 x, wo;
-                if (!dielectric_event<CURVED, RIF, BND>(P, rng, o, d, itsT, false, T, etaPath, x, wo)) {
+                bool enters;
+                if constexpr (rough) {
+                    f3 Le; float eLen;
+                    enters = rough_event<CURVED, RIF, BND>(P, rng, o, d, itsT, T, etaPath, x, wo, Le, eLen) == 2;      // T = 0 if the path ends
+                    if (!is_zero(Le)) { const float pl = plen + edge_length(P, eLen); L = L + mod_weight<EXTRA>(P, Le, pl); film_contribute(P, px, py, Le, pl); }
+                } else enters = dielectric_event<CURVED, RIF, BND>(P, rng, o, d, itsT, false, T, etaPath, x, wo);
+                if (!enters) {
                     L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen);
                     ev = EV_PATH_DONE;
                 } else {
@@ -862,6 +873,12 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             // ---- luminaire sampling of the point emitter, if any (after the environment NEE, as in the oracle's draw order).
             // Curved rays: the connection is a shooting problem of hundreds of sensitivity steps -- it gets a kernel of its
             // own (K_connect) in which every lane solves one; the path resumes at EV_PHASE2 in the next pass.
+            if (EXTRA && hasPoint && ev == EV_PHASE && rough) {
+                // a rough boundary is a non-null surface: the shadow ray toward the (outside) emitter stops at it; the emitter sample is drawn
+                // (volpath's nextSample2D) and contributes nothing.  The surface vertex samples the emitter instead (rough_event).
+                C.nee++;
+                (void) rng.next1D(); (void) rng.next1D();
+            } else
             if (EXTRA && hasPoint && ev == EV_PHASE) {
                 if (CURVED) {                        // park the slot: K_connect takes the connection from here (state CP_NEW)
                     connecting = true;
@@ -961,11 +978,17 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             if (CURVED) { T = T * m.refRatioSq; SET_FLAG(F_ITSVALID, true); }         // edge.cpp:45-60
             ev = EV_PATH_DONE;
             if (dielectric && itsValid && !(depth >= maxDepth && maxDepth != -1)) {
-                // hdielectric boundary from inside: total internal / Fresnel reflection keeps the path in the medium
+                // dielectric boundary from inside: total internal / Fresnel (or microfacet) reflection keeps the path in the medium
                 f3 ro = ps, rd = dsave; float tHit = itsT;
                 if (CURVED) { ro = m.p; rd = normalize(m.d); tHit = intersect_shape_b<BND>(P, ro, rd, 0.0f, MER_INF); if (!(tHit >= 0)) tHit = 0.0f; }   // re-hit (edge.cpp:45-60)
                 f3 x, wo;
-                if (!dielectric_event<CURVED, RIF, BND>(P, rng, ro, rd, tHit, true, T, etaPath, x, wo)) {
+                bool stays;
+                if constexpr (rough) {
+                    f3 Le; float eLen;
+                    stays = rough_event<CURVED, RIF, BND>(P, rng, ro, rd, tHit, T, etaPath, x, wo, Le, eLen) == 2;      // T = 0 if the path ends
+                    if (!is_zero(Le)) { const float pl = plen + edge_length(P, eLen); L = L + mod_weight<EXTRA>(P, Le, pl); film_contribute(P, px, py, Le, pl); }
+                } else stays = dielectric_event<CURVED, RIF, BND>(P, rng, ro, rd, tHit, true, T, etaPath, x, wo);
+                if (!stays) {
                     L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen);
                 } else {
                     ps = x; dsave = wo;

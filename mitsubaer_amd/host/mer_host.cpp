@@ -173,7 +173,7 @@ void Shape::addChild(const std::string &name, ObjRef child) {
     if (cls == "Medium") {
         if (name == "interior") {
             interior = std::static_pointer_cast<Medium>(child);
-            if (interior->isheterogeneousrefractive() && hasBSDF && bsdf != MER_BSDF_HDIELECTRIC)        // shape.cpp:172-176
+            if (interior->isheterogeneousrefractive() && hasBSDF && bsdf != MER_BSDF_HDIELECTRIC && bsdf != MER_BSDF_HROUGHDIELECTRIC)   // shape.cpp:172-176
                 Log_EError("A shape with heterogeneous refractive index medium should only have a bsdf that is also heterogeneous!");
         } else if (name == "exterior") Log_EError("Shape: an 'exterior' medium is not supported on the GPU path (the sensor must be in vacuum)");
         else Log_EError("Shape: Invalid medium child (must be named 'interior' or 'exterior')!");    // shape.cpp:186-188
@@ -426,7 +426,28 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             o->kind = MER_BSDF_HDIELECTRIC;
             const Spectrum r = props.getSpectrum("specularReflectance", Spectrum{{1, 1, 1}}), t = props.getSpectrum("specularTransmittance", Spectrum{{1, 1, 1}});
             for (int i = 0; i < 3; i++) if (r.c[i] != 1.0f || t.c[i] != 1.0f) Log_EError("hdielectric: specularReflectance / specularTransmittance other than 1 are not supported on the GPU path");
-        } else Log_EError("bsdf \"" + type + "\" is not supported on the GPU path (null, hdielectric)");
+        } else if (type == "hroughdielectric") {                          // src/bsdfs/hroughdielectric.cpp:47-80, microfacet.h:100-142
+            o->kind = MER_BSDF_HROUGHDIELECTRIC;
+            const Spectrum r = props.getSpectrum("specularReflectance", Spectrum{{1, 1, 1}}), t = props.getSpectrum("specularTransmittance", Spectrum{{1, 1, 1}});
+            for (int i = 0; i < 3; i++) if (r.c[i] != 1.0f || t.c[i] != 1.0f) Log_EError("hroughdielectric: specularReflectance / specularTransmittance other than 1 are not supported on the GPU path");
+            const std::string dist = lower(props.getString("distribution", "beckmann"));
+            if (dist == "beckmann") o->distribution = MER_MICROFACET_BECKMANN;
+            else if (dist == "ggx") o->distribution = MER_MICROFACET_GGX;
+            else if (dist == "phong") o->distribution = MER_MICROFACET_PHONG;
+            else if (dist == "as") Log_EError("hroughdielectric: the anisotropic 'as' distribution is not supported on the GPU path");
+            else Log_EError("Specified an invalid distribution \"" + dist + "\", must be \"beckmann\", \"ggx\", \"phong\" or \"as\"!");
+            if (props.hasProperty("alpha")) o->alpha = props.getFloat("alpha");
+            else if (props.hasProperty("alphaU") || props.hasProperty("alphaV")) {
+                if (!props.hasProperty("alphaU") || !props.hasProperty("alphaV")) Log_EError("Microfacet model: please specify either 'alpha' or 'alphaU'/'alphaV'.");
+                const float au = props.getFloat("alphaU"), av = props.getFloat("alphaV");
+                if (au != av) Log_EError("hroughdielectric: anisotropic roughness (alphaU != alphaV) is not supported on the GPU path");
+                o->alpha = au;
+            }
+            if (!(o->alpha >= 0) || !std::isfinite(o->alpha)) Log_EError("hroughdielectric: alpha must be finite and >= 0");
+            o->alpha = std::max(o->alpha, 1e-4f);                             // microfacet.h:131-136
+            o->sampleVisible = props.getBoolean("sampleVisible", true);
+            if (o->distribution == MER_MICROFACET_PHONG) o->sampleVisible = false;     // microfacet.h:137-142
+        } else Log_EError("bsdf \"" + type + "\" is not supported on the GPU path (null, hdielectric, hroughdielectric)");
         out = o;
     } else if (tag == "emitter") {
         auto o = std::make_shared<Emitter>();
@@ -623,7 +644,8 @@ struct Loader {
         }
         ObjRef obj = createObject(n.tag, props, baseDir);
         if (n.tag == "shape") for (auto &ch : children) if (std::string(ch.second->getClassName()) == "BSDF") {
-            std::static_pointer_cast<Shape>(obj)->hasBSDF = true; std::static_pointer_cast<Shape>(obj)->bsdf = std::static_pointer_cast<BSDF>(ch.second)->kind; }
+            std::static_pointer_cast<Shape>(obj)->hasBSDF = true; std::static_pointer_cast<Shape>(obj)->bsdf = std::static_pointer_cast<BSDF>(ch.second)->kind;
+            std::static_pointer_cast<Shape>(obj)->bsdfObj = std::static_pointer_cast<BSDF>(ch.second); }
         for (auto &ch : children) obj->addChild(ch.first, ch.second);
         obj->configure();
         if (n.attr.count("id")) byId[subst(n.attr.at("id"))] = obj;
@@ -655,6 +677,34 @@ std::shared_ptr<Scene> loadScene(const std::string &path, const std::map<std::st
 }
 
 // ------------------------------------------------------------------------------------------------ integrator
+// the point emitter inside the medium shape: cube, sphere, or the negative region of the signed-distance grid (trilinear, as lookupFloat)
+static bool point_inside_shape(const mer_scene_desc &d, const Medium &m) {
+    const float *p = d.point_position;
+    if (d.boundary == MER_BOUNDARY_SPHERE) {
+        float d2 = 0; for (int i = 0; i < 3; i++) d2 += (p[i] - d.sph_center[i]) * (p[i] - d.sph_center[i]);
+        return d2 < d.sph_radius * d.sph_radius;
+    }
+    if (d.boundary != MER_BOUNDARY_SDF) { bool in = true; for (int i = 0; i < 3; i++) in = in && p[i] >= d.bmin[i] && p[i] <= d.bmax[i]; return in; }
+    const VolumeDataSource &v = *m.sdf;
+    const float *W = v.worldToVolume; bool ident = true; for (int i = 0; i < 12; i++) ident = ident && W[i] == 0.0f;
+    float q[3];
+    for (int r = 0; r < 3; r++) q[r] = ident ? p[r] : W[4 * r] * p[0] + W[4 * r + 1] * p[1] + W[4 * r + 2] * p[2] + W[4 * r + 3];
+    int c[3]; float f[3];
+    for (int i = 0; i < 3; i++) {
+        const float g = (q[i] - v.aabb_min[i]) * (v.res[i] - 1) / (v.aabb_max[i] - v.aabb_min[i]);
+        c[i] = (int) std::floor(g); f[i] = g - c[i];
+        if (!(g == g) || c[i] < 0 || c[i] >= v.res[i] - 1) return false;              // off the grid: outside (lookupFloat returns 0 there: "far")
+    }
+    const float *data = (const float *) v.data.data();
+    float val = 0;
+    for (int k = 0; k < 8; k++) {
+        const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
+        const float w = (dx ? f[0] : 1 - f[0]) * (dy ? f[1] : 1 - f[1]) * (dz ? f[2] : 1 - f[2]);
+        val += w * data[((size_t) (c[2] + dz) * v.res[1] + (c[1] + dy)) * v.res[0] + (c[0] + dx)];
+    }
+    return val < 0;
+}
+
 void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     std::memset(&d, 0, sizeof(d));
     const Sensor &se = *scene.sensor; const Film &fi = *se.film;
@@ -676,6 +726,10 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     for (auto &s : scene.shapes) if (s->interior) { if (shape) Log_EError("Only one shape with an interior medium is supported on the GPU path"); shape = s.get(); }
     if (!shape) Log_EError("No shape with an 'interior' medium was found");
     d.boundary = shape->boundary; d.boundary_bsdf = shape->bsdf; d.sdf = 0;
+    d.rough_distribution = 0; d.rough_alpha = 0.0f; d.rough_sample_visible = 0;
+    if (shape->bsdf == MER_BSDF_HROUGHDIELECTRIC) {
+        d.rough_distribution = shape->bsdfObj->distribution; d.rough_alpha = shape->bsdfObj->alpha; d.rough_sample_visible = shape->bsdfObj->sampleVisible ? 1 : 0;
+    }
     for (int i = 0; i < 3; i++) { d.bmin[i] = shape->bmin[i]; d.bmax[i] = shape->bmax[i]; d.sph_center[i] = shape->center[i]; }
     d.sph_radius = shape->radius;
     const Medium &m = *shape->interior;
@@ -731,6 +785,10 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
             if (++nconst > 1) Log_EError("Only one constant emitter is supported on the GPU path");
             for (int i = 0; i < 3; i++) d.env_radiance[i] = e->radiance.c[i];
         }
+    }
+    if (d.boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {
+        if (narea) Log_EError("hroughdielectric: the area emitter needs an index-matched (null) boundary");
+        if (npoint && point_inside_shape(d, m)) Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
 }
 

@@ -135,15 +135,18 @@ public:
     std::shared_ptr<Medium> interior;
     bool isRectangle = false; float rectToWorld[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};   ///< `rectangle` (src/shapes/rectangle.cpp): carrier of an area emitter
     std::shared_ptr<class Emitter> areaEmitter;
-    bool hasBSDF = false;              ///< a bsdf child was given (null | hdielectric)
+    bool hasBSDF = false;              ///< a bsdf child was given (null | hdielectric | hroughdielectric)
     int bsdf = MER_BSDF_NULL;          ///< MER_BSDF_*
+    std::shared_ptr<class BSDF> bsdfObj;
 };
-/// BSDF of the medium shape: `null` (index-matched) or `hdielectric` (src/bsdfs/hdielectric.cpp: eta = RIF at the hit point)
+/// BSDF of the medium shape: `null` (index-matched), `hdielectric` (src/bsdfs/hdielectric.cpp: eta = RIF at the hit point) or
+/// `hroughdielectric` (src/bsdfs/hroughdielectric.cpp: its microfacet form; distribution, alpha (clamped to >= 1e-4), sampleVisible)
 class BSDF : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "BSDF"; }
     int kind = MER_BSDF_NULL;
-    bool isheterogeneousbsdf() const { return kind == MER_BSDF_HDIELECTRIC; }
+    int distribution = MER_MICROFACET_BECKMANN; float alpha = 0.1f; bool sampleVisible = true;
+    bool isheterogeneousbsdf() const { return kind == MER_BSDF_HDIELECTRIC || kind == MER_BSDF_HROUGHDIELECTRIC; }   // hroughdielectric.cpp:59
 };
 
 class ReconstructionFilter : public ConfigurableObject {

@@ -21,7 +21,8 @@ FILTER_BOX, FILTER_GAUSSIAN = 0, 1
 ALBEDO_CONST, ALBEDO_GRID = 0, 1
 DECOMPOSITION_NONE, DECOMPOSITION_TRANSIENT, DECOMPOSITION_BOUNCE = 0, 1, 2
 METHOD_WOODCOCK, METHOD_SIMPSON = 0, 1
-BSDF_NULL, BSDF_HDIELECTRIC = 0, 1
+BSDF_NULL, BSDF_HDIELECTRIC, BSDF_HROUGHDIELECTRIC = 0, 1, 2
+MICROFACET_BECKMANN, MICROFACET_GGX, MICROFACET_PHONG = 0, 1, 2
 MODULATION_NONE, MODULATION_SINE, MODULATION_SQUARE, MODULATION_HAMILTONIAN, MODULATION_MSEQ, MODULATION_DEPTHSELECTIVE = 0, 1, 2, 3, 4, 5
 
 
@@ -74,6 +75,9 @@ class SceneParams:
         # shape: cube [-1,1]^3 (scenes/volumetric/bounds.obj), null BSDF
         self.boundary = BOUNDARY_AABB
         self.boundary_bsdf = BSDF_NULL                            # BSDF_HDIELECTRIC: smooth dielectric, eta = RIF at the hit point
+        # BSDF_HROUGHDIELECTRIC (src/bsdfs/hroughdielectric.cpp): its microfacet form -- distribution, isotropic alpha (clamped to >= 1e-4),
+        # visible-normal sampling (off for phong)
+        self.rough_distribution = MICROFACET_BECKMANN; self.rough_alpha = 0.1; self.rough_sample_visible = True
         self.bmin = [-1.0, -1.0, -1.0]; self.bmax = [1.0, 1.0, 1.0]
         self.sph_center = [0.0, 0.0, 0.0]; self.sph_radius = 1.0
         self.sdf = None; self.sdf_aabb = ([-1, -1, -1], [1, 1, 1])    # BOUNDARY_SDF: signed-distance grid, negative inside

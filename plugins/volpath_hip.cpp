@@ -196,8 +196,48 @@ public:
         const BSDF *bsdf = shape->getBSDF();
         const std::string bsdfName = bsdf ? bsdf->getClass()->getName() : "Null";
         if (bsdfName == "HDielectric") d.boundary_bsdf = MER_BSDF_HDIELECTRIC;
+        else if (bsdfName == "HRoughDielectric") {
+            /* src/bsdfs/hroughdielectric.cpp: the BSDF keeps its parameters private; the distribution and sampleVisible are read from its
+               toString() (:520-532), alpha from getRoughness() (:515-518, a constant texture ignores the intersection), anisotropy and
+               textured alpha from the type flags configure() sets (:76-82).  A point emitter inside the shape and the area emitter are
+               refused by mer_render. */
+            d.boundary_bsdf = MER_BSDF_HROUGHDIELECTRIC;
+            if (bsdf->getType() & (BSDF::EAnisotropic | BSDF::ESpatiallyVarying))
+                Log(EError, "volpath_hip: hroughdielectric needs one constant isotropic alpha (no alphaU != alphaV, no textured alpha)");
+            const std::string desc = bsdf->toString();
+            auto field = [&](const char *key) -> std::string {
+                const size_t at = desc.find(key);
+                if (at == std::string::npos) return "";
+                const size_t b = at + strlen(key), e = desc.find_first_of(",\n", b);
+                return desc.substr(b, e == std::string::npos ? std::string::npos : e - b);
+            };
+            const std::string dist = field("distribution = ");
+            if (dist == "beckmann") d.rough_distribution = MER_MICROFACET_BECKMANN;
+            else if (dist == "ggx") d.rough_distribution = MER_MICROFACET_GGX;
+            else if (dist == "phong") d.rough_distribution = MER_MICROFACET_PHONG;
+            else Log(EError, "volpath_hip: hroughdielectric distribution \"%s\" is not supported (beckmann, ggx, phong)", dist.c_str());
+            d.rough_sample_visible = (field("sampleVisible = ") == "1" && d.rough_distribution != MER_MICROFACET_PHONG) ? 1 : 0;
+            Intersection its;
+            d.rough_alpha = (float) bsdf->getRoughness(its, 0);
+            /* specularReflectance / specularTransmittance: a constant texture prints its Spectrum, "[v0, v1, v2]" (ConstantSpectrumTexture::toString,
+               include/mitsuba/hw/basicshader.h; Spectrum::toString, include/mitsuba/core/spectrum.h:590-600); anything else is refused too */
+            for (const char *key : {"specularReflectance = ", "specularTransmittance = "}) {
+                const size_t at = desc.find(key);
+                const size_t b = at == std::string::npos ? at : at + strlen(key);
+                const size_t e = b == std::string::npos ? b : desc.find(']', b);
+                bool unit = b != std::string::npos && e != std::string::npos && desc[b] == '[';
+                for (size_t q = b + 1; unit && q < e;) {
+                    char *end = NULL;
+                    const double v = strtod(desc.c_str() + q, &end);
+                    unit = end != desc.c_str() + q && v == 1.0;
+                    q = (size_t) (end - desc.c_str());
+                    while (q < e && (desc[q] == ',' || desc[q] == ' ')) q++;
+                }
+                if (!unit) Log(EError, "volpath_hip: hroughdielectric: specularReflectance / specularTransmittance other than 1 are not supported");
+            }
+        }
         else if (bsdfName == "Null") d.boundary_bsdf = MER_BSDF_NULL;               /* no BSDF => `null` (src/librender/shape.cpp:48-70) */
-        else Log(EError, "volpath_hip: the medium shape's BSDF must be null or hdielectric");
+        else Log(EError, "volpath_hip: the medium shape's BSDF must be null, hdielectric or hroughdielectric");
 
         /* ---- medium, phase function, volumes */
         fillMedium(ctx, shape->getInteriorMedium(), d, volumes);
