@@ -56,6 +56,20 @@ typedef struct {
     float   world_to_volume[12];
 } mer_grid_desc;
 
+/* One entry of mer_scene_desc.emitters (Scene::getEmitters, src/librender/scene.cpp:854-898).  MER_EMITTER_POINT: emitter `point`
+   (position, intensity -- as point_position / point_intensity); MER_EMITTER_AREA: emitter `area` on a `rectangle` (to_world, radiance --
+   as area_to_world / area_radiance).  The fields of the other kind are ignored.  sampling_weight = the emitter's `samplingWeight`
+   (src/librender/emitter.cpp:103; > 0, 1 in the XML by default): at every collision ONE emitter of each kind is sampled, emitter k with
+   probability sampling_weight_k / (sum of the weights of its kind), and its sample is divided by that probability. */
+#define MER_MAX_EMITTERS 32
+enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2 };
+typedef struct {
+    int32_t type;
+    float   position[3], intensity[3];
+    float   to_world[12], radiance[3];
+    float   sampling_weight;
+} mer_emitter;
+
 /* Flat scene: what Integrator::render() (include/mitsuba/render/integrator.h:74) sees through
    Scene/Sensor/Film/Medium/PhaseFunction/VolumeDataSource/Emitter objects. */
 typedef struct {
@@ -134,6 +148,15 @@ typedef struct {
        MIS partner (volpath.cpp:120-173,370-428).  All-zero radiance = none.  The rectangle lies outside the medium shape.  Straight rays
        (rif_mode = MER_RIF_CONST), index-matched cube / sphere boundary. */
     float   area_to_world[12], area_radiance[3];
+    /* several emitters: n_emitters entries (at most MER_MAX_EMITTERS) of a HOST array the caller owns for the duration of the call (placed
+       before the rough_* fields, which stay the last 12 bytes of the struct, pointer first: no padding); every call that takes the scene reads it (each context of a mer_multi uploads it in its own mer_render).  n_emitters = 0: the point_* and
+       area_* fields above describe the (at most one) point and area emitter.  n_emitters > 0: those fields must be zero and the list holds
+       every point and area emitter (the constant environment stays env_radiance).  Each entry is checked as the single emitter of its kind
+       is; in addition every rectangle must lie outside the medium shape by an exact test (sphere: its closest point; cube: a rectangle /
+       box overlap test), and a list with a rectangle must not hold a point emitter outside the shape (point samples are not tested
+       against rectangles).  Rectangles are all-absorbing occluders: the nearest one ends a camera ray, look-up or escaping path; any one
+       blocks the environment's luminaire sample; an area sample on rectangle k is blocked by every other rectangle in front of it. */
+    const mer_emitter *emitters; int32_t n_emitters;
     /* boundary_bsdf = MER_BSDF_HROUGHDIELECTRIC (src/bsdfs/hroughdielectric.cpp: microfacet dielectric whose eta is the RIF at the hit point,
        exterior index 1, eta taken as for hdielectric): MER_MICROFACET_* distribution, one isotropic roughness alpha (the XML default is 0.1;
        clamped to >= 1e-4 as src/bsdfs/microfacet.h:131-136), and visible-normal sampling (Heitz & d'Eon 2014) or the full distribution with

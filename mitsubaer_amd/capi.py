@@ -37,6 +37,12 @@ class GridDesc(C.Structure):
                 ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("world_to_volume", C.c_float * 12)]
 
 
+class EmitterDesc(C.Structure):
+    """mer_emitter: one entry of SceneDesc.emitters"""
+    _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("intensity", C.c_float * 3),
+                ("to_world", C.c_float * 12), ("radiance", C.c_float * 3), ("sampling_weight", C.c_float)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32),
@@ -67,8 +73,15 @@ class SceneDesc(C.Structure):
         ("ac_n_o", C.c_float), ("ac_n_max", C.c_float), ("ac_k_r", C.c_float), ("ac_mode", C.c_int32),
         ("method", C.c_int32), ("het_stepsize", C.c_float),
         ("area_to_world", C.c_float * 12), ("area_radiance", C.c_float * 3),
+        ("emitters", C.POINTER(EmitterDesc)), ("n_emitters", C.c_int32),
         ("rough_distribution", C.c_int32), ("rough_alpha", C.c_float), ("rough_sample_visible", C.c_int32),
     ]
+
+
+def _rows3x4(to_world):
+    """a 3x4 / 4x4 transform (None = identity) as the 12 row-major float32 values of the C structs"""
+    m = np.eye(4); t = np.asarray(to_world if to_world is not None else np.eye(4), np.float64); m[:t.shape[0], :4] = t
+    return [float(v) for v in m[:3, :4].astype(np.float32).reshape(-1)]
 
 
 def _sdf_value(p, x):
@@ -120,6 +133,71 @@ def validate_rough(p):
         if inside:
             raise MerError("hroughdielectric: the point emitter must lie outside the medium shape "
                            "(a curved connection that starts on the boundary is not built)")
+
+
+def _rect_meets_shape(p, m):
+    """exact test that the rectangle O + a U + b V (a, b in [-1, 1]; columns of the 3x4 m) meets the closed cube / sphere of p"""
+    U, V, O = m[:, 0], m[:, 1], m[:, 3]
+    if p.boundary == P.BOUNDARY_SPHERE:
+        c = np.asarray(p.sph_center, np.float64)
+        a = np.clip(np.dot(c - O, U) / np.dot(U, U), -1, 1); b = np.clip(np.dot(c - O, V) / np.dot(V, V), -1, 1)
+        q = O + a * U + b * V - c
+        return float(np.dot(q, q)) < float(p.sph_radius) ** 2
+    lo, hi = np.asarray(p.bmin, np.float64), np.asarray(p.bmax, np.float64)
+    c, h = 0.5 * (lo + hi) - O, 0.5 * (hi - lo)
+    E = np.eye(3)
+    axes = [E[0], E[1], E[2], U, V, np.cross(U, V)] + [np.cross(E[i], w) for i in range(3) for w in (U, V)]
+    for L in axes:            # separating axis theorem; touching counts as meeting
+        if abs(np.dot(c, L)) > np.dot(h, np.abs(L)) + abs(np.dot(U, L)) + abs(np.dot(V, L)):
+            return False
+    return True
+
+
+def _point_in_shape(p, x):
+    x = np.asarray(x, np.float32)
+    if p.boundary == P.BOUNDARY_AABB:
+        return bool(np.all(x >= np.asarray(p.bmin, np.float32)) and np.all(x <= np.asarray(p.bmax, np.float32)))
+    if p.boundary == P.BOUNDARY_SPHERE:
+        return float(np.sum((x - np.asarray(p.sph_center, np.float32)) ** 2)) < float(p.sph_radius) ** 2
+    return _sdf_value(p, x) < 0 if p.sdf is not None else False
+
+
+def validate_emitters(p):
+    """The refusals of an emitter list (p.emitters), as mer_render applies them: MerError.  No GPU needed."""
+    ems = list(getattr(p, "emitters", None) or [])
+    if not ems:
+        return
+    if len(ems) > P.MAX_EMITTERS:
+        raise MerError("emitter list: at most %d entries (MER_MAX_EMITTERS)" % P.MAX_EMITTERS)
+    if any(v != 0 for v in p.point_intensity) or any(v != 0 for v in p.area_radiance):
+        raise MerError("emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0")
+    has_rect, outside_point = False, False
+    for j, e in enumerate(ems):
+        at = "emitter list, entry %d: " % j
+        w = float(e.get("sampling_weight", 1.0))
+        if not (np.isfinite(w) and w > 0):
+            raise MerError(at + "samplingWeight must be positive")
+        if e["type"] == P.EMITTER_POINT:
+            if not all(v >= 0 for v in e["intensity"]):
+                raise MerError(at + "emitter radiance / intensity must be non-negative")
+            inside = _point_in_shape(p, e["position"])
+            if p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC and inside:
+                raise MerError(at + "hroughdielectric: the point emitter must lie outside the medium shape")
+            outside_point = outside_point or (p.boundary != P.BOUNDARY_SDF and not inside)
+        elif e["type"] == P.EMITTER_AREA:
+            if p.rif_mode != P.RIF_CONST:
+                raise MerError(at + "the area emitter is built for straight rays (rif_mode = CONST)")
+            if p.boundary_bsdf != P.BSDF_NULL or p.boundary == P.BOUNDARY_SDF:
+                raise MerError(at + "the area emitter needs an index-matched cube / sphere boundary")
+            if not all(v >= 0 for v in e["radiance"]):
+                raise MerError(at + "emitter radiance / intensity must be non-negative")
+            if _rect_meets_shape(p, np.array(_rows3x4(e.get("to_world")), np.float64).reshape(3, 4)):
+                raise MerError(at + "the area emitter's rectangle must lie outside the medium shape")
+            has_rect = True
+        else:
+            raise MerError(at + "unknown emitter type")
+    if has_rect and outside_point:
+        raise MerError("emitter list: a point emitter outside the medium shape cannot be combined with an area emitter")
 
 
 class Shard(C.Structure):
@@ -329,9 +407,21 @@ class Context:
         s.boundary_bsdf = p.boundary_bsdf
         s.sdf = sdf.handle if sdf is not None else 0
         s.aggressive_tracing = int(p.aggressive_tracing); s.sdf_max_error = P.sdf_max_error(p)
-        m = np.eye(4); t = np.asarray(p.area_to_world if p.area_to_world is not None else np.eye(4), np.float64); m[:t.shape[0], :4] = t
-        s.area_to_world[:] = [float(v) for v in m[:3, :4].astype(np.float32).reshape(-1)]
+        s.area_to_world[:] = _rows3x4(p.area_to_world)
         s.area_radiance[:] = p.area_radiance
+        ems = list(getattr(p, "emitters", None) or [])
+        validate_emitters(p)
+        if ems:
+            arr = (EmitterDesc * len(ems))()
+            for e, d in zip(arr, ems):
+                e.type = int(d["type"]); e.sampling_weight = float(d.get("sampling_weight", 1.0))
+                if e.type == P.EMITTER_POINT:
+                    e.position[:] = [float(v) for v in d["position"]]; e.intensity[:] = [float(v) for v in d["intensity"]]
+                else:
+                    e.to_world[:] = _rows3x4(d.get("to_world")); e.radiance[:] = [float(v) for v in d["radiance"]]
+            s.n_emitters = len(ems)
+            s.emitters = C.cast(arr, C.POINTER(EmitterDesc))
+            s._emitters_keep = arr                  # the list lives as long as the scene desc that points at it
         validate_rough(p)
         rough = p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC
         s.rough_distribution = p.rough_distribution if rough else 0

@@ -123,6 +123,123 @@ static int check_rough(mer_context *ctx, const mer_scene_desc *sc) {
     if (sc->rough_sample_visible != 0 && sc->rough_sample_visible != 1) return fail(ctx, "hroughdielectric: sampleVisible must be 0 or 1");
     return 0;
 }
+// inside test of the cube / sphere medium shape (heterogeneousrefractive.cpp:707-726), as the host applies it to an emitter position
+static bool point_in_shape(const mer_scene_desc *sc, const float q[3]) {
+    if (sc->boundary == MER_BOUNDARY_AABB) { bool in = true; for (int i = 0; i < 3; i++) in = in && q[i] >= sc->bmin[i] && q[i] <= sc->bmax[i]; return in; }
+    if (sc->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (q[i] - sc->sph_center[i]) * (q[i] - sc->sph_center[i]); return d2 < sc->sph_radius * sc->sph_radius; }
+    return false;
+}
+
+// Rectangle::configure (src/shapes/rectangle.cpp:99-110): objectToWorld (row-major 3x4, also returned in M), its inverse, the frame normal
+// and 1 / area of the image of [-1,1]^2 x {0}.  Returns an error message or nullptr.
+static const char *rect_derive(const float to_world[12], DRect &R, double M[3][4]) {
+    double inv[3][3];
+    for (int i = 0; i < 12; i++) { R.o2w[i] = to_world[i]; M[i / 4][i % 4] = to_world[i]; }
+    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    if (!(std::fabs(det) > 0)) return "area emitter: 'toWorld' is singular";
+    inv[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det; inv[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det; inv[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
+    inv[1][0] = (M[1][2] * M[2][0] - M[1][0] * M[2][2]) / det; inv[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) / det; inv[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) / det;
+    inv[2][0] = (M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det; inv[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det; inv[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det;
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) R.w2o[4 * i + j] = (float) inv[i][j];
+        R.w2o[4 * i + 3] = (float) -(inv[i][0] * M[0][3] + inv[i][1] * M[1][3] + inv[i][2] * M[2][3]);
+    }
+    const double du[3] = {2 * M[0][0], 2 * M[1][0], 2 * M[2][0]}, dv[3] = {2 * M[0][1], 2 * M[1][1], 2 * M[2][1]};
+    const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+    if (std::fabs((du[0] * dv[0] + du[1] * dv[1] + du[2] * dv[2]) / (lu * lv)) > MER_EPSILON) return "Error: 'toWorld' transformation contains shear!";    // :108-109
+    const double nn[3] = {inv[2][0], inv[2][1], inv[2][2]}, ln = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // o2w(Normal(0,0,1)): inverse transpose
+    for (int i = 0; i < 3; i++) R.n[i] = (float) (nn[i] / ln);
+    R.inv_area = (float) (1.0 / (lu * lv));
+    return nullptr;
+}
+
+// Exact test that the rectangle O + a U + b V (a, b in [-1, 1]; U = column 0, V = column 1, O = column 3 of M; U orthogonal to V) meets
+// the closed medium shape.  Sphere: its point closest to the centre lies inside.  Cube: no separating axis among the box axes, the
+// rectangle's edges and normal, and the nine edge-by-edge cross products.
+static bool rect_meets_shape(const mer_scene_desc *sc, const double M[3][4]) {
+    const double U[3] = {M[0][0], M[1][0], M[2][0]}, V[3] = {M[0][1], M[1][1], M[2][1]}, O[3] = {M[0][3], M[1][3], M[2][3]};
+    auto dot3 = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
+    if (sc->boundary == MER_BOUNDARY_SPHERE) {
+        const double d[3] = {sc->sph_center[0] - O[0], sc->sph_center[1] - O[1], sc->sph_center[2] - O[2]};
+        const double a = std::min(1.0, std::max(-1.0, dot3(d, U) / dot3(U, U))), b = std::min(1.0, std::max(-1.0, dot3(d, V) / dot3(V, V)));
+        double d2 = 0;
+        for (int i = 0; i < 3; i++) { const double e = O[i] + a * U[i] + b * V[i] - sc->sph_center[i]; d2 += e * e; }
+        return d2 < (double) sc->sph_radius * sc->sph_radius;
+    }
+    double c[3], h[3];
+    for (int i = 0; i < 3; i++) { c[i] = 0.5 * ((double) sc->bmin[i] + sc->bmax[i]) - O[i]; h[i] = 0.5 * ((double) sc->bmax[i] - sc->bmin[i]); }
+    const double N[3] = {U[1] * V[2] - U[2] * V[1], U[2] * V[0] - U[0] * V[2], U[0] * V[1] - U[1] * V[0]};
+    double axes[13][3];
+    int na = 0;
+    for (int i = 0; i < 3; i++) { axes[na][0] = axes[na][1] = axes[na][2] = 0; axes[na][i] = 1; na++; }
+    for (const double *w : {U, V, N}) { for (int i = 0; i < 3; i++) axes[na][i] = w[i]; na++; }
+    for (int i = 0; i < 3; i++)
+        for (const double *w : {U, V}) {
+            const double e[3] = {i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0};
+            axes[na][0] = e[1] * w[2] - e[2] * w[1]; axes[na][1] = e[2] * w[0] - e[0] * w[2]; axes[na][2] = e[0] * w[1] - e[1] * w[0]; na++;
+        }
+    for (int k = 0; k < na; k++) {
+        const double *L = axes[k];
+        const double rBox = h[0] * std::fabs(L[0]) + h[1] * std::fabs(L[1]) + h[2] * std::fabs(L[2]);
+        const double rRect = std::fabs(dot3(U, L)) + std::fabs(dot3(V, L));
+        if (std::fabs(dot3(c, L)) > rBox + rRect) return false;           // separated (touching counts as meeting: the cube is closed)
+    }
+    return true;
+}
+
+// mer_scene_desc.emitters -> the point / area tables: each entry checked as the single emitter of its kind is, the rectangles by the exact
+// outside test, then every kind's selection pdf = sampling_weight / sum and its CDF
+static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects) {
+    if (sc->n_emitters < 0 || sc->n_emitters > MER_MAX_EMITTERS) return fail(ctx, "emitter list: at most " + std::to_string(MER_MAX_EMITTERS) + " entries (MER_MAX_EMITTERS)");
+    if (!sc->emitters) return fail(ctx, "emitter list: n_emitters > 0 but no entries");
+    if (!points.empty() || !rects.empty()) return fail(ctx, "emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0");
+    std::vector<double> wp, wr;
+    for (int j = 0; j < sc->n_emitters; ++j) {
+        const mer_emitter &e = sc->emitters[j];
+        const std::string at = "emitter list, entry " + std::to_string(j) + ": ";
+        if (!(e.sampling_weight > 0) || !std::isfinite(e.sampling_weight)) return fail(ctx, at + "samplingWeight must be positive");
+        if (e.type == MER_EMITTER_POINT) {
+            for (int i = 0; i < 3; i++) if (!(e.intensity[i] >= 0) || !std::isfinite(e.position[i])) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
+            if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point_in_shape(sc, e.position))
+                return fail(ctx, at + "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+            DPoint E{};
+            for (int i = 0; i < 3; i++) { E.pos[i] = e.position[i]; E.Ie[i] = e.intensity[i]; }
+            points.push_back(E); wp.push_back(e.sampling_weight);
+        } else if (e.type == MER_EMITTER_AREA) {
+            if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, at + "the area emitter is built for straight rays (rif_mode = CONST)");
+            if (sc->boundary_bsdf != MER_BSDF_NULL || sc->boundary == MER_BOUNDARY_SDF) return fail(ctx, at + "the area emitter needs an index-matched cube / sphere boundary");
+            for (int i = 0; i < 3; i++) if (!(e.radiance[i] >= 0)) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
+            DRect R{}; double M[3][4];
+            if (const char *err = rect_derive(e.to_world, R, M)) return fail(ctx, at + err);
+            if (rect_meets_shape(sc, M)) return fail(ctx, at + "the area emitter's rectangle must lie outside the medium shape");
+            for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = e.radiance[i];
+            rects.push_back(R); wr.push_back(e.sampling_weight);
+        } else return fail(ctx, at + "unknown emitter type");
+    }
+    if (!rects.empty())
+        for (const DPoint &E : points)
+            if (!point_in_shape(sc, E.pos))
+                return fail(ctx, "emitter list: a point emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
+    // selection pdf and CDF of every kind; the sample of emitter k is divided by its pdf on the host (intensity / pdf, radiance / pdf)
+    double sum = 0, cum = 0;
+    for (double w : wp) sum += w;
+    for (size_t k = 0; k < points.size(); ++k) {
+        cum += wp[k];
+        DPoint &E = points[k];
+        E.pdf = (float) (wp[k] / sum); E.cdf = k + 1 == points.size() ? 1.0f : (float) (cum / sum);
+        for (int i = 0; i < 3; i++) E.Ie[i] = E.Ie[i] / E.pdf;
+    }
+    sum = 0; cum = 0;
+    for (double w : wr) sum += w;
+    for (size_t k = 0; k < rects.size(); ++k) {
+        cum += wr[k];
+        DRect &R = rects[k];
+        R.pdf = (float) (wr[k] / sum); R.cdf = k + 1 == rects.size() ? 1.0f : (float) (cum / sum);
+        for (int i = 0; i < 3; i++) R.Le[i] = R.L[i] / R.pdf;
+    }
+    return 0;
+}
+
 int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf) {
     std::memset(&P, 0, sizeof(P));
     P.sc = *sc;
@@ -264,33 +381,17 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
     if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {
         if (check_rough(ctx, sc)) return 1;
         const bool point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
-        bool inside = false;
-        if (sc->boundary == MER_BOUNDARY_AABB) { inside = true; for (int i = 0; i < 3; i++) inside = inside && sc->point_position[i] >= sc->bmin[i] && sc->point_position[i] <= sc->bmax[i]; }
-        else if (sc->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (sc->point_position[i] - sc->sph_center[i]) * (sc->point_position[i] - sc->sph_center[i]); inside = d2 < sc->sph_radius * sc->sph_radius; }
         // (a signed-distance shape: tested below, where its grid is known)
-        if (point && inside) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+        if (point && point_in_shape(sc, sc->point_position)) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
-    P.has_area = (sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0) ? 1 : 0;
-    if (P.has_area) {               // Rectangle::configure (src/shapes/rectangle.cpp:99-110)
+    std::vector<DPoint> points; std::vector<DRect> rects;
+    const bool legacy_area = sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0;
+    const bool legacy_point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
+    if (legacy_area) {
         if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, "the area emitter is built for straight rays (rif_mode = CONST)");
         if (sc->boundary_bsdf != MER_BSDF_NULL || sc->boundary == MER_BOUNDARY_SDF) return fail(ctx, "the area emitter needs an index-matched cube / sphere boundary");
-        double M[3][4], inv[3][3];
-        for (int i = 0; i < 12; i++) { P.rect_o2w[i] = sc->area_to_world[i]; M[i / 4][i % 4] = sc->area_to_world[i]; }
-        const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-        if (!(std::fabs(det) > 0)) return fail(ctx, "area emitter: 'toWorld' is singular");
-        inv[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det; inv[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det; inv[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
-        inv[1][0] = (M[1][2] * M[2][0] - M[1][0] * M[2][2]) / det; inv[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) / det; inv[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) / det;
-        inv[2][0] = (M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det; inv[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det; inv[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det;
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) P.rect_w2o[4 * i + j] = (float) inv[i][j];
-            P.rect_w2o[4 * i + 3] = (float) -(inv[i][0] * M[0][3] + inv[i][1] * M[1][3] + inv[i][2] * M[2][3]);
-        }
-        const double du[3] = {2 * M[0][0], 2 * M[1][0], 2 * M[2][0]}, dv[3] = {2 * M[0][1], 2 * M[1][1], 2 * M[2][1]};
-        const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
-        if (std::fabs((du[0] * dv[0] + du[1] * dv[1] + du[2] * dv[2]) / (lu * lv)) > MER_EPSILON) return fail(ctx, "Error: 'toWorld' transformation contains shear!");    // :108-109
-        const double nn[3] = {inv[2][0], inv[2][1], inv[2][2]}, ln = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // o2w(Normal(0,0,1)): inverse transpose
-        for (int i = 0; i < 3; i++) P.rect_n[i] = (float) (nn[i] / ln);
-        P.rect_inv_area = (float) (1.0 / (lu * lv));
+        DRect R{}; double M[3][4];
+        if (const char *e = rect_derive(sc->area_to_world, R, M)) return fail(ctx, e);
         // the rectangle must lie outside the (convex) medium shape: corners and centre are tested
         for (int k = 0; k < 5; k++) {
             const float lx = k == 4 ? 0.0f : (k & 1 ? 1.0f : -1.0f), ly = k == 4 ? 0.0f : (k & 2 ? 1.0f : -1.0f);
@@ -300,7 +401,17 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
             else for (int i = 0; i < 3; i++) in = in && q[i] >= sc->bmin[i] && q[i] <= sc->bmax[i];
             if (in) return fail(ctx, "the area emitter's rectangle must lie outside the medium shape");
         }
+        for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = sc->area_radiance[i];
+        R.pdf = R.cdf = 1.0f;
+        rects.push_back(R);
     }
+    if (legacy_point) {
+        DPoint E{};
+        for (int i = 0; i < 3; i++) { E.pos[i] = sc->point_position[i]; E.Ie[i] = sc->point_intensity[i]; }
+        E.pdf = E.cdf = 1.0f;
+        points.push_back(E);
+    }
+    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects)) return 1;
     if (film_frames(ctx, sc, P.frames)) return 1;
     P.film_ch = P.frames * 3 + 2;
     P.mod_phase = (float) (sc->mod_phase_deg * M_PI / 180);                                                   // pathlengthsampler.cpp:15
@@ -317,9 +428,8 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         fill_dgrid(ctx, it->second, P.sdf);
         float d2 = 0; for (int i = 0; i < 3; i++) d2 += (P.sdf.bmax[i] - P.sdf.bmin[i]) * (P.sdf.bmax[i] - P.sdf.bmin[i]);
         P.sdf_eps = 1e-4f * std::sqrt(d2);
-        const bool point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
-        if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point) {      // the emitter inside the signed-distance shape: the grid's value there (sdf_value)
-            const DGrid &g = P.sdf; const float *q = sc->point_position;
+        for (const DPoint &E : points) if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {      // an emitter inside the signed-distance shape: the grid's value there (sdf_value)
+            const DGrid &g = P.sdf; const float *q = E.pos;
             float c[3];
             for (int i = 0; i < 3; i++) c[i] = g.m[4 * i] * q[0] + g.m[4 * i + 1] * q[1] + g.m[4 * i + 2] * q[2] + g.m[4 * i + 3];
             const int x1 = (int) std::floor(c[0]), y1 = (int) std::floor(c[1]), z1 = (int) std::floor(c[2]);
@@ -341,10 +451,22 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         if (sc->rif_mode == MER_RIF_CONST) return fail(ctx, "aggressivetracing is a property of curved-ray tracing (heterogeneousrefractive)");
         if (!(sc->sdf_max_error >= 0)) return fail(ctx, "aggressivetracing: sdf_max_error must be non-negative");
     }
-    {
-        const bool has_point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
-        for (int i = 0; i < 3; i++) if (sc->point_intensity[i] < 0 || sc->env_radiance[i] < 0) return fail(ctx, "emitter radiance / intensity must be non-negative");
-        (void) has_point;      // curved rays reach a point emitter outside the shape through the boundary (Connector::path_lengths, cross = true)
+    for (int i = 0; i < 3; i++) if (sc->point_intensity[i] < 0 || sc->env_radiance[i] < 0) return fail(ctx, "emitter radiance / intensity must be non-negative");
+    // curved rays reach a point emitter outside the shape through the boundary (Connector::path_lengths, cross = true)
+    ctx->point_outside = false;
+    for (const DPoint &E : points) if (sc->boundary != MER_BOUNDARY_SDF && !point_in_shape(sc, E.pos)) ctx->point_outside = true;
+    {   // the tables go to device memory when they change; no kernel of this context is in flight here (renders and leaf calls return synchronised)
+        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, bytes = off + sizeof(DRect) * MER_MAX_EMITTERS;
+        std::vector<unsigned char> h(bytes, 0);
+        if (!points.empty()) std::memcpy(h.data(), points.data(), sizeof(DPoint) * points.size());
+        if (!rects.empty()) std::memcpy(h.data() + off, rects.data(), sizeof(DRect) * rects.size());
+        if (!ctx->etab) HIP_CHECK(ctx, hipMalloc(&ctx->etab, bytes));
+        if (ctx->etab_host != h) {
+            HIP_CHECK(ctx, hipMemcpy(ctx->etab, h.data(), bytes, hipMemcpyHostToDevice));
+            ctx->etab_host.swap(h);
+        }
+        P.n_point = (int32_t) points.size(); P.n_rect = (int32_t) rects.size();
+        P.points = (const DPoint *) ctx->etab; P.rects = (const DRect *) ((const unsigned char *) ctx->etab + off);
     }
     P.counters = ctx->counters;
     P.work_counter = ctx->counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
@@ -523,6 +645,7 @@ void mer_context_destroy(mer_context *ctx) {
     }
     if (ctx->counters) (void) hipFree(ctx->counters);
     if (ctx->ftable) (void) hipFree(ctx->ftable);
+    if (ctx->etab) (void) hipFree(ctx->etab);
     if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {
         if (pp.slots) (void) hipFree(pp.slots);

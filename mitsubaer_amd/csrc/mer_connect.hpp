@@ -145,6 +145,7 @@ struct ConnState {
     m33 J;                            // Jacobian of the residual at x
     float cost, lambda, radius, weight, RIFp, optDist, dist;
     int it, tries, iterations, phase, ok;
+    int em = 0;                       // index of the point emitter K_event selected (bits 19-31 of the last word)
     __device__ __forceinline__ void load(const uint32_t *r) {
         const uint4 *q = (const uint4 *) r; const uint4 a = q[0], b = q[1], c = q[2], d = q[3], g = q[4], h = q[5], k = q[6], l = q[7];
 #define F(u) __uint_as_float(u)
@@ -154,7 +155,7 @@ struct ConnState {
         J.m[2][0] = F(h.y); J.m[2][1] = F(h.z); J.m[2][2] = F(h.w);
         cost = F(k.x); lambda = F(k.y); radius = F(k.z); weight = F(k.w); RIFp = F(l.x); optDist = F(l.y); dist = F(l.z);
 #undef F
-        it = (int) (l.w & 31u); tries = (int) ((l.w >> 5) & 7u); iterations = (int) ((l.w >> 8) & 127u); phase = (int) ((l.w >> 15) & 7u); ok = (int) ((l.w >> 18) & 1u);
+        it = (int) (l.w & 31u); tries = (int) ((l.w >> 5) & 7u); iterations = (int) ((l.w >> 8) & 127u); phase = (int) ((l.w >> 15) & 7u); ok = (int) ((l.w >> 18) & 1u); em = (int) (l.w >> 19);
     }
     __device__ __forceinline__ void store(uint32_t *r) const {
         uint4 *q = (uint4 *) r;
@@ -163,7 +164,7 @@ struct ConnState {
         q[2] = make_uint4(U(xn.z), U(tempSol.x), U(tempSol.y), U(tempSol.z)); q[3] = make_uint4(U(dir.x), U(dir.y), U(dir.z), U(J.m[0][0]));
         q[4] = make_uint4(U(J.m[0][1]), U(J.m[0][2]), U(J.m[1][0]), U(J.m[1][1])); q[5] = make_uint4(U(J.m[1][2]), U(J.m[2][0]), U(J.m[2][1]), U(J.m[2][2]));
         q[6] = make_uint4(U(cost), U(lambda), U(radius), U(weight));
-        q[7] = make_uint4(U(RIFp), U(optDist), U(dist), (uint32_t) it | ((uint32_t) tries << 5) | ((uint32_t) iterations << 8) | ((uint32_t) phase << 15) | ((uint32_t) (ok != 0) << 18));
+        q[7] = make_uint4(U(RIFp), U(optDist), U(dist), (uint32_t) it | ((uint32_t) tries << 5) | ((uint32_t) iterations << 8) | ((uint32_t) phase << 15) | ((uint32_t) (ok != 0) << 18) | ((uint32_t) em << 19));
 #undef U
     }
 };
@@ -542,8 +543,9 @@ template <bool CURVED, int RIF, int STEPPER, int SIGMA, int BND = 0>
 __device__ __forceinline__ f3 point_nee(const Params &P, Rng &rng, LaneCounters &C, f3 ps, f3 wi, int depth, float &optLen) {   // inlined: an out-of-line callee taking Params by reference forces a scratch copy of the kernel arguments
     optLen = 0.0f;
     const mer_scene_desc &S = P.sc;
-    const f3 I(S.point_intensity[0], S.point_intensity[1], S.point_intensity[2]);
-    const f3 pp(S.point_position[0], S.point_position[1], S.point_position[2]);
+    float pk; const DPoint &E = P.points[emitter_select(P.points, P.n_point, rng, 3, pk)];     // one of the point emitters; E.Ie = I / its pdf
+    const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);
+    const f3 pp(E.pos[0], E.pos[1], E.pos[2]);
     const int interactions = S.max_depth - depth - 1;
     C.nee++;
     static_assert(!CURVED, "curved-ray connections run in K_connect");
@@ -570,10 +572,10 @@ __device__ __forceinline__ f3 point_nee(const Params &P, Rng &rng, LaneCounters 
 // path throughput): I / |pp - ps|^2 (the straight-line distance of PointEmitter::sampleDirect, which the reference keeps for curved
 // connections) x transmittance along the connecting ray (arc length dist, launched along dir) x solver weight x phase function.
 template <int RIF, int STEPPER, int SIGMA, int BND = 0>
-__device__ __forceinline__ f3 connection_value(const Params &P, Rng &rng, LaneCounters &C, f3 ps, f3 wi, f3 dir, float dist, float w) {
+__device__ __forceinline__ f3 connection_value(const Params &P, const DPoint &E, Rng &rng, LaneCounters &C, f3 ps, f3 wi, f3 dir, float dist, float w) {
     const mer_scene_desc &S = P.sc;
-    const f3 I(S.point_intensity[0], S.point_intensity[1], S.point_intensity[2]);
-    const f3 pp(S.point_position[0], S.point_position[1], S.point_position[2]);
+    const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);                 // intensity / selection pdf of the emitter the connection was built to
+    const f3 pp(E.pos[0], E.pos[1], E.pos[2]);
     const int nwalks = (SIGMA == MER_SIGMA_GRID && S.tr_estimator == MER_TR_WOODCOCK2) ? 2 : 1;
     f3 tr;
     if (SIGMA == MER_SIGMA_HOMOGENEOUS) tr = f3(expf(P.sigT.x * (-dist)), expf(P.sigT.y * (-dist)), expf(P.sigT.z * (-dist)));

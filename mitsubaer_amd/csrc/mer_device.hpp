@@ -695,6 +695,13 @@ __device__ __forceinline__ float maxexp_cdf(const MaxExp &m, float t) {         
     return m.cdf[index] + (upper - lower) * m.invNormalization;
 }
 
+// One point emitter of a context's device table (make_params): position, intensity / pdf, the probability pdf with which it is selected
+// among the point emitters (sampling_weight / sum), and the upper end of its interval of the selection CDF.
+struct DPoint { float pos[3], Ie[3], pdf, cdf; };
+// One area emitter (`rectangle`): objectToWorld, its inverse, the frame normal, 1 / area, radiance, selection pdf, radiance / pdf, CDF bound.
+struct DRect { float o2w[12], w2o[12], n[3], inv_area, L[3], pdf, Le[3], cdf; };
+static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144, "emitter records: 16-byte multiples");
+
 // Everything a render / leaf kernel needs, passed by value as the kernel argument.
 struct Params {
     mer_scene_desc sc;
@@ -742,8 +749,9 @@ struct Params {
     uint32_t *msorted, *msort_hist, *msort_cursor, *msort_count;
     unsigned long long *chk;            // MER_BOUNDS_CHECK: violation record (NULL in the product build)
     uint64_t n_film, n_path_out;        // float counts of film / path_out: the extents the checks use
-    // emitter `area` on a `rectangle` (EXTRA kernels, straight rays): objectToWorld, its inverse, the frame normal, 1 / area (make_params)
-    int32_t has_area; float rect_o2w[12], rect_w2o[12], rect_n[3], rect_inv_area;
+    // the point and area emitters (EXTRA kernels): device tables built by make_params from the legacy point_* / area_* fields or from the
+    // scene's emitter list -- the records live in device memory, not in these kernel arguments
+    int32_t n_point, n_rect; const DPoint *points; const DRect *rects;
 };
 #define MER_LIVE_SLOTS 4096
 #define MER_COUNTER_REPLICAS 64        // counters are flushed into one of this many copies (summed on the host)
@@ -957,8 +965,8 @@ __device__ __forceinline__ bool dielectric_event(const Params &P, Rng &rng, f3 r
 
 // ---- emitter `area` on a `rectangle` shape (src/emitters/area.cpp:67-187, src/shapes/rectangle.cpp:99-222, src/librender/shape.cpp:102-126)
 // Rectangle::rayIntersect (:125-148): t in [mint, maxt] or -1
-__device__ __forceinline__ float rect_intersect(const Params &P, f3 o, f3 d, float mint, float maxt) {
-    const float *W = P.rect_w2o;
+__device__ __forceinline__ float rect_intersect(const DRect &R, f3 o, f3 d, float mint, float maxt) {
+    const float *W = R.w2o;
     const float oz = W[8] * o.x + W[9] * o.y + W[10] * o.z + W[11], dz = W[8] * d.x + W[9] * d.y + W[10] * d.z;
     const float hit = -oz / dz;
     if (!(hit >= mint && hit <= maxt)) return -1.0f;
@@ -966,41 +974,74 @@ __device__ __forceinline__ float rect_intersect(const Params &P, f3 o, f3 d, flo
                 ly = (W[4] * o.x + W[5] * o.y + W[6] * o.z + W[7]) + hit * (W[4] * d.x + W[5] * d.y + W[6] * d.z);
     return (fabsf(lx) <= 1 && fabsf(ly) <= 1) ? hit : -1.0f;
 }
+// the nearest of the scene's rectangles along o + t d, t in [mint, maxt]: t or -1, and its index in k (ties: the first listed).  The loop
+// index is wave-uniform, so all lanes of a wave read the same record address; the compiler emits vector loads with a uniform address (not
+// s_load: the kernels also write global memory, so the table is not provably invariant) -- one cache line per wave and record.
+__device__ __forceinline__ float rect_nearest(const Params &P, f3 o, f3 d, float mint, float maxt, int &k) {
+    float best = -1.0f; k = 0;
+    for (int j = 0; j < P.n_rect; ++j) {
+        const float t = rect_intersect(P.rects[j], o, d, mint, best >= 0 ? best : maxt);
+        if (t >= 0 && (best < 0 || t < best)) { best = t; k = j; }
+    }
+    return best;
+}
+// does any rectangle other than `skip` cross o + t d, t in [mint, maxt]?  (skip = -1: any rectangle)
+__device__ __forceinline__ bool rect_blocks(const Params &P, f3 o, f3 d, float mint, float maxt, int skip) {
+    bool hit = false;
+    for (int j = 0; j < P.n_rect; ++j)
+        if (j != skip && rect_intersect(P.rects[j], o, d, mint, maxt) >= 0) hit = true;
+    return hit;
+}
+// Scene::sampleAttenuatedEmitterDirect's choice of ONE emitter (scene.cpp:854-874, m_emitterPDF): index k with probability pdf = tab[k].pdf,
+// from the first number of the forked stream `kind` (3: point emitters, 4: area emitters) -- the path's own stream does not advance.  One
+// emitter: no draw, k = 0, pdf = 1.
+template <class R>
+__device__ __forceinline__ int emitter_select(const R *tab, int n, const Rng &rng, uint64_t kind, float &pdf) {
+    if (n <= 1) { pdf = 1.0f; return 0; }
+    Rng s = rng.fork(kind);
+    const float u = s.next1D();
+    int k = 0;
+    for (int j = 0; j < n - 1; ++j) k += u >= tab[j].cdf ? 1 : 0;
+    pdf = tab[k].pdf;
+    return k;
+}
 // AreaLight::eval (area.cpp:102-107): the radiance a ray travelling along d picks up on the rectangle (one-sided)
-__device__ __forceinline__ f3 rect_le(const Params &P, f3 d) {
-    const f3 n(P.rect_n[0], P.rect_n[1], P.rect_n[2]);
-    return dot(n, -d) <= 0 ? f3(0, 0, 0) : f3(P.sc.area_radiance[0], P.sc.area_radiance[1], P.sc.area_radiance[2]);
+__device__ __forceinline__ f3 rect_le(const DRect &R, f3 d) {
+    const f3 n(R.n[0], R.n[1], R.n[2]);
+    return dot(n, -d) <= 0 ? f3(0, 0, 0) : f3(R.L[0], R.L[1], R.L[2]);
 }
 // Shape::sampleDirect + AreaLight::sampleDirect (shape.cpp:102-115, area.cpp:162-177) for a reference point inside a medium (refN = 0):
-// radiance / pdf (0 on the back side), direction, distance, solid-angle pdf
-__device__ __forceinline__ f3 rect_sample_direct(const Params &P, f3 ref, float sx, float sy, f3 &d, float &dist, float &pdf) {
-    const float *M = P.rect_o2w; const float lx = sx * 2 - 1, ly = sy * 2 - 1;
+// radiance / pdf (0 on the back side), direction, distance, solid-angle pdf -- of the rectangle selected with probability R.pdf: the
+// radiance is R.Le = L / R.pdf and the pdf includes R.pdf (AreaLight's dRec.pdf *= emPdf; value /= emPdf)
+__device__ __forceinline__ f3 rect_sample_direct(const DRect &R, f3 ref, float sx, float sy, f3 &d, float &dist, float &pdf) {
+    const float *M = R.o2w; const float lx = sx * 2 - 1, ly = sy * 2 - 1;
     const f3 p(M[0] * lx + M[1] * ly + M[3], M[4] * lx + M[5] * ly + M[7], M[8] * lx + M[9] * ly + M[11]);
-    const f3 n(P.rect_n[0], P.rect_n[1], P.rect_n[2]);
+    const f3 n(R.n[0], R.n[1], R.n[2]);
     d = p - ref;
     const float distSquared = dot(d, d);
     dist = sqrtf(distSquared);
     d = d / dist;
     const float dp = fabsf(dot(d, n));
-    pdf = P.rect_inv_area * (dp != 0 ? (distSquared / dp) : 0.0f);
-    if (dot(d, n) < 0 && pdf != 0) return f3(P.sc.area_radiance[0], P.sc.area_radiance[1], P.sc.area_radiance[2]) / pdf;
+    pdf = R.inv_area * (dp != 0 ? (distSquared / dp) : 0.0f);
+    if (dot(d, n) < 0 && pdf != 0) { const f3 v = f3(R.Le[0], R.Le[1], R.Le[2]) / pdf; pdf = pdf * R.pdf; return v; }
     pdf = 0.0f;
     return f3(0, 0, 0);
 }
 // AreaLight::pdfDirect (area.cpp:179-187) for a hit at distance dist along d
-__device__ __forceinline__ float rect_pdf_direct(const Params &P, f3 d, float dist) {
-    const f3 n(P.rect_n[0], P.rect_n[1], P.rect_n[2]);
-    return dot(d, n) < 0 ? P.rect_inv_area * (dist * dist) / fabsf(dot(d, n)) : 0.0f;
+__device__ __forceinline__ float rect_pdf_direct(const DRect &R, f3 d, float dist) {
+    const f3 n(R.n[0], R.n[1], R.n[2]);
+    return dot(d, n) < 0 ? R.inv_area * (dist * dist) / fabsf(dot(d, n)) : 0.0f;
 }
-// what a ray sees that has left the convex medium shape for good (or never meets it): the rectangle if it is hit -- front side: its radiance, back
-// side: black, and either way it hides the environment (all-absorbing BSDF, shape.cpp:48-56) -- else the environment.  extra = the optical length of
-// the free-space leg to the rectangle (transient films).  AREA is a compile-time switch: the plain kernels carry none of this.
+// what a ray sees that has left the convex medium shape for good (or never meets it): the nearest rectangle if one is hit -- front side: its
+// radiance, back side: black, and either way it hides the environment (all-absorbing BSDF, shape.cpp:48-56) -- else the environment.
+// extra = the optical length of the free-space leg to the rectangle (transient films).  AREA is a compile-time switch: the plain kernels
+// carry none of this.
 template <bool AREA>
 __device__ __forceinline__ f3 escape_radiance(const Params &P, f3 env, f3 o, f3 d, float mint, float &extra) {
     extra = 0.0f;
-    if (AREA && P.has_area) {
-        const float t = rect_intersect(P, o, d, mint, MER_INF);
-        if (t >= 0) { extra = t * P.sc.rif_const; return rect_le(P, d); }
+    if (AREA && P.n_rect) {
+        int k; const float t = rect_nearest(P, o, d, mint, MER_INF, k);
+        if (t >= 0) { extra = t * P.sc.rif_const; return rect_le(P.rects[k], d); }
     }
     return env;
 }

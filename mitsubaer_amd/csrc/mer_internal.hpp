@@ -72,6 +72,9 @@ struct mer_context {
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
+    // point / area emitter tables on the device (MER_MAX_EMITTERS DPoint records, then as many DRect records), the bytes they hold, and
+    // whether a point emitter of the last make_params lies outside the (cube / sphere) medium shape
+    void *etab = nullptr; std::vector<unsigned char> etab_host; bool point_outside = false;
     unsigned long long *chk = nullptr;           // MER_BOUNDS_CHECK build: violation record (count, kind, index, limit)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;

@@ -221,8 +221,9 @@ __device__ __forceinline__ int rough_event(const Params &P, Rng &rng, f3 ro, f3 
     const Microfacet d = microfacet_make(S.rough_distribution, S.rough_alpha, S.rough_sample_visible);
     (void) rng.next1D(); (void) rng.next1D();                     // (1)
     Le = f3(0, 0, 0); eLen = 0.0f;
-    if (S.point_intensity[0] != 0 || S.point_intensity[1] != 0 || S.point_intensity[2] != 0) {
-        f3 dv(S.point_position[0] - x.x, S.point_position[1] - x.y, S.point_position[2] - x.z);
+    if (P.n_point) {
+        float pk; const DPoint &E = P.points[emitter_select(P.points, P.n_point, rng, 3, pk)];    // one of the point emitters; E.Ie = I / its pdf
+        f3 dv(E.pos[0] - x.x, E.pos[1] - x.y, E.pos[2] - x.z);
         const float dist = sqrtf(dot(dv, dv));
         dv = dv / dist;
         const f3 wl(dot(dv, s), dot(dv, u), dot(dv, n));
@@ -233,7 +234,7 @@ __device__ __forceinline__ int rough_event(const Params &P, Rng &rng, f3 ro, f3 
         if (visible) {
             float pdfE;
             const float f = rough_dielectric_eval(d, etaB, wi, wl, pdfE);
-            const f3 I(S.point_intensity[0], S.point_intensity[1], S.point_intensity[2]);
+            const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);
             Le = T * I * (f / (dist * dist));
             eLen = dist;
         }

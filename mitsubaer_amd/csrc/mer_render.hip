@@ -132,11 +132,11 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (P.total_work == 0) return 0;
 
-    const bool has_point = scene->point_intensity[0] != 0 || scene->point_intensity[1] != 0 || scene->point_intensity[2] != 0;
+    const bool has_point = P.n_point > 0;            // the legacy point / area fields or the emitter list (make_params)
     const bool curved = scene->rif_mode != MER_RIF_CONST;
     // EXTRA kernels carry the point emitter, the modulated film and the dielectric boundary; the signed-distance boundary exists in
     // the EXTRA kernels only
-    const bool has_area = scene->area_radiance[0] != 0 || scene->area_radiance[1] != 0 || scene->area_radiance[2] != 0;
+    const bool has_area = P.n_rect > 0;
     const bool extra = scene->boundary == MER_BOUNDARY_SDF || has_point || has_area || scene->modulation != MER_MODULATION_NONE || scene->boundary_bsdf != MER_BSDF_NULL;
     KernelSet ks{};
     if (!pick_kernels(ctx, scene, extra, ks)) {
@@ -153,12 +153,9 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     if (inline_walks) ks.event = ks.event_inline;
     if (scene->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) ks.event = inline_walks ? ks.event_inline_rough : ks.event_rough;   // its own instances (mer_wavefront.hpp)
     const bool connect_stage = has_point && curved && scene->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC;   // a rough boundary: the surface vertex samples the emitter
-    if (connect_stage) {            // an emitter outside the shape is reached through the boundary: the kernel that carries the refraction code
-        bool inside = false;        // (signed-distance shapes: the plain kernel carries it too, the side is tested per connection)
-        if (scene->boundary == MER_BOUNDARY_AABB) { inside = true; for (int i = 0; i < 3; i++) inside = inside && scene->point_position[i] >= scene->bmin[i] && scene->point_position[i] <= scene->bmax[i]; }
-        else if (scene->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (scene->point_position[i] - scene->sph_center[i]) * (scene->point_position[i] - scene->sph_center[i]); inside = d2 < scene->sph_radius * scene->sph_radius; }
-        if (!inside) ks.connect = ks.connect_cross;
-    }
+    // any point emitter outside the shape is reached through the boundary: the kernel that carries the refraction code (it connects to emitters
+    // inside the shape as well; signed-distance shapes: the plain kernel carries it too, the side is tested per connection)
+    if (connect_stage && ctx->point_outside) ks.connect = ks.connect_cross;
 
     // spawned side walks (mer_wavefront.hpp): the plain curved kernels hand luminaire-sample / look-up walks to side-walk slots -- four per path, behind
     // the path slots -- when the render is a steady-state film with an environment to reach (per-path output keeps every walk in the path's own lane:

@@ -208,8 +208,8 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                 float plen = 0.0f;                                   // transient film: optical path length so far
                 const float itsT = intersect_shape_b<BND>(P, o, d, mint, maxt);
                 // the area emitter's rectangle in front of the medium shape (or hit instead of it): its.isEmitter() => Le, then the all-absorbing BSDF ends the path
-                const float tRect = (EXTRA && P.has_area) ? rect_intersect(P, o, d, mint, maxt) : -1.0f;
-                if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P, d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
+                int kRect = 0; const float tRect = (EXTRA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
+                if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P.rects[kRect], d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
                 else if (itsT < 0) { if (!S.hide_emitters) L = env; }
                 else if (1 >= maxDepth && maxDepth != -1) { }
                 else if (EXTRA && S.boundary_bsdf != MER_BSDF_NULL) hit = true;      // Fresnel / microfacet sampling at the surface: K_event
@@ -295,7 +295,8 @@ __device__ __forceinline__ int connect_class(const Params &P, int group, float p
 }
 // group and predicted length of the unit a parked solver state will run next
 __device__ __forceinline__ int connect_class_of(const Params &P, const ConnState &S, f3 ps) {
-    const f3 d(P.sc.point_position[0] - ps.x, P.sc.point_position[1] - ps.y, P.sc.point_position[2] - ps.z);
+    const DPoint &E = P.points[S.em];
+    const f3 d(E.pos[0] - ps.x, E.pos[1] - ps.y, E.pos[2] - ps.z);
     if (S.phase == CP_OK) return connect_class(P, 2, S.dist);
     const f3 dir = S.phase == CP_TRIAL ? S.xn : (S.phase == CP_PATHLEN ? S.dir : S.x);
     return connect_class(P, S.phase == CP_PATHLEN ? 1 : 0, dot(d, dir) * __builtin_amdgcn_rsqf(dot(dir, dir)));
@@ -594,7 +595,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
     // a dielectric boundary blocks emitter sampling and look-ups from inside: the environment is reached by refracting out
     const bool hasEnv = !is_zero(env) && !dielectric;
     const bool hasEmission = S.emission[0] != 0 || S.emission[1] != 0 || S.emission[2] != 0;
-    const bool hasPoint = EXTRA && (S.point_intensity[0] != 0 || S.point_intensity[1] != 0 || S.point_intensity[2] != 0);
+    const bool hasPoint = EXTRA && P.n_point > 0;
     const int maxDepth = S.max_depth;
     const int nwalks = (SIGMA == MER_SIGMA_GRID && S.tr_estimator == MER_TR_WOODCOCK2) ? 2 : 1;
     enum { F_SCATTERED = 1, F_EMITTED = 2, F_ITSVALID = 4, F_FORKED = 8 };      // F_FORKED: the lane's sampler is a side walk's child stream; the path's own state waits in prng
@@ -682,9 +683,9 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             C.paths++;
             ev = EV_NONE;
             itsT = intersect_shape_b<BND>(P, o, d, mint, maxt);                       // rRec.rayIntersect(ray)
-            const float tRect = (EXTRA && P.has_area) ? rect_intersect(P, o, d, mint, maxt) : -1.0f;
-            if (tRect >= 0 && (itsT < 0 || tRect < itsT)) {                              // the area emitter's rectangle is met first (K_gen retires these; gen_all hands them over)
-                if (!S.hide_emitters) { if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); const f3 Le = rect_le(P, d); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }
+            int kRect = 0; const float tRect = (EXTRA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
+            if (tRect >= 0 && (itsT < 0 || tRect < itsT)) {                              // an area emitter's rectangle is met first (K_gen retires these; gen_all hands them over)
+                if (!S.hide_emitters) { if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); const f3 Le = rect_le(P.rects[kRect], d); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }
                 ev = EV_PATH_DONE;
             } else
             if (itsT < 0) {
@@ -834,8 +835,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             if (W.kind == K_NEE) {
                 const float dpdf = MER_INV_FOURPI;
                 f3 value = env / dpdf;
-                // the rectangle shadows the environment (Scene::evalTransmittance stops at a non-null surface); tested after the walk so that the sampler draws stay the oracle's
-                if (EXTRA && P.has_area && rect_intersect(P, ps, dd, 0.0f, MER_INF) >= 0) tr = f3(0, 0, 0);
+                // any rectangle shadows the environment (Scene::evalTransmittance stops at a non-null surface); tested after the walk so that the sampler draws stay the oracle's
+                if (EXTRA && P.n_rect && rect_blocks(P, ps, dd, 0.0f, MER_INF, -1)) tr = f3(0, 0, 0);
                 value = value * tr;
                 if (!is_zero(value)) {
                     const float phaseVal = phase_eval(S.phase, S.g, wi, dd);
@@ -854,10 +855,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 if (!blocked && !is_zero(tr)) {
                     f3 value = tr * env;
                     float emitterPdf = MER_INV_FOURPI, extra = 0.0f;
-                    if (EXTRA && P.has_area) {
-                        // rayIntersectAndLookForEmitter (volpath.cpp:370-428): beyond the null boundary the ray meets the rectangle or the environment
-                        const float tR = rect_intersect(P, ps, dsave, 0.0f, MER_INF);
-                        if (tR >= 0) { value = tr * rect_le(P, dsave); emitterPdf = rect_pdf_direct(P, dsave, tR); extra = (tR - (itsValid ? itsT : 0.0f)) * S.rif_const; }
+                    if (EXTRA && P.n_rect) {
+                        // rayIntersectAndLookForEmitter (volpath.cpp:370-428): beyond the null boundary the ray meets the nearest rectangle or the environment;
+                        // the MIS partner's pdf is that of sampling this rectangle: its selection probability x its solid-angle pdf
+                        int k; const float tR = rect_nearest(P, ps, dsave, 0.0f, MER_INF, k);
+                        if (tR >= 0) { const DRect &R = P.rects[k]; value = tr * rect_le(R, dsave); emitterPdf = R.pdf * rect_pdf_direct(R, dsave, tR); extra = (tR - (itsValid ? itsT : 0.0f)) * S.rif_const; }
                         else if (!hasEnv) value = f3(0, 0, 0);
                     }
                     if (!is_zero(value)) {
@@ -880,14 +882,16 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 (void) rng.next1D(); (void) rng.next1D();
             } else
             if (EXTRA && hasPoint && ev == EV_PHASE) {
-                if (CURVED) {                        // park the slot: K_connect takes the connection from here (state CP_NEW)
+                if (CURVED) {                        // park the slot: K_connect takes the connection from here (state CP_NEW) toward the selected emitter
                     connecting = true;
+                    float pk; const int k = emitter_select(P.points, P.n_point, rng, 3, pk);
                     {   // its first unit shoots along a direction whose cosine to the chord is the NEXT sampler number (Connector::uniform_sample): peek
                         Rng peek = rng; const float cosChord = peek.next1D();
-                        const f3 dch(S.point_position[0] - ps.x, S.point_position[1] - ps.y, S.point_position[2] - ps.z);
+                        const DPoint &E = P.points[k];
+                        const f3 dch(E.pos[0] - ps.x, E.pos[1] - ps.y, E.pos[2] - ps.z);
                         cq_class = connect_class(P, 0, cosChord * sqrtf(dot(dch, dch)));
                     }
-                    P.cstate[(size_t) MER_CHK(P.chk, CHK_SLOT, i, P.nslots) * MER_CSTATE_WORDS + MER_CSTATE_WORDS - 1] = (uint32_t) CP_NEW << 15;
+                    P.cstate[(size_t) MER_CHK(P.chk, CHK_SLOT, i, P.nslots) * MER_CSTATE_WORDS + MER_CSTATE_WORDS - 1] = ((uint32_t) CP_NEW << 15) | ((uint32_t) k << 19);
                     break;
                 }
                 float optLen = 0.0f;
@@ -895,19 +899,22 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 L = L + mod_weight<EXTRA>(P, c, plen + edge_length(P, optLen));
                 film_contribute(P, px, py, c, plen + edge_length(P, optLen));
             }
-            // ---- luminaire sampling of the area emitter (scene.cpp:854-874, area.cpp:162-177, shape.cpp:102-115); its MIS partner is the look-up below
-            if (EXTRA && !CURVED && P.has_area && ev == EV_PHASE) {
+            // ---- luminaire sampling of ONE area emitter (scene.cpp:854-874, area.cpp:162-177, shape.cpp:102-115); its MIS partner is the look-up below
+            if (EXTRA && !CURVED && P.n_rect && ev == EV_PHASE) {
                 C.nee++;
                 const int interactions = maxDepth - depth - 1;
+                float pk; const int k = emitter_select(P.rects, P.n_rect, rng, 4, pk);
                 const float sx = rng.next1D(), sy = rng.next1D();
                 f3 dvec; float dist, dpdf;
-                f3 value = rect_sample_direct(P, ps, sx, sy, dvec, dist, dpdf);
+                f3 value = rect_sample_direct(P.rects[k], ps, sx, sy, dvec, dist, dpdf);
                 if (!is_zero(value)) {
                     const float tExit = intersect_shape_b<BND>(P, ps, dvec, 0.0f, MER_INF);      // the segment crosses the (null) boundary once on its way out
                     const bool crosses = tExit >= 0 && tExit < dist;
                     f3 trA(1, 1, 1);
                     if (crosses && interactions == 0) trA = f3(0, 0, 0);
                     else trA = straight_transmittance<SIGMA>(P, rng, C, ps, dvec, crosses ? tExit : dist);
+                    // the other rectangles are all-absorbing occluders (tested after the walk: the sampler draws do not depend on them)
+                    if (P.n_rect > 1 && rect_blocks(P, ps, dvec, 0.0f, dist, k)) trA = f3(0, 0, 0);
                     value = value * trA;
                     if (!is_zero(value)) {
                         const float phaseVal = phase_eval(S.phase, S.g, wi, dvec);
@@ -926,7 +933,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             dsave = wo;
             if (CURVED) { itsT = 0; SET_FLAG(F_ITSVALID, true); }
             else { itsT = intersect_shape_b<BND>(P, ps, wo, 0.0f, MER_INF); SET_FLAG(F_ITSVALID, itsT >= 0); }
-            if (hasEnv || (EXTRA && P.has_area)) {
+            if (hasEnv || (EXTRA && P.n_rect)) {
                 W.kind = K_LOOKUP;
                 trOpt = (!CURVED && itsValid) ? itsT * S.rif_const : 0.0f;
                 if (!CURVED && !itsValid) { trv = f3(1, 1, 1); ev = EV_TR_DONE; }
@@ -1114,11 +1121,12 @@ __global__ void MER_CONNECT_BOUNDS connect_stage_kernel(const Params P, uint32_t
         rng.inc = (((((uint64_t) sample) << 32) | (uint64_t) pixel) << 1) | 1ULL;
         uint32_t *cs = P.cstate + (size_t) MER_CHK(P.chk, CHK_SLOT, i, P.nslots) * MER_CSTATE_WORDS;
         ConnState S; S.load(cs);
-        const f3 ps(SLOTF(CO_PSX), SLOTF(CO_PSY), SLOTF(CO_PSZ)), pp(P.sc.point_position[0], P.sc.point_position[1], P.sc.point_position[2]);
+        const DPoint &E = P.points[S.em];                   // the point emitter K_event selected for this connection
+        const f3 ps(SLOTF(CO_PSX), SLOTF(CO_PSY), SLOTF(CO_PSZ)), pp(E.pos[0], E.pos[1], E.pos[2]);
         if (S.phase == CP_OK) {
             // the connecting ray is known: transmittance along it, emitter value, phase function -- the luminaire sample of this vertex
             const f3 T(SLOTF(CO_TX), SLOTF(CO_TY), SLOTF(CO_TZ)), wi(SLOTF(CO_WIX), SLOTF(CO_WIY), SLOTF(CO_WIZ));
-            const f3 c0 = T * connection_value<RIF, STEPPER, SIGMA, BND>(P, rng, C, ps, wi, S.dir, S.dist, S.weight);
+            const f3 c0 = T * connection_value<RIF, STEPPER, SIGMA, BND>(P, E, rng, C, ps, wi, S.dir, S.dist, S.weight);
             const float plen = SLOTF(CO_PLEN) + edge_length(P, S.optDist);
             film_contribute(P, SLOTF(CO_PXF), SLOTF(CO_PYF), c0, plen);
             const f3 c = mod_weight<EXTRA>(P, c0, plen);

@@ -464,6 +464,8 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             if (props.hasProperty("toWorld")) Log_EError("Found a 'toWorld' transformation -- this is not allowed -- the area light inherits this transformation from its parent shape");
             o->radiance = props.getSpectrum("radiance", Spectrum{{1, 1, 1}});
         } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, point, area)");
+        o->samplingWeight = props.getFloat("samplingWeight", 1.0f);     // src/librender/emitter.cpp:103
+        if (!(o->samplingWeight > 0) || !std::isfinite(o->samplingWeight)) Log_EError("emitter \"" + type + "\": samplingWeight must be positive");
         out = o;
     } else Log_EError("Unsupported scene element <" + tag + ">");
     return out;
@@ -678,8 +680,7 @@ std::shared_ptr<Scene> loadScene(const std::string &path, const std::map<std::st
 
 // ------------------------------------------------------------------------------------------------ integrator
 // the point emitter inside the medium shape: cube, sphere, or the negative region of the signed-distance grid (trilinear, as lookupFloat)
-static bool point_inside_shape(const mer_scene_desc &d, const Medium &m) {
-    const float *p = d.point_position;
+static bool point_inside_shape(const mer_scene_desc &d, const Medium &m, const float *p) {
     if (d.boundary == MER_BOUNDARY_SPHERE) {
         float d2 = 0; for (int i = 0; i < 3; i++) d2 += (p[i] - d.sph_center[i]) * (p[i] - d.sph_center[i]);
         return d2 < d.sph_radius * d.sph_radius;
@@ -765,30 +766,55 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     }
     d.phase = m.phase->kind; d.g = m.phase->g;
     d.tr_estimator = m.trEstimator; d.method = m.method; d.het_stepsize = m.hetStepSize;
+    // point emitters and the area emitters of `rectangle` shapes, in scene order (rectangles first).  At most one of each kind: the single-emitter
+    // fields of the scene desc; more: the emitter list (scene.emitterList), each entry with its samplingWeight
     int nconst = 0, npoint = 0, narea = 0;
+    std::vector<mer_emitter> &list = scene.emitterList;
+    list.clear();
     for (int i = 0; i < 3; i++) { d.env_radiance[i] = 0; d.point_intensity[i] = 0; d.point_position[i] = 0; d.emission[i] = m.emission.c[i]; d.area_radiance[i] = 0; }
     for (int i = 0; i < 12; i++) d.area_to_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    d.n_emitters = 0; d.emitters = nullptr;
     for (auto &sh : scene.shapes) {
         if (!sh->isRectangle) continue;
         if (!sh->areaEmitter) Log_EError("shape \"rectangle\" is supported on the GPU path as the carrier of an area emitter only");
-        if (++narea > 1) Log_EError("Only one area emitter is supported on the GPU path");
-        for (int i = 0; i < 12; i++) d.area_to_world[i] = sh->rectToWorld[i];
-        for (int i = 0; i < 3; i++) d.area_radiance[i] = sh->areaEmitter->radiance.c[i];
+        mer_emitter e{}; e.type = MER_EMITTER_AREA; e.sampling_weight = sh->areaEmitter->samplingWeight;
+        for (int i = 0; i < 12; i++) e.to_world[i] = sh->rectToWorld[i];
+        for (int i = 0; i < 3; i++) e.radiance[i] = sh->areaEmitter->radiance.c[i];
+        list.push_back(e); ++narea;
     }
     for (auto &e : scene.emitters) {
         if (e->kind == Emitter::EArea) Log_EError("An area light must be child of a shape instance");            // area.cpp:200-201
         if (e->kind == Emitter::EPoint) {
-            if (++npoint > 1) Log_EError("Only one point emitter is supported on the GPU path");
-            d.point_position[0] = e->position.x; d.point_position[1] = e->position.y; d.point_position[2] = e->position.z;
-            for (int i = 0; i < 3; i++) d.point_intensity[i] = e->radiance.c[i];
+            mer_emitter q{}; q.type = MER_EMITTER_POINT; q.sampling_weight = e->samplingWeight;
+            q.position[0] = e->position.x; q.position[1] = e->position.y; q.position[2] = e->position.z;
+            for (int i = 0; i < 3; i++) q.intensity[i] = e->radiance.c[i];
+            list.push_back(q); ++npoint;
         } else {
             if (++nconst > 1) Log_EError("Only one constant emitter is supported on the GPU path");
             for (int i = 0; i < 3; i++) d.env_radiance[i] = e->radiance.c[i];
         }
     }
+    if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point and area emitters are supported on the GPU path");
+    if (npoint <= 1 && narea <= 1) {
+        for (const mer_emitter &e : list) {
+            if (e.type == MER_EMITTER_AREA) { for (int i = 0; i < 12; i++) d.area_to_world[i] = e.to_world[i]; for (int i = 0; i < 3; i++) d.area_radiance[i] = e.radiance[i]; }
+            else for (int i = 0; i < 3; i++) { d.point_position[i] = e.position[i]; d.point_intensity[i] = e.intensity[i]; }
+        }
+        list.clear();
+    } else { d.n_emitters = (int32_t) list.size(); d.emitters = list.data(); }
     if (d.boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {
         if (narea) Log_EError("hroughdielectric: the area emitter needs an index-matched (null) boundary");
-        if (npoint && point_inside_shape(d, m)) Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+        if (npoint == 1 && point_inside_shape(d, m, d.point_position))
+            Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+        for (const mer_emitter &e : list)
+            if (point_inside_shape(d, m, e.position))
+                Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+    }
+    if (narea && !list.empty()) {     // the checks mer_render applies to the list (the area emitter's own checks run there too)
+        if (d.rif_mode != MER_RIF_CONST) Log_EError("the area emitter is built for straight rays (rif_mode = CONST)");
+        for (const mer_emitter &e : list)
+            if (e.type == MER_EMITTER_POINT && d.boundary != MER_BOUNDARY_SDF && !point_inside_shape(d, m, e.position))
+                Log_EError("a point emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
     }
 }
 
@@ -919,6 +945,9 @@ int merhost_flatten_xml(const char *path, const char *defines, mer_scene_desc *o
     try {
         auto scene = merhost::loadScene(path, parseDefines(defines));
         scene->integrator->flatten(*scene, *out);
+        static std::vector<mer_emitter> g_flat_emitters;             // out->emitters outlives the scene: the library keeps the list
+        g_flat_emitters = scene->emitterList;
+        out->emitters = out->n_emitters ? g_flat_emitters.data() : nullptr;
         if (spp) *spp = scene->sensor->sampler->sampleCount;
         return 0;
     } catch (const std::exception &e) { g_host_error = e.what(); return 1; }

@@ -186,6 +186,7 @@ public:
     enum Kind { EConstant, EPoint, EArea } kind = EConstant;
     Spectrum radiance{};                        // constant / area: radiance ; point: intensity
     Vec3 position{0, 0, 0};                     // point (src/emitters/point.cpp:60-68)
+    float samplingWeight = 1.0f;                // `samplingWeight` (src/librender/emitter.cpp:103): selection weight among the emitters of its kind
 };
 
 class Scene;
@@ -194,7 +195,8 @@ class Integrator : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "Integrator"; }
     int maxDepth = -1, rrDepth = 5; bool hideEmitters = false, strictNormals = false;
-    /// flatten (validates like the reference's configure()) -- no GPU needed
+    /// flatten (validates like the reference's configure()) -- no GPU needed.  Several point or area emitters: desc.emitters points into
+    /// scene.emitterList, which must outlive desc
     void flatten(const Scene &scene, mer_scene_desc &desc) const;
     /// upload volumes, render `spp` samples per pixel (0 = the sampler's sampleCount), return the film [h][w][5]
     std::vector<float> render(const Scene &scene, int device, int spp, unsigned long long seed, int layout) const;
@@ -210,6 +212,7 @@ public:
     std::shared_ptr<Integrator> integrator; std::shared_ptr<Sensor> sensor;
     std::vector<std::shared_ptr<Shape>> shapes; std::vector<std::shared_ptr<Emitter>> emitters;
     std::vector<std::shared_ptr<Medium>> media;
+    mutable std::vector<mer_emitter> emitterList;       // storage behind mer_scene_desc.emitters (Integrator::flatten)
 };
 
 /// PluginManager::createObject (src/libcore/plugin.cpp:180-196): plugin found by its short name = XML `type`
@@ -232,7 +235,8 @@ void writeExr(const std::string &path, const float *rgb, int h, int w);
 extern "C" {
 /* C entry points of libmer_host.so for non-C++ callers (tests): return 0 / 1, message via merhost_last_error() */
 const char *merhost_last_error(void);
-/* parse + validate only: fills the flat scene (volumes = 0 handles) and width/height/spp */
+/* parse + validate only: fills the flat scene (volumes = 0 handles) and width/height/spp; out->emitters (several point or area emitters)
+   points to storage of the library that stays valid until the next merhost_flatten_xml call */
 int merhost_flatten_xml(const char *path, const char *defines /* "k=v;k=v" */, mer_scene_desc *out, int32_t *spp);
 /* parse, upload, render on `device`; film_host = float[h][w][5] of the scene's film size (query with flatten first) */
 int merhost_render_xml(const char *path, const char *defines, int32_t device, int32_t spp, uint64_t seed, int32_t layout, float *film_host);

@@ -109,6 +109,9 @@ class SceneParams:
         # emitter `area` on a `rectangle` shape (src/emitters/area.cpp, src/shapes/rectangle.cpp): the image of [-1,1]^2 x {0} under area_to_world
         # (3x4 or 4x4, no shear; None = identity), radiance into the half space of its normal toWorld(0,0,1); zero radiance = none
         self.area_to_world = None; self.area_radiance = [0.0, 0.0, 0.0]
+        # several point / area emitters (include/mer.h: mer_emitter): a list of point_emitter(...) / area_emitter(...) entries.  Non-empty:
+        # point_intensity and area_radiance must stay zero; one emitter of each kind is sampled per collision, chosen by samplingWeight
+        self.emitters = []
         # film decomposition (src/librender/film.cpp:56-84): 0 none | 1 transient | 2 bounce (bins by edge count); frames = ceil((max-min)/binWidth)
         self.decomposition = DECOMPOSITION_NONE; self.min_bound = 0.0; self.max_bound = 0.0; self.bin_width = 1.0
         self.calibrated_transient = False
@@ -127,6 +130,22 @@ class SceneParams:
                 raise AttributeError("unknown scene parameter '%s'" % k)
             setattr(q, k, v)
         return q
+
+
+EMITTER_POINT = 1
+EMITTER_AREA = 2
+MAX_EMITTERS = 32
+
+
+def point_emitter(position, intensity, sampling_weight=1.0):
+    """an entry of SceneParams.emitters: emitter `point` (src/emitters/point.cpp) with its `samplingWeight`"""
+    return {"type": EMITTER_POINT, "position": [float(v) for v in position], "intensity": [float(v) for v in intensity],
+            "sampling_weight": float(sampling_weight)}
+
+
+def area_emitter(to_world, radiance, sampling_weight=1.0):
+    """an entry of SceneParams.emitters: emitter `area` on a `rectangle`, the image of [-1,1]^2 x {0} under to_world (3x4 or 4x4, no shear)"""
+    return {"type": EMITTER_AREA, "to_world": to_world, "radiance": [float(v) for v in radiance], "sampling_weight": float(sampling_weight)}
 
 
 def sdf_max_error(p):

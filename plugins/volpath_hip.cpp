@@ -242,7 +242,8 @@ public:
         /* ---- medium, phase function, volumes */
         fillMedium(ctx, shape->getInteriorMedium(), d, volumes);
 
-        /* ---- emitters: constant environment and / or one point emitter */
+        /* ---- emitters: constant environment, point emitters and area emitters on rectangles.  One of each kind at most: the single-emitter
+           fields of mer_scene_desc; more: the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
         if (const Emitter *env = scene->getEnvironmentEmitter()) {
             if (env->getClass()->getName() != "ConstantBackgroundEmitter") Log(EError, "volpath_hip: the environment emitter must be 'constant'");
             const Spectrum L = env->evalEnvironment(RayDifferential(Point(0.0f), Vector(0, 0, 1), 0));
@@ -250,6 +251,8 @@ public:
             d.env_radiance[0] = r; d.env_radiance[1] = g; d.env_radiance[2] = b;
         }
         const ref_vector<Emitter> &emitters = scene->getEmitters();
+        std::vector<mer_emitter> list;
+        int npoint = 0, narea = 0;
         for (size_t i = 0; i < emitters.size(); ++i) {
             const Emitter *e = emitters[i].get();
             if (e->isEnvironmentEmitter()) continue;
@@ -264,19 +267,38 @@ public:
                 const Point c = p00.p + du + dv;
                 const Normal n = p00.n;                                                          /* the frame normal, toWorld(Normal(0,0,1)) normalized */
                 const float cols[3][4] = { { du.x, dv.x, n.x, c.x }, { du.y, dv.y, n.y, c.y }, { du.z, dv.z, n.z, c.z } };
-                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) d.area_to_world[4 * r + k] = cols[r][k];
                 PositionSamplingRecord pr(0.0f); rs->samplePosition(pr, Point2(0.5f));
                 const Spectrum Le = e->evalPosition(pr) * INV_PI;                                 /* AreaLight::evalPosition = radiance * pi (area.cpp:98-100) */
                 Float r, g, b; Le.toLinearRGB(r, g, b);
-                d.area_radiance[0] = r; d.area_radiance[1] = g; d.area_radiance[2] = b;
+                mer_emitter m; memset(&m, 0, sizeof(m));
+                m.type = MER_EMITTER_AREA; m.sampling_weight = (float) e->getSamplingWeight();
+                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) m.to_world[4 * r + k] = cols[r][k];
+                m.radiance[0] = r; m.radiance[1] = g; m.radiance[2] = b;
+                list.push_back(m); ++narea;
                 continue;
             }
             if (e->getClass()->getName() != "PointEmitter") Log(EError, "volpath_hip: emitters must be 'constant', 'point' or 'area' (on a rectangle)");
             PositionSamplingRecord pRec(0.0f);
             const Spectrum I = e->samplePosition(pRec, Point2(0.5f)) / (4 * M_PI);       /* src/emitters/point.cpp:82-90 */
             Float r, g, b; I.toLinearRGB(r, g, b);
-            d.point_intensity[0] = r; d.point_intensity[1] = g; d.point_intensity[2] = b;
-            d.point_position[0] = pRec.p.x; d.point_position[1] = pRec.p.y; d.point_position[2] = pRec.p.z;
+            mer_emitter m; memset(&m, 0, sizeof(m));
+            m.type = MER_EMITTER_POINT; m.sampling_weight = (float) e->getSamplingWeight();
+            m.intensity[0] = r; m.intensity[1] = g; m.intensity[2] = b;
+            m.position[0] = pRec.p.x; m.position[1] = pRec.p.y; m.position[2] = pRec.p.z;
+            list.push_back(m); ++npoint;
+        }
+        if (npoint <= 1 && narea <= 1) {
+            for (size_t i = 0; i < list.size(); ++i) {
+                const mer_emitter &m = list[i];
+                if (m.type == MER_EMITTER_AREA) {
+                    for (int k = 0; k < 12; ++k) d.area_to_world[k] = m.to_world[k];
+                    for (int k = 0; k < 3; ++k) d.area_radiance[k] = m.radiance[k];
+                } else
+                    for (int k = 0; k < 3; ++k) { d.point_intensity[k] = m.intensity[k]; d.point_position[k] = m.position[k]; }
+            }
+        } else {
+            if (list.size() > MER_MAX_EMITTERS) Log(EError, "volpath_hip: at most %i point and area emitters", (int) MER_MAX_EMITTERS);
+            d.n_emitters = (int32_t) list.size(); d.emitters = &list[0];       /* `list` outlives the mer_multi_render below */
         }
 
         /* ---- render on every listed GPU, then hand the reduced image to the film as one block */
