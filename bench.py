@@ -12,6 +12,10 @@ line.  A world size that differs from --gpus is an error.  --scaling weak (defau
 (spp x N)-sample job, sample-interleaved.  --scaling strong: the job is fixed (--spp samples per pixel of the whole film) and is cut
 into 32x32 image tiles dealt round-robin to the ranks (the reference's block partition, src/librender/renderproc.cpp:79,142-149).
 Either way the film is sum-reduced with one RCCL all-reduce inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set-up, --warmup steps, --steps timed steps, --dump-outputs, the line.
+--full adds what takes runs or steps of its own: the roofline (rocprofv3 counter passes in child processes and one single-pipeline
+step), the CPU baseline and the 512^3 target block; --no-cpu-baseline, --no-target-512, --no-solo-step and --no-live-pmc skip parts of it.
 """
 import argparse
 import json
@@ -69,7 +73,7 @@ def dominant_family(workload):
 
 def live_pmc(workload, res, size, spp, layout, options, budget_s=240.0):
     """Counter passes of THIS workload taken in THIS run: for every entry of PMC_PASSES one child process `rocprofv3 --pmc <counters>
-    --kernel-trace -- python3 bench.py <one single-pipeline step>`, started before this process touches the GPU (a GPU process must not
+    --kernel-trace -- python3 bench.py <one plain single-pipeline step>`, started before this process touches the GPU (a GPU process must not
     exec; and the profiler's counters need the chip to themselves).  Returns the traffic entry (as profiles/round3/hbm_traffic.json
     holds them) or (None, reason)."""
     import shutil
@@ -90,7 +94,7 @@ def live_pmc(workload, res, size, spp, layout, options, budget_s=240.0):
         out = tempfile.mkdtemp(prefix="mer_pmc_%s_" % name, dir="/tmp")
         cmd = [exe, "--pmc"] + ctrs.split() + ["--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
                "--workload", workload, "--res", str(res), "--size", str(size), "--spp", str(spp), "--layout", layout, "--steps", "1", "--warmup", "0",
-               "--no-cpu-baseline", "--no-solo-step", "--no-target-512", "--no-live-pmc", "--options", opts]
+               "--options", opts]
         env = dict(os.environ); env["TMPDIR"] = "/tmp"; env["MER_BENCH_PMC_CHILD"] = "1"
         try:
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=left)
@@ -330,7 +334,7 @@ def spawn_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -345,18 +349,26 @@ def main():
     ap.add_argument("--shard", default=None, choices=["samples", "tiles"], help="default: samples for weak scaling, tiles for strong")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--device", type=int, default=None, help="force this GPU index for every rank (rehearsal on one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the roofline (counter passes + one single-pipeline step), the CPU baseline and the 512^3 target block")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (and without the 512^3 block)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-target-512", action="store_true", help="skip the 512^3 block of the default run")
-    ap.add_argument("--no-solo-step", action="store_true", help="skip the extra single-pipeline step (profiled runs)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not take the roofline's counter passes (child rocprofv3 runs) inside this run; fall back to the committed pass")
+    ap.add_argument("--no-target-512", action="store_true", help="--full without the 512^3 block")
+    ap.add_argument("--no-solo-step", action="store_true", help="--full without the single-pipeline step, hence without the roofline (profiled runs)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full without its own counter passes (child rocprofv3 runs): the roofline falls back to the committed pass")
     ap.add_argument("--options", default="", help="mer_context_set_option pairs, e.g. pipes=1,ksteps=96")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the film of the last timed step to DIR/film.npy (float32; a seeded pixel sample above 64 MB)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.dump_outputs and args.steps < 1:
         ap.error("--dump-outputs needs --steps >= 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_target_512 = args.no_solo_step = args.no_live_pmc = True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     if args.layout == "auto":

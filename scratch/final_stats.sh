@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final_stats; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() { tag=$1; shift
   rm -rf /tmp/prof_$tag
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py "$@" > $O/${tag}_bench.json 2> $O/${tag}_stderr.txt
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py --full "$@" > $O/${tag}_bench.json 2> $O/${tag}_stderr.txt
   f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${tag}_kernel_stats.csv
   echo "$tag rc=$? $(tail -c 300 $O/${tag}_bench.json | head -c 10)"; tail -1 $O/${tag}_bench.json | cut -c1-260

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3_stats; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() { tag=$1; shift
   rm -rf /tmp/prof_$tag
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py --no-live-pmc --no-cpu-baseline --no-target-512 "$@" > $O/${tag}_bench.json 2> $O/${tag}_stderr.txt
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 $R/bench.py --full --no-live-pmc --no-cpu-baseline --no-target-512 "$@" > $O/${tag}_bench.json 2> $O/${tag}_stderr.txt
   f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/${tag}_kernel_stats.csv
   echo "$tag: $(python3 -c "import json,sys; d=json.loads(open('$O/${tag}_bench.json').read().strip().splitlines()[-1]); print('%.1f Mpaths/s %.1f ms' % (d['value'], d['ms_per_step']))" 2>&1 | tail -1)"
