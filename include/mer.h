@@ -60,13 +60,25 @@ typedef struct {
    (position, intensity -- as point_position / point_intensity); MER_EMITTER_AREA: emitter `area` on a `rectangle` (to_world, radiance --
    as area_to_world / area_radiance).  The fields of the other kind are ignored.  sampling_weight = the emitter's `samplingWeight`
    (src/librender/emitter.cpp:103; > 0, 1 in the XML by default): at every collision ONE emitter of each kind is sampled, emitter k with
-   probability sampling_weight_k / (sum of the weights of its kind), and its sample is divided by that probability. */
+   probability sampling_weight_k / (sum of the weights of its kind), and its sample is divided by that probability.
+   MER_EMITTER_SPOT: emitter `spot` (src/emitters/spot.cpp:66-200), a point emitter with a cone -- list entries only.  to_world = its frame
+   (row-major 3x4; the position is its translation column, `position` is ignored), intensity = its peak intensity, cutoff_angle_deg /
+   beam_width_deg = `cutoffAngle` / `beamWidth` in degrees (0 <= beam <= cutoff <= 180; the XML defaults are 20 and 3/4 of the cutoff).  It
+   joins the point emitters: same selection CDF, same connections, and every evaluation is multiplied by falloffCurve (:105-118) with
+   cosTheta = z row of the inverse of to_world's linear part . (-d) -- not normalised, as the reference has it -- where d is the unit
+   STRAIGHT-LINE direction from the shading point to the emitter, also for curved rays (the reference's volpath takes the emitter value from
+   sampleDirect before the medium's curved eval, scene.cpp:854-874; heterogeneousrefractive.cpp:571-640).  The projection `texture` is not
+   built. */
 #define MER_MAX_EMITTERS 32
-enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2 };
+enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3 };
 typedef struct {
     int32_t type;
     float   position[3], intensity[3];
-    float   to_world[12], radiance[3];
+    float   to_world[12];
+    union {                                          /* a spot's angles overlay the radiance it does not have: the record keeps its size */
+        float radiance[3];                           /* MER_EMITTER_AREA */
+        struct { float cutoff_angle_deg, beam_width_deg, spot_reserved; };      /* MER_EMITTER_SPOT (spot_reserved: 0) */
+    };
     float   sampling_weight;
 } mer_emitter;
 
@@ -303,6 +315,10 @@ int  mer_eval_transmittance(mer_context *ctx, const mer_scene_desc *scene, const
    (p1 inside the medium shape -- cube, sphere or signed-distance grid --, p2 inside or outside it) by a curved ray; out stride 12: ok, weight, dirToP2[3] (optical momentum at p1),
    revDirToP1[3], distance, opticalLength, 0, 0; RNG stream of item i = (seed, pixel=i, sample=0) */
 int  mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1, const float *p2, int64_t n, uint64_t seed, float *out);
+/* PointEmitter / SpotEmitter::sampleDirect (src/emitters/point.cpp, spot.cpp:184-199) of entry k of the scene's emitter list (a point or a
+   spot) at n reference points ref[3*i..]: out stride 8: value RGB (intensity x falloff / dist^2, NOT divided by the selection pdf), the unit
+   direction to the emitter [3], the distance, the falloff (1 for a point).  The render kernels' own device function. */
+int  mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, int64_t n, float *out);
 /* PhaseFunction::sample / eval (src/phase/hg.cpp:74-110, src/phase/isotropic.cpp:62-78) */
 int  mer_phase_sample(mer_context *ctx, int32_t phase, float g, const float *wi, const float *u2, int64_t n, float *wo, float *pdf);
 int  mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, const float *wo, int64_t n, float *val);

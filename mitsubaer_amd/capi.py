@@ -22,7 +22,7 @@ SYMBOLS = [
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
-    "mer_sample_distance", "mer_connect", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
+    "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
     "mer_rough_dielectric_sample", "mer_camera_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
@@ -37,10 +37,20 @@ class GridDesc(C.Structure):
                 ("aabb_min", C.c_float * 3), ("aabb_max", C.c_float * 3), ("world_to_volume", C.c_float * 12)]
 
 
+class _SpotAngles(C.Structure):
+    _fields_ = [("cutoff_angle_deg", C.c_float), ("beam_width_deg", C.c_float), ("spot_reserved", C.c_float)]
+
+
+class _RadianceOrAngles(C.Union):
+    _anonymous_ = ("_angles",)
+    _fields_ = [("radiance", C.c_float * 3), ("_angles", _SpotAngles)]
+
+
 class EmitterDesc(C.Structure):
-    """mer_emitter: one entry of SceneDesc.emitters"""
+    """mer_emitter: one entry of SceneDesc.emitters (a spot's cutoff_angle_deg / beam_width_deg overlay radiance)"""
+    _anonymous_ = ("_u",)
     _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("intensity", C.c_float * 3),
-                ("to_world", C.c_float * 12), ("radiance", C.c_float * 3), ("sampling_weight", C.c_float)]
+                ("to_world", C.c_float * 12), ("_u", _RadianceOrAngles), ("sampling_weight", C.c_float)]
 
 
 class SceneDesc(C.Structure):
@@ -184,6 +194,16 @@ def validate_emitters(p):
             if p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC and inside:
                 raise MerError(at + "hroughdielectric: the point emitter must lie outside the medium shape")
             outside_point = outside_point or (p.boundary != P.BOUNDARY_SDF and not inside)
+        elif e["type"] == P.EMITTER_SPOT:
+            err = P.spot_error(e.get("to_world"), e["cutoff_deg"], e["beam_deg"])
+            if err:
+                raise MerError(at + err)
+            if not all(np.isfinite(v) and v >= 0 for v in e["intensity"]):
+                raise MerError(at + "emitter radiance / intensity must be non-negative")
+            inside = _point_in_shape(p, P.spot_position(e))
+            if p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC and inside:
+                raise MerError(at + "hroughdielectric: the spot emitter must lie outside the medium shape")
+            outside_point = outside_point or (p.boundary != P.BOUNDARY_SDF and not inside)
         elif e["type"] == P.EMITTER_AREA:
             if p.rif_mode != P.RIF_CONST:
                 raise MerError(at + "the area emitter is built for straight rays (rif_mode = CONST)")
@@ -197,7 +217,7 @@ def validate_emitters(p):
         else:
             raise MerError(at + "unknown emitter type")
     if has_rect and outside_point:
-        raise MerError("emitter list: a point emitter outside the medium shape cannot be combined with an area emitter")
+        raise MerError("emitter list: a point or spot emitter outside the medium shape cannot be combined with an area emitter")
 
 
 class Shard(C.Structure):
@@ -417,6 +437,9 @@ class Context:
                 e.type = int(d["type"]); e.sampling_weight = float(d.get("sampling_weight", 1.0))
                 if e.type == P.EMITTER_POINT:
                     e.position[:] = [float(v) for v in d["position"]]; e.intensity[:] = [float(v) for v in d["intensity"]]
+                elif e.type == P.EMITTER_SPOT:
+                    e.to_world[:] = _rows3x4(d.get("to_world")); e.intensity[:] = [float(v) for v in d["intensity"]]
+                    e.cutoff_angle_deg = float(d["cutoff_deg"]); e.beam_width_deg = float(d["beam_deg"])
                 else:
                     e.to_world[:] = _rows3x4(d.get("to_world")); e.radiance[:] = [float(v) for v in d["radiance"]]
             s.n_emitters = len(ems)
@@ -555,6 +578,14 @@ class Context:
         p1 = _f32(p1); p2 = _f32(p2); n = p1.shape[0]
         out = np.zeros((n, 12), np.float32)
         self._check(self.lib.mer_connect(self.h, C.byref(scene), _fp(p1), _fp(p2), C.c_int64(n), C.c_uint64(seed), _fp(out)))
+        return out
+
+    def emitter_direct(self, scene, k, ref):
+        """mer_emitter_direct: sampleDirect of emitter-list entry k (a point or a spot) at the reference points ref (n x 3); (n, 8) float32:
+        value RGB (not divided by the selection pdf), unit direction to the emitter, distance, falloff"""
+        ref = _f32(ref).reshape(-1, 3); n = ref.shape[0]
+        out = np.zeros((n, 8), np.float32)
+        self._check(self.lib.mer_emitter_direct(self.h, C.byref(scene), C.c_int32(k), _fp(ref), C.c_int64(n), _fp(out)))
         return out
 
     def eval_transmittance(self, scene, o, d, maxt, seed):

@@ -187,13 +187,36 @@ static bool rect_meets_shape(const mer_scene_desc *sc, const double M[3][4]) {
     return true;
 }
 
-// mer_scene_desc.emitters -> the point / area tables: each entry checked as the single emitter of its kind is, the rectangles by the exact
+// emitter `spot` (src/emitters/spot.cpp:68-95): the cone record of its point-table slot, in float as the reference derives it (degToRad in
+// float, util.h:293; std::cos of the float angle).  The z row of the inverse linear part is computed in double and rounded.  Returns an
+// error message or nullptr.
+static const char *spot_derive(const mer_emitter &e, DSpot &s) {
+    const float cdeg = e.cutoff_angle_deg, bdeg = e.beam_width_deg;
+    if (!std::isfinite(cdeg) || !std::isfinite(bdeg) || cdeg < 0 || bdeg < 0) return "spot emitter: cutoffAngle and beamWidth must be finite and non-negative";
+    if (cdeg > 180) return "spot emitter: cutoffAngle must not exceed 180 degrees";
+    if (bdeg > cdeg) return "spot emitter: beamWidth must not exceed cutoffAngle (Assert(m_cutoffAngle >= m_beamWidth))";
+    double M[3][3];
+    for (int i = 0; i < 12; i++) { if (!std::isfinite(e.to_world[i])) return "spot emitter: 'toWorld' must be finite"; if (i % 4 != 3) M[i / 4][i % 4] = e.to_world[i]; }
+    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return "spot emitter: 'toWorld' is singular";
+    s.z[0] = (float) ((M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det);       // row 2 of the inverse
+    s.z[1] = (float) ((M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det);
+    s.z[2] = (float) ((M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det);
+    const float beam = (float) (bdeg * (M_PI / 180.0f)), cutoff = (float) (cdeg * (M_PI / 180.0f));
+    s.cos_beam = std::cos(beam); s.cos_cutoff = std::cos(cutoff);
+    s.cutoff = cutoff; s.inv_width = 1.0f / (cutoff - beam);
+    s.pad = 0;
+    return nullptr;
+}
+
+// mer_scene_desc.emitters -> the point / area tables (and the spots' cones, one per point-table slot): each entry checked as the single emitter of its kind is, the rectangles by the exact
 // outside test, then every kind's selection pdf = sampling_weight / sum and its CDF
-static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects) {
+static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects, std::vector<DSpot> &spots) {
     if (sc->n_emitters < 0 || sc->n_emitters > MER_MAX_EMITTERS) return fail(ctx, "emitter list: at most " + std::to_string(MER_MAX_EMITTERS) + " entries (MER_MAX_EMITTERS)");
     if (!sc->emitters) return fail(ctx, "emitter list: n_emitters > 0 but no entries");
     if (!points.empty() || !rects.empty()) return fail(ctx, "emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0");
     std::vector<double> wp, wr;
+    bool any_spot = false;
     for (int j = 0; j < sc->n_emitters; ++j) {
         const mer_emitter &e = sc->emitters[j];
         const std::string at = "emitter list, entry " + std::to_string(j) + ": ";
@@ -205,6 +228,17 @@ static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::v
             DPoint E{};
             for (int i = 0; i < 3; i++) { E.pos[i] = e.position[i]; E.Ie[i] = e.intensity[i]; }
             points.push_back(E); wp.push_back(e.sampling_weight);
+            DSpot none{}; none.cos_cutoff = none.cos_beam = -2.0f; spots.push_back(none);         // falloff 1
+        } else if (e.type == MER_EMITTER_SPOT) {      // a point emitter at toWorld's origin with a cone: it joins the point table
+            DSpot cone{};
+            if (const char *err = spot_derive(e, cone)) return fail(ctx, at + err);
+            DPoint E{};
+            for (int i = 0; i < 3; i++) { E.pos[i] = e.to_world[4 * i + 3]; E.Ie[i] = e.intensity[i]; }
+            for (int i = 0; i < 3; i++) if (!(e.intensity[i] >= 0) || !std::isfinite(e.intensity[i])) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
+            if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point_in_shape(sc, E.pos))
+                return fail(ctx, at + "hroughdielectric: the spot emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+            points.push_back(E); wp.push_back(e.sampling_weight); spots.push_back(cone);
+            any_spot = true;
         } else if (e.type == MER_EMITTER_AREA) {
             if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, at + "the area emitter is built for straight rays (rif_mode = CONST)");
             if (sc->boundary_bsdf != MER_BSDF_NULL || sc->boundary == MER_BOUNDARY_SDF) return fail(ctx, at + "the area emitter needs an index-matched cube / sphere boundary");
@@ -219,7 +253,8 @@ static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::v
     if (!rects.empty())
         for (const DPoint &E : points)
             if (!point_in_shape(sc, E.pos))
-                return fail(ctx, "emitter list: a point emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
+                return fail(ctx, "emitter list: a point or spot emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
+    if (!any_spot) spots.clear();                 // point-only scenes carry no cone table: the kernels skip the falloff
     // selection pdf and CDF of every kind; the sample of emitter k is divided by its pdf on the host (intensity / pdf, radiance / pdf)
     double sum = 0, cum = 0;
     for (double w : wp) sum += w;
@@ -384,7 +419,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         // (a signed-distance shape: tested below, where its grid is known)
         if (point && point_in_shape(sc, sc->point_position)) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
-    std::vector<DPoint> points; std::vector<DRect> rects;
+    std::vector<DPoint> points; std::vector<DRect> rects; std::vector<DSpot> spots;
     const bool legacy_area = sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0;
     const bool legacy_point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
     if (legacy_area) {
@@ -411,7 +446,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         E.pdf = E.cdf = 1.0f;
         points.push_back(E);
     }
-    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects)) return 1;
+    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects, spots)) return 1;
     if (film_frames(ctx, sc, P.frames)) return 1;
     P.film_ch = P.frames * 3 + 2;
     P.mod_phase = (float) (sc->mod_phase_deg * M_PI / 180);                                                   // pathlengthsampler.cpp:15
@@ -456,10 +491,11 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
     ctx->point_outside = false;
     for (const DPoint &E : points) if (sc->boundary != MER_BOUNDARY_SDF && !point_in_shape(sc, E.pos)) ctx->point_outside = true;
     {   // the tables go to device memory when they change; no kernel of this context is in flight here (renders and leaf calls return synchronised)
-        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, bytes = off + sizeof(DRect) * MER_MAX_EMITTERS;
+        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, off_spot = off + sizeof(DRect) * MER_MAX_EMITTERS, bytes = off_spot + sizeof(DSpot) * MER_MAX_EMITTERS;
         std::vector<unsigned char> h(bytes, 0);
         if (!points.empty()) std::memcpy(h.data(), points.data(), sizeof(DPoint) * points.size());
         if (!rects.empty()) std::memcpy(h.data() + off, rects.data(), sizeof(DRect) * rects.size());
+        if (!spots.empty()) std::memcpy(h.data() + off_spot, spots.data(), sizeof(DSpot) * spots.size());
         if (!ctx->etab) HIP_CHECK(ctx, hipMalloc(&ctx->etab, bytes));
         if (ctx->etab_host != h) {
             HIP_CHECK(ctx, hipMemcpy(ctx->etab, h.data(), bytes, hipMemcpyHostToDevice));
@@ -467,6 +503,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         }
         P.n_point = (int32_t) points.size(); P.n_rect = (int32_t) rects.size();
         P.points = (const DPoint *) ctx->etab; P.rects = (const DRect *) ((const unsigned char *) ctx->etab + off);
+        P.has_spot = spots.empty() ? 0 : 1;             // the kernels find the cones at off_spot (spot_table)
     }
     P.counters = ctx->counters;
     P.work_counter = ctx->counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
@@ -1123,6 +1160,24 @@ int mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, co
     hipLaunchKernelGGL(phase_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, phase, g, a.as<float>(), b.as<float>(), n, c.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
     return c.download(val, n * 4);
+}
+int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, int64_t n, float *out) {
+    MER_USE_DEVICE(ctx);
+    if (scene->n_emitters <= 0 || !scene->emitters) return fail(ctx, "mer_emitter_direct: the scene has no emitter list");
+    if (k < 0 || k >= scene->n_emitters) return fail(ctx, "mer_emitter_direct: entry index out of range");
+    const int type = scene->emitters[k].type;
+    if (type != MER_EMITTER_POINT && type != MER_EMITTER_SPOT) return fail(ctx, "mer_emitter_direct: entry k must be a point or spot emitter");
+    int slot = 0;                                   // its slot of the point table: the point / spot entries before it, in list order
+    for (int j = 0; j < k; ++j) slot += (scene->emitters[j].type == MER_EMITTER_POINT || scene->emitters[j].type == MER_EMITTER_SPOT) ? 1 : 0;
+    Params P;
+    if (make_params(ctx, scene, P, true)) return 1;
+    if (n <= 0) return 0;
+    const float *I = scene->emitters[k].intensity;
+    DevBuf a(ctx), r(ctx);
+    if (a.upload(ref, n * 12) || r.alloc(n * 32)) return 1;
+    hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, (const DSpot *) (P.has_spot ? P.rects + MER_MAX_EMITTERS : nullptr), slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    return r.download(out, n * 32);
 }
 int mer_rough_dielectric_eval(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *wo, int64_t n,
                               float *out_val, float *out_pdf) {

@@ -543,7 +543,8 @@ template <bool CURVED, int RIF, int STEPPER, int SIGMA, int BND = 0>
 __device__ __forceinline__ f3 point_nee(const Params &P, Rng &rng, LaneCounters &C, f3 ps, f3 wi, int depth, float &optLen) {   // inlined: an out-of-line callee taking Params by reference forces a scratch copy of the kernel arguments
     optLen = 0.0f;
     const mer_scene_desc &S = P.sc;
-    float pk; const DPoint &E = P.points[emitter_select(P.points, P.n_point, rng, 3, pk)];     // one of the point emitters; E.Ie = I / its pdf
+    float pk; const int k = emitter_select(P.points, P.n_point, rng, 3, pk);
+    const DPoint &E = P.points[k];                          // one of the point emitters; E.Ie = I / its pdf
     const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);
     const f3 pp(E.pos[0], E.pos[1], E.pos[2]);
     const int interactions = S.max_depth - depth - 1;
@@ -554,6 +555,7 @@ __device__ __forceinline__ f3 point_nee(const Params &P, Rng &rng, LaneCounters 
         const float dist = sqrtf(dot(dvec, dvec)), invDist = 1.0f / dist;
         dvec = dvec * invDist;
         f3 value = I * (invDist * invDist);
+        value = value * point_falloff(spot_table(P), k, dvec);          // a spot's cone (1 for a point emitter)
         optLen = dist * S.rif_const;
         const float tExit = intersect_shape_b<BND>(P, ps, dvec, 0.0f, MER_INF);
         const bool crosses = tExit >= 0 && tExit < dist;
@@ -570,9 +572,9 @@ __device__ __forceinline__ f3 point_nee(const Params &P, Rng &rng, LaneCounters 
 
 // The radiance a finished curved-ray connection carries from the point emitter to the scattering point ps (to be multiplied by the
 // path throughput): I / |pp - ps|^2 (the straight-line distance of PointEmitter::sampleDirect, which the reference keeps for curved
-// connections) x transmittance along the connecting ray (arc length dist, launched along dir) x solver weight x phase function.
+// connections) x a spot's falloff toward that straight line x transmittance along the connecting ray (arc length dist, launched along dir) x solver weight x phase function.
 template <int RIF, int STEPPER, int SIGMA, int BND = 0>
-__device__ __forceinline__ f3 connection_value(const Params &P, const DPoint &E, Rng &rng, LaneCounters &C, f3 ps, f3 wi, f3 dir, float dist, float w) {
+__device__ __forceinline__ f3 connection_value(const Params &P, const DPoint &E, int k, Rng &rng, LaneCounters &C, f3 ps, f3 wi, f3 dir, float dist, float w) {
     const mer_scene_desc &S = P.sc;
     const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);                 // intensity / selection pdf of the emitter the connection was built to
     const f3 pp(E.pos[0], E.pos[1], E.pos[2]);
@@ -606,7 +608,8 @@ __device__ __forceinline__ f3 connection_value(const Params &P, const DPoint &E,
     if (is_zero(tr)) return f3(0, 0, 0);
     const f3 dv = pp - ps;
     const float invDist = 1.0f / sqrtf(dot(dv, dv));
-    const f3 value = I * (invDist * invDist) * tr * w;
+    // a spot's cone at the straight-line direction of sampleDirect, as the 1 / dist^2 (not at the curved ray's end direction)
+    const f3 value = I * (invDist * invDist) * point_falloff(spot_table(P), k, dv * invDist) * tr * w;
     return value * phase_eval(S.phase, S.g, wi, normalize(dir));
 }
 

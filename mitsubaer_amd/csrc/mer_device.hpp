@@ -700,7 +700,11 @@ __device__ __forceinline__ float maxexp_cdf(const MaxExp &m, float t) {         
 struct DPoint { float pos[3], Ie[3], pdf, cdf; };
 // One area emitter (`rectangle`): objectToWorld, its inverse, the frame normal, 1 / area, radiance, selection pdf, radiance / pdf, CDF bound.
 struct DRect { float o2w[12], w2o[12], n[3], inv_area, L[3], pdf, Le[3], cdf; };
-static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144, "emitter records: 16-byte multiples");
+// The cone of the point-table slot with the same index (emitter `spot`, src/emitters/spot.cpp:66-118), derived in float as SpotEmitter's
+// constructor / configure() do: z row of the inverse of toWorld's linear part, cos(cutoff), cos(beamWidth), cutoff (radians),
+// 1 / (cutoff - beamWidth).  A point emitter's slot holds z = 0 and both cosines -2: its falloff is exactly 1.
+struct DSpot { float z[3], cos_cutoff, cos_beam, cutoff, inv_width, pad; };
+static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144 && sizeof(DSpot) == 32, "emitter records: 16-byte multiples");
 
 // Everything a render / leaf kernel needs, passed by value as the kernel argument.
 struct Params {
@@ -729,6 +733,8 @@ struct Params {
     unsigned long long *counters;       // MER_C_COUNT
     unsigned long long *work_counter;
     int32_t dbg_pixel;
+    int32_t has_spot;                   // 1: the scene has a spot emitter; one DSpot per point-table slot follows the rectangle table (spot_table).
+                                        // It fills what was padding: Params keeps its size and kernel-argument layout up to the emitter tables
     // wavefront path-state slots (struct of arrays, word k of slot i at slots[k*nslots + i])
     uint32_t *slots; uint32_t nslots; int32_t ksteps;
     uint32_t nslots_all;                // nslots path slots + the side-walk slots behind them (4 per path when walks are spawned, else 0): extent of `slots` and of the work lists' item ids
@@ -1004,6 +1010,23 @@ __device__ __forceinline__ int emitter_select(const R *tab, int n, const Rng &rn
     for (int j = 0; j < n - 1; ++j) k += u >= tab[j].cdf ? 1 : 0;
     pdf = tab[k].pdf;
     return k;
+}
+// SpotEmitter::falloffCurve(trafo.inverse()(-d)) (spot.cpp:105-118, 184-199) for d = the unit straight-line direction from the shading
+// point to the emitter: cosTheta is the z component of the inverse-transformed vector, not normalised (a scaled toWorld keeps the
+// reference's quirk).  A constant projection texture is skipped there as here.
+__device__ __forceinline__ float spot_falloff(const DSpot &s, f3 d) {
+    const float cosTheta = s.z[0] * (-d.x) + s.z[1] * (-d.y) + s.z[2] * (-d.z);
+    if (cosTheta <= s.cos_cutoff) return 0.0f;
+    if (cosTheta >= s.cos_beam) return 1.0f;
+    return (s.cutoff - acosf(cosTheta)) * s.inv_width;
+}
+// the cones of the point-table slots (make_params stores them behind the MER_MAX_EMITTERS rectangle records), or NULL without a spot emitter
+__device__ __forceinline__ const DSpot *spot_table(const Params &P) {
+    return P.has_spot ? (const DSpot *) (P.rects + MER_MAX_EMITTERS) : nullptr;
+}
+// the falloff of point-table slot k toward the unit direction d (to the emitter): 1 without a spot in the scene (a wave-uniform branch)
+__device__ __forceinline__ float point_falloff(const DSpot *spots, int k, f3 d) {
+    return spots ? spot_falloff(spots[k], d) : 1.0f;
 }
 // AreaLight::eval (area.cpp:102-107): the radiance a ray travelling along d picks up on the rectangle (one-sided)
 __device__ __forceinline__ f3 rect_le(const DRect &R, f3 d) {

@@ -148,6 +148,20 @@ __global__ void phase_eval_kernel(int kind, float g, const float *wi, const floa
     if (i >= n) return;
     val[i] = phase_eval(kind, g, f3(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]), f3(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]));
 }
+// PointEmitter / SpotEmitter::sampleDirect (point.cpp, spot.cpp:184-199) of point-table slot k at ref[3*i..]: value (intensity I, not divided
+// by the selection pdf), unit direction to the emitter, distance, falloff -- point_falloff is what the render kernels apply
+__global__ void emitter_direct_kernel(const DPoint *points, const DSpot *spots, int k, float Ix, float Iy, float Iz, const float *ref, int64_t n, float *out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DPoint &E = points[k];
+    f3 d(E.pos[0] - ref[3 * i], E.pos[1] - ref[3 * i + 1], E.pos[2] - ref[3 * i + 2]);
+    const float dist = sqrtf(dot(d, d)), invDist = 1.0f / dist;
+    d = d * invDist;
+    const float fall = point_falloff(spots, k, d);
+    const f3 v = f3(Ix, Iy, Iz) * (invDist * invDist) * fall;
+    float *o = out + 8 * i;
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dist; o[7] = fall;
+}
 __global__ void rough_eval_kernel(int type, float alpha, int visible, const float *eta, const float *wi, const float *wo, int64_t n, float *val, float *pdf) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

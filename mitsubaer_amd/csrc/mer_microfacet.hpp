@@ -222,7 +222,8 @@ __device__ __forceinline__ int rough_event(const Params &P, Rng &rng, f3 ro, f3 
     (void) rng.next1D(); (void) rng.next1D();                     // (1)
     Le = f3(0, 0, 0); eLen = 0.0f;
     if (P.n_point) {
-        float pk; const DPoint &E = P.points[emitter_select(P.points, P.n_point, rng, 3, pk)];    // one of the point emitters; E.Ie = I / its pdf
+        float pk; const int k = emitter_select(P.points, P.n_point, rng, 3, pk);
+        const DPoint &E = P.points[k];                            // one of the point emitters; E.Ie = I / its pdf
         f3 dv(E.pos[0] - x.x, E.pos[1] - x.y, E.pos[2] - x.z);
         const float dist = sqrtf(dot(dv, dv));
         dv = dv / dist;
@@ -235,7 +236,7 @@ __device__ __forceinline__ int rough_event(const Params &P, Rng &rng, f3 ro, f3 
             float pdfE;
             const float f = rough_dielectric_eval(d, etaB, wi, wl, pdfE);
             const f3 I(E.Ie[0], E.Ie[1], E.Ie[2]);
-            Le = T * I * (f / (dist * dist));
+            Le = T * I * (f / (dist * dist)) * point_falloff(spot_table(P), k, dv);     // a spot's cone (1 for a point emitter)
             eLen = dist;
         }
     }

@@ -1126,7 +1126,7 @@ __global__ void MER_CONNECT_BOUNDS connect_stage_kernel(const Params P, uint32_t
         if (S.phase == CP_OK) {
             // the connecting ray is known: transmittance along it, emitter value, phase function -- the luminaire sample of this vertex
             const f3 T(SLOTF(CO_TX), SLOTF(CO_TY), SLOTF(CO_TZ)), wi(SLOTF(CO_WIX), SLOTF(CO_WIY), SLOTF(CO_WIZ));
-            const f3 c0 = T * connection_value<RIF, STEPPER, SIGMA, BND>(P, E, rng, C, ps, wi, S.dir, S.dist, S.weight);
+            const f3 c0 = T * connection_value<RIF, STEPPER, SIGMA, BND>(P, E, S.em, rng, C, ps, wi, S.dir, S.dist, S.weight);
             const float plen = SLOTF(CO_PLEN) + edge_length(P, S.optDist);
             film_contribute(P, SLOTF(CO_PXF), SLOTF(CO_PYF), c0, plen);
             const f3 c = mod_weight<EXTRA>(P, c0, plen);

@@ -463,7 +463,26 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             o->kind = Emitter::EArea;
             if (props.hasProperty("toWorld")) Log_EError("Found a 'toWorld' transformation -- this is not allowed -- the area light inherits this transformation from its parent shape");
             o->radiance = props.getSpectrum("radiance", Spectrum{{1, 1, 1}});
-        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, point, area)");
+        } else if (type == "spot") {                                     // src/emitters/spot.cpp:68-77
+            o->kind = Emitter::ESpot;
+            props.getTransform("toWorld", o->toWorld);
+            o->radiance = props.getSpectrum("intensity", Spectrum{{1, 1, 1}});
+            o->cutoffAngle = props.getFloat("cutoffAngle", 20);
+            o->beamWidth = props.getFloat("beamWidth", o->cutoffAngle * 3.0f / 4.0f);
+            // a spectrum-valued `texture` becomes a ConstantSpectrumTexture, which falloffCurve skips (:110): read and ignored
+            if (props.hasProperty("texture")) (void) props.getSpectrum("texture");
+            if (!std::isfinite(o->cutoffAngle) || !std::isfinite(o->beamWidth) || o->cutoffAngle < 0 || o->beamWidth < 0)
+                Log_EError("spot emitter: cutoffAngle and beamWidth must be finite and non-negative");
+            if (o->cutoffAngle > 180) Log_EError("spot emitter: cutoffAngle must not exceed 180 degrees");
+            if (o->beamWidth > o->cutoffAngle) Log_EError("Assertion 'm_cutoffAngle >= m_beamWidth' failed (spot emitter: beamWidth > cutoffAngle)");   // :74
+            for (int i = 0; i < 12; i++) if (!std::isfinite(o->toWorld[i])) Log_EError("spot emitter: 'toWorld' must be finite");
+            const float *M = o->toWorld;
+            const double det = (double) M[0] * ((double) M[5] * M[10] - (double) M[6] * M[9]) - (double) M[1] * ((double) M[4] * M[10] - (double) M[6] * M[8]) +
+                               (double) M[2] * ((double) M[4] * M[9] - (double) M[5] * M[8]);
+            if (!(std::fabs(det) > 0)) Log_EError("spot emitter: 'toWorld' is singular");
+            for (int i = 0; i < 3; i++) if (!(o->radiance.c[i] >= 0)) Log_EError("spot emitter: intensity must be non-negative");
+            o->position = Vec3{M[3], M[7], M[11]};
+        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, point, spot, area)");
         o->samplingWeight = props.getFloat("samplingWeight", 1.0f);     // src/librender/emitter.cpp:103
         if (!(o->samplingWeight > 0) || !std::isfinite(o->samplingWeight)) Log_EError("emitter \"" + type + "\": samplingWeight must be positive");
         out = o;
@@ -642,6 +661,7 @@ struct Loader {
                 v.x = g("x"); v.y = g("y"); v.z = g("z");
                 props.setPoint(name, v);
             } else if (c.tag == "transform") { float m[16]; transform(c, m); props.setTransform(name, m); }
+            else if (c.tag == "texture") Log_EError("<texture> plugins are not supported on the GPU path (a spot emitter's projection texture is not built; a spectrum-valued 'texture' is accepted and ignored)");
             else Log_EError("Unsupported property tag <" + c.tag + ">");
         }
         ObjRef obj = createObject(n.tag, props, baseDir);
@@ -768,7 +788,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     d.tr_estimator = m.trEstimator; d.method = m.method; d.het_stepsize = m.hetStepSize;
     // point emitters and the area emitters of `rectangle` shapes, in scene order (rectangles first).  At most one of each kind: the single-emitter
     // fields of the scene desc; more: the emitter list (scene.emitterList), each entry with its samplingWeight
-    int nconst = 0, npoint = 0, narea = 0;
+    int nconst = 0, npoint = 0, narea = 0, nspot = 0;
     std::vector<mer_emitter> &list = scene.emitterList;
     list.clear();
     for (int i = 0; i < 3; i++) { d.env_radiance[i] = 0; d.point_intensity[i] = 0; d.point_position[i] = 0; d.emission[i] = m.emission.c[i]; d.area_radiance[i] = 0; }
@@ -789,13 +809,19 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
             q.position[0] = e->position.x; q.position[1] = e->position.y; q.position[2] = e->position.z;
             for (int i = 0; i < 3; i++) q.intensity[i] = e->radiance.c[i];
             list.push_back(q); ++npoint;
+        } else if (e->kind == Emitter::ESpot) {                          // always a list entry (the single-emitter fields have no cone)
+            mer_emitter q{}; q.type = MER_EMITTER_SPOT; q.sampling_weight = e->samplingWeight;
+            for (int i = 0; i < 12; i++) q.to_world[i] = e->toWorld[i];
+            for (int i = 0; i < 3; i++) { q.intensity[i] = e->radiance.c[i]; q.position[i] = e->toWorld[4 * i + 3]; }
+            q.cutoff_angle_deg = e->cutoffAngle; q.beam_width_deg = e->beamWidth;
+            list.push_back(q); ++nspot;
         } else {
             if (++nconst > 1) Log_EError("Only one constant emitter is supported on the GPU path");
             for (int i = 0; i < 3; i++) d.env_radiance[i] = e->radiance.c[i];
         }
     }
-    if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point and area emitters are supported on the GPU path");
-    if (npoint <= 1 && narea <= 1) {
+    if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point, spot and area emitters are supported on the GPU path");
+    if (npoint <= 1 && narea <= 1 && nspot == 0) {
         for (const mer_emitter &e : list) {
             if (e.type == MER_EMITTER_AREA) { for (int i = 0; i < 12; i++) d.area_to_world[i] = e.to_world[i]; for (int i = 0; i < 3; i++) d.area_radiance[i] = e.radiance[i]; }
             else for (int i = 0; i < 3; i++) { d.point_position[i] = e.position[i]; d.point_intensity[i] = e.intensity[i]; }
@@ -807,14 +833,15 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
         if (npoint == 1 && point_inside_shape(d, m, d.point_position))
             Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
         for (const mer_emitter &e : list)
-            if (point_inside_shape(d, m, e.position))
-                Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
+            if (e.type != MER_EMITTER_AREA && point_inside_shape(d, m, e.position))
+                Log_EError(std::string("hroughdielectric: the ") + (e.type == MER_EMITTER_SPOT ? "spot" : "point") +
+                           " emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
     if (narea && !list.empty()) {     // the checks mer_render applies to the list (the area emitter's own checks run there too)
         if (d.rif_mode != MER_RIF_CONST) Log_EError("the area emitter is built for straight rays (rif_mode = CONST)");
         for (const mer_emitter &e : list)
-            if (e.type == MER_EMITTER_POINT && d.boundary != MER_BOUNDARY_SDF && !point_inside_shape(d, m, e.position))
-                Log_EError("a point emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
+            if ((e.type == MER_EMITTER_POINT || e.type == MER_EMITTER_SPOT) && d.boundary != MER_BOUNDARY_SDF && !point_inside_shape(d, m, e.position))
+                Log_EError("a point or spot emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
     }
 }
 

@@ -183,9 +183,11 @@ public:
 class Emitter : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "Emitter"; }
-    enum Kind { EConstant, EPoint, EArea } kind = EConstant;
-    Spectrum radiance{};                        // constant / area: radiance ; point: intensity
+    enum Kind { EConstant, EPoint, EArea, ESpot } kind = EConstant;
+    Spectrum radiance{};                        // constant / area: radiance ; point / spot: intensity
     Vec3 position{0, 0, 0};                     // point (src/emitters/point.cpp:60-68)
+    float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // spot: its frame (src/emitters/spot.cpp:124-131)
+    float cutoffAngle = 20, beamWidth = 15;     // spot: degrees (spot.cpp:68-73)
     float samplingWeight = 1.0f;                // `samplingWeight` (src/librender/emitter.cpp:103): selection weight among the emitters of its kind
 };
 

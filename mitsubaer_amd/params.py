@@ -134,6 +134,7 @@ class SceneParams:
 
 EMITTER_POINT = 1
 EMITTER_AREA = 2
+EMITTER_SPOT = 3
 MAX_EMITTERS = 32
 
 
@@ -146,6 +147,45 @@ def point_emitter(position, intensity, sampling_weight=1.0):
 def area_emitter(to_world, radiance, sampling_weight=1.0):
     """an entry of SceneParams.emitters: emitter `area` on a `rectangle`, the image of [-1,1]^2 x {0} under to_world (3x4 or 4x4, no shear)"""
     return {"type": EMITTER_AREA, "to_world": to_world, "radiance": [float(v) for v in radiance], "sampling_weight": float(sampling_weight)}
+
+
+def spot_error(to_world, cutoff_deg, beam_deg):
+    """why mer_render refuses a spot emitter with these parameters (None: accepted)"""
+    import numpy as np
+    c, b = float(cutoff_deg), float(beam_deg)
+    if not (np.isfinite(c) and np.isfinite(b) and c >= 0 and b >= 0):
+        return "spot emitter: cutoffAngle and beamWidth must be finite and non-negative"
+    if c > 180:
+        return "spot emitter: cutoffAngle must not exceed 180 degrees"
+    if b > c:
+        return "spot emitter: beamWidth must not exceed cutoffAngle"
+    m = np.asarray(to_world if to_world is not None else np.eye(4), np.float64)
+    if m.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(m)):
+        return "spot emitter: 'toWorld' must be a finite 3x4 or 4x4 transform"
+    if not abs(np.linalg.det(m[:3, :3].astype(np.float32).astype(np.float64))) > 0:
+        return "spot emitter: 'toWorld' is singular"
+    return None
+
+
+def spot_emitter(to_world, intensity, cutoff_deg=20.0, beam_deg=None, weight=1.0):
+    """an entry of SceneParams.emitters: emitter `spot` (src/emitters/spot.cpp:66-118), a point emitter at to_world's origin whose cone
+    axis is to_world's z axis; intensity is its peak intensity, cutoff_deg / beam_deg its `cutoffAngle` / `beamWidth` in degrees (beam
+    defaults to 3/4 of the cutoff, in float as the reference computes it).  ValueError for what mer_render refuses."""
+    import numpy as np
+    if beam_deg is None:
+        beam_deg = float(np.float32(cutoff_deg) * np.float32(3.0) / np.float32(4.0))
+    err = spot_error(to_world, cutoff_deg, beam_deg)
+    if err:
+        raise ValueError(err)
+    return {"type": EMITTER_SPOT, "to_world": to_world, "intensity": [float(v) for v in intensity],
+            "cutoff_deg": float(cutoff_deg), "beam_deg": float(beam_deg), "sampling_weight": float(weight)}
+
+
+def spot_position(e):
+    """the position of a spot entry: the translation column of its to_world"""
+    import numpy as np
+    m = np.asarray(e.get("to_world") if e.get("to_world") is not None else np.eye(4), np.float64)
+    return [float(np.float32(v)) for v in m[:3, 3]]
 
 
 def sdf_max_error(p):

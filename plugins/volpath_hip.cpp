@@ -242,8 +242,8 @@ public:
         /* ---- medium, phase function, volumes */
         fillMedium(ctx, shape->getInteriorMedium(), d, volumes);
 
-        /* ---- emitters: constant environment, point emitters and area emitters on rectangles.  One of each kind at most: the single-emitter
-           fields of mer_scene_desc; more: the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
+        /* ---- emitters: constant environment, point and spot emitters and area emitters on rectangles.  One point and one area emitter at
+           most and no spot: the single-emitter fields of mer_scene_desc; otherwise the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
         if (const Emitter *env = scene->getEnvironmentEmitter()) {
             if (env->getClass()->getName() != "ConstantBackgroundEmitter") Log(EError, "volpath_hip: the environment emitter must be 'constant'");
             const Spectrum L = env->evalEnvironment(RayDifferential(Point(0.0f), Vector(0, 0, 1), 0));
@@ -252,7 +252,7 @@ public:
         }
         const ref_vector<Emitter> &emitters = scene->getEmitters();
         std::vector<mer_emitter> list;
-        int npoint = 0, narea = 0;
+        int npoint = 0, narea = 0, nspot = 0;
         for (size_t i = 0; i < emitters.size(); ++i) {
             const Emitter *e = emitters[i].get();
             if (e->isEnvironmentEmitter()) continue;
@@ -277,7 +277,25 @@ public:
                 list.push_back(m); ++narea;
                 continue;
             }
-            if (e->getClass()->getName() != "PointEmitter") Log(EError, "volpath_hip: emitters must be 'constant', 'point' or 'area' (on a rectangle)");
+            if (e->getClass()->getName() == "SpotEmitter") {
+                /* `spot` (src/emitters/spot.cpp:66-200): its cone parameters are private, so they are read from the properties it was created
+                   from (ConfigurableObject::getProperties, cobject.h:77) with the constructor's defaults; the frame from its world transform.
+                   Always a list entry. */
+                const Properties &props = e->getProperties();
+                const Float cutoff = props.getFloat("cutoffAngle", 20), beam = props.getFloat("beamWidth", cutoff * 3.0f / 4.0f);
+                const Spectrum I = props.getSpectrum("intensity", Spectrum(1.0f));
+                Float r, g, b; I.toLinearRGB(r, g, b);
+                const Matrix4x4 &M = e->getWorldTransform()->eval(0).getMatrix();
+                mer_emitter m; memset(&m, 0, sizeof(m));
+                m.type = MER_EMITTER_SPOT; m.sampling_weight = (float) e->getSamplingWeight();
+                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) m.to_world[4 * r + k] = (float) M.m[r][k];
+                for (int k = 0; k < 3; ++k) m.position[k] = m.to_world[4 * k + 3];
+                m.intensity[0] = r; m.intensity[1] = g; m.intensity[2] = b;
+                m.cutoff_angle_deg = (float) cutoff; m.beam_width_deg = (float) beam;
+                list.push_back(m); ++nspot;
+                continue;
+            }
+            if (e->getClass()->getName() != "PointEmitter") Log(EError, "volpath_hip: emitters must be 'constant', 'point', 'spot' or 'area' (on a rectangle)");
             PositionSamplingRecord pRec(0.0f);
             const Spectrum I = e->samplePosition(pRec, Point2(0.5f)) / (4 * M_PI);       /* src/emitters/point.cpp:82-90 */
             Float r, g, b; I.toLinearRGB(r, g, b);
@@ -287,7 +305,7 @@ public:
             m.position[0] = pRec.p.x; m.position[1] = pRec.p.y; m.position[2] = pRec.p.z;
             list.push_back(m); ++npoint;
         }
-        if (npoint <= 1 && narea <= 1) {
+        if (npoint <= 1 && narea <= 1 && nspot == 0) {
             for (size_t i = 0; i < list.size(); ++i) {
                 const mer_emitter &m = list[i];
                 if (m.type == MER_EMITTER_AREA) {
@@ -297,7 +315,7 @@ public:
                     for (int k = 0; k < 3; ++k) { d.point_intensity[k] = m.intensity[k]; d.point_position[k] = m.position[k]; }
             }
         } else {
-            if (list.size() > MER_MAX_EMITTERS) Log(EError, "volpath_hip: at most %i point and area emitters", (int) MER_MAX_EMITTERS);
+            if (list.size() > MER_MAX_EMITTERS) Log(EError, "volpath_hip: at most %i point, spot and area emitters", (int) MER_MAX_EMITTERS);
             d.n_emitters = (int32_t) list.size(); d.emitters = &list[0];       /* `list` outlives the mer_multi_render below */
         }
 
