@@ -68,9 +68,15 @@ typedef struct {
    cosTheta = z row of the inverse of to_world's linear part . (-d) -- not normalised, as the reference has it -- where d is the unit
    STRAIGHT-LINE direction from the shading point to the emitter, also for curved rays (the reference's volpath takes the emitter value from
    sampleDirect before the medium's curved eval, scene.cpp:854-874; heterogeneousrefractive.cpp:571-640).  The projection `texture` is not
-   built. */
+   built.
+   MER_EMITTER_ENVMAP: emitter `envmap` (src/emitters/envmap.cpp:100-645), an importance-sampled lat-long environment map -- list entries
+   only, at most one ("The scene may only contain one environment emitter", src/librender/scene.cpp:512), and not together with a non-zero
+   env_radiance.  envmap = a handle of mer_envmap_upload, env_scale = its `scale`, env_reserved = 0; to_world = its `toWorld` (row-major 3x4,
+   the linear part a rotation within 1e-5, the translation ignored).  It takes the constant environment's place at every site: camera-ray
+   and path escapes, the luminaire sample at each collision (its selection probability is 1: sampling_weight must be > 0 but does not
+   scale it) and the phase-sampled look-up, with pdfDirect as the MIS partner.  Curved rays: DESIGN.md section 1. */
 #define MER_MAX_EMITTERS 32
-enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3 };
+enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3, MER_EMITTER_ENVMAP = 4 };
 typedef struct {
     int32_t type;
     float   position[3], intensity[3];
@@ -78,6 +84,7 @@ typedef struct {
     union {                                          /* a spot's angles overlay the radiance it does not have: the record keeps its size */
         float radiance[3];                           /* MER_EMITTER_AREA */
         struct { float cutoff_angle_deg, beam_width_deg, spot_reserved; };      /* MER_EMITTER_SPOT (spot_reserved: 0) */
+        struct { mer_volume envmap; float env_scale, env_reserved; };           /* MER_EMITTER_ENVMAP (env_reserved: 0) */
     };
     float   sampling_weight;
 } mer_emitter;
@@ -260,6 +267,12 @@ int  mer_volume_upload_dev(mer_context *ctx, const mer_grid_desc *desc, const vo
 int  mer_volume_build_spline(mer_context *ctx, mer_volume v);
 int  mer_volume_download_spline(mer_context *ctx, mer_volume v, float *coeff_host);
 int  mer_volume_destroy(mer_context *ctx, mer_volume v);
+/* emitter `envmap` (src/emitters/envmap.cpp:100-190, 260-320): rgb_host = float32 [height][width][3], the lat-long image as loaded (level 0,
+   no resampling).  The texels are rounded to IEEE half (the reference's TMIPMap<Spectrum, SpectrumHalf>), and the sampling tables are
+   built from the rounded texels on the host in the reference's order and precision: a conditional luminance CDF per row, the row weights
+   sin((y + 0.5) pi / height), the marginal CDF and the normalisation.  Fails as configure() does on an all-black or non-finite map.  The
+   handle is freed by mer_volume_destroy (it is no grid: no other volume call takes it). */
+int  mer_envmap_upload(mer_context *ctx, int32_t width, int32_t height, const float *rgb_host, mer_volume *out);
 
 /* ---- film (ImageBlock, include/mitsuba/render/imageblock.h:124-205): float[height][width][channels], channels = 5
         (R,G,B,alpha,weight) in steady state; mer_film_channels() for a scene with a transient decomposition; the *_n
@@ -319,6 +332,14 @@ int  mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1,
    spot) at n reference points ref[3*i..]: out stride 8: value RGB (intensity x falloff / dist^2, NOT divided by the selection pdf), the unit
    direction to the emitter [3], the distance, the falloff (1 for a point).  The render kernels' own device function. */
 int  mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, int64_t n, float *out);
+/* EnvironmentMap::evalEnvironment (level 0, bilinear) and pdfDirect (envmap.cpp:385-415, 531-645) of the scene's envmap entry for n world
+   directions dirs[3*i..] (need not be unit): out_rgb[3*i..] = value x scale, out_pdf[i] = the solid-angle density of the luminaire
+   sample.  The render kernels' own device functions. */
+int  mer_envmap_eval(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_rgb, float *out_pdf);
+/* EnvironmentMap::sampleDirect (envmap.cpp:516-610) for n samples u2[2*i..]: out_dir[3*i..] = the world direction, out_value_over_pdf[3*i..]
+   = value x scale / pdf (0 when pdf is 0), out_pdf[i] = pdf.  The render kernels' own device function. */
+int  mer_envmap_sample(mer_context *ctx, const mer_scene_desc *scene, const float *u2, int64_t n, float *out_dir, float *out_value_over_pdf,
+                       float *out_pdf);
 /* PhaseFunction::sample / eval (src/phase/hg.cpp:74-110, src/phase/isotropic.cpp:62-78) */
 int  mer_phase_sample(mer_context *ctx, int32_t phase, float g, const float *wi, const float *u2, int64_t n, float *wo, float *pdf);
 int  mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, const float *wo, int64_t n, float *val);
@@ -367,6 +388,8 @@ int  mer_multi_set_option(mer_multi *m, const char *name, int64_t value);
 int  mer_multi_volume_upload(mer_multi *m, const mer_grid_desc *desc, const void *host_data, int32_t layout, mer_volume *out);
 int  mer_multi_volume_build_spline(mer_multi *m, mer_volume v);
 int  mer_multi_volume_destroy(mer_multi *m, mer_volume v);
+/* mer_envmap_upload on every context; ONE handle, valid in all of them (mer_multi_volume_destroy frees it) */
+int  mer_multi_envmap_upload(mer_multi *m, int32_t width, int32_t height, const float *rgb_host, mer_volume *out);
 /* renders sample indices spp_begin .. spp_begin + spp_count - 1 of every pixel, sharded over the contexts, and returns the reduced film
    float[height][width][mer_film_channels] in film_host.  rccl: 1 = use RCCL when the devices allow it and the library initialises (default choice; peer copy + add otherwise --
    mer_multi_last_stats reports which), 0 = always peer copy + add, 2 = RCCL even for a single context (a one-rank communicator: exercises the library binding on one GPU). */

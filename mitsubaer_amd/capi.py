@@ -22,7 +22,7 @@ SYMBOLS = [
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
-    "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
+    "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_envmap_upload", "mer_envmap_eval", "mer_envmap_sample", "mer_multi_envmap_upload", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
     "mer_rough_dielectric_sample", "mer_camera_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
@@ -41,13 +41,17 @@ class _SpotAngles(C.Structure):
     _fields_ = [("cutoff_angle_deg", C.c_float), ("beam_width_deg", C.c_float), ("spot_reserved", C.c_float)]
 
 
+class _EnvmapRef(C.Structure):
+    _fields_ = [("envmap", C.c_int32), ("env_scale", C.c_float), ("env_reserved", C.c_float)]
+
+
 class _RadianceOrAngles(C.Union):
-    _anonymous_ = ("_angles",)
-    _fields_ = [("radiance", C.c_float * 3), ("_angles", _SpotAngles)]
+    _anonymous_ = ("_angles", "_env")
+    _fields_ = [("radiance", C.c_float * 3), ("_angles", _SpotAngles), ("_env", _EnvmapRef)]
 
 
 class EmitterDesc(C.Structure):
-    """mer_emitter: one entry of SceneDesc.emitters (a spot's cutoff_angle_deg / beam_width_deg overlay radiance)"""
+    """mer_emitter: one entry of SceneDesc.emitters (a spot's cutoff_angle_deg / beam_width_deg and an envmap's envmap / env_scale overlay radiance)"""
     _anonymous_ = ("_u",)
     _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("intensity", C.c_float * 3),
                 ("to_world", C.c_float * 12), ("_u", _RadianceOrAngles), ("sampling_weight", C.c_float)]
@@ -181,7 +185,7 @@ def validate_emitters(p):
         raise MerError("emitter list: at most %d entries (MER_MAX_EMITTERS)" % P.MAX_EMITTERS)
     if any(v != 0 for v in p.point_intensity) or any(v != 0 for v in p.area_radiance):
         raise MerError("emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0")
-    has_rect, outside_point = False, False
+    has_rect, outside_point, n_env = False, False, 0
     for j, e in enumerate(ems):
         at = "emitter list, entry %d: " % j
         w = float(e.get("sampling_weight", 1.0))
@@ -214,10 +218,28 @@ def validate_emitters(p):
             if _rect_meets_shape(p, np.array(_rows3x4(e.get("to_world")), np.float64).reshape(3, 4)):
                 raise MerError(at + "the area emitter's rectangle must lie outside the medium shape")
             has_rect = True
+        elif e["type"] == P.EMITTER_ENVMAP:
+            if n_env or any(v != 0 for v in p.env_radiance):
+                raise MerError(at + "The scene may only contain one environment emitter (an envmap entry excludes a second one and a non-zero env_radiance)")
+            n_env += 1
+            err = P.envmap_error(e["image"], e.get("to_world"), e.get("scale", 1.0), w) if e.get("image") is not None else None
+            if err:
+                raise MerError(at + err)
         else:
             raise MerError(at + "unknown emitter type")
     if has_rect and outside_point:
         raise MerError("emitter list: a point or spot emitter outside the medium shape cannot be combined with an area emitter")
+
+
+def _upload_scene_envmap(ctx, p, vols):
+    """upload_scene: the image of the emitter list's envmap entry (validated first), appended to vols; None without one"""
+    ems = [e for e in (getattr(p, "emitters", None) or []) if e["type"] == P.EMITTER_ENVMAP and e.get("image") is not None]
+    if not ems:
+        return None
+    validate_emitters(p)
+    env = ctx.upload_envmap(ems[0]["image"])
+    vols.append(env)
+    return env
 
 
 class Shard(C.Structure):
@@ -391,8 +413,9 @@ class Context:
         return v
 
     # ---- scene ---------------------------------------------------------------------------------
-    def scene_desc(self, p, density=None, albedo_grid=None, rif=None, sdf=None):
-        """p: params.SceneParams; volumes as Volume objects."""
+    def scene_desc(self, p, density=None, albedo_grid=None, rif=None, sdf=None, envmap=None):
+        """p: params.SceneParams; volumes as Volume objects; envmap: the Volume of upload_envmap for the list's envmap entry (or the entry's
+        "handle")."""
         s = SceneDesc()
         s.width, s.height = p.width, p.height
         s.fov_x_deg, s.near_clip, s.far_clip = p.fov_x_deg, p.near_clip, p.far_clip
@@ -440,6 +463,9 @@ class Context:
                 elif e.type == P.EMITTER_SPOT:
                     e.to_world[:] = _rows3x4(d.get("to_world")); e.intensity[:] = [float(v) for v in d["intensity"]]
                     e.cutoff_angle_deg = float(d["cutoff_deg"]); e.beam_width_deg = float(d["beam_deg"])
+                elif e.type == P.EMITTER_ENVMAP:
+                    e.to_world[:] = _rows3x4(d.get("to_world")); e.env_scale = float(d.get("scale", 1.0)); e.env_reserved = 0.0
+                    e.envmap = envmap.handle if envmap is not None else int(d.get("handle", 0))
                 else:
                     e.to_world[:] = _rows3x4(d.get("to_world")); e.radiance[:] = [float(v) for v in d["radiance"]]
             s.n_emitters = len(ems)
@@ -473,7 +499,17 @@ class Context:
         if p.boundary == P.BOUNDARY_SDF and p.sdf is not None:
             sdf = self.upload_volume(p.sdf, p.sdf_aabb[0], p.sdf_aabb[1], LAYOUT_DENSE, p.sdf_to_world)
             vols.append(sdf)
-        return self.scene_desc(p, dens, alb, rif, sdf), vols
+        env = _upload_scene_envmap(self, p, vols)
+        return self.scene_desc(p, dens, alb, rif, sdf, env), vols
+
+    def upload_envmap(self, image):
+        """mer_envmap_upload: the lat-long image float [height][width][3] -> a Volume handle (freed by destroy / mer_volume_destroy)"""
+        a = np.ascontiguousarray(np.asarray(image, np.float32))
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise MerError("envmap emitter: the image must be float [height][width][3]")
+        h = C.c_int32()
+        self._check(self.lib.mer_envmap_upload(self.h, C.c_int32(a.shape[1]), C.c_int32(a.shape[0]), _fp(a), C.byref(h)))
+        return Volume(self, h.value, None, None)
 
     # ---- film + render -------------------------------------------------------------------------
     def film_channels(self, scene):
@@ -579,6 +615,20 @@ class Context:
         out = np.zeros((n, 12), np.float32)
         self._check(self.lib.mer_connect(self.h, C.byref(scene), _fp(p1), _fp(p2), C.c_int64(n), C.c_uint64(seed), _fp(out)))
         return out
+
+    def envmap_eval(self, scene, dirs):
+        """mer_envmap_eval: the scene's envmap at world directions dirs (n x 3) -> (value x scale (n, 3), pdfDirect (n,))"""
+        d = _f32(dirs).reshape(-1, 3); n = d.shape[0]
+        val = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
+        self._check(self.lib.mer_envmap_eval(self.h, C.byref(scene), _fp(d), C.c_int64(n), _fp(val), _fp(pdf)))
+        return val, pdf
+
+    def envmap_sample(self, scene, u2):
+        """mer_envmap_sample: sampleDirect for samples u2 (n x 2) -> (direction (n, 3), value / pdf (n, 3), pdf (n,))"""
+        u = _f32(u2).reshape(-1, 2); n = u.shape[0]
+        d = np.zeros((n, 3), np.float32); v = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
+        self._check(self.lib.mer_envmap_sample(self.h, C.byref(scene), _fp(u), C.c_int64(n), _fp(d), _fp(v), _fp(pdf)))
+        return d, v, pdf
 
     def emitter_direct(self, scene, k, ref):
         """mer_emitter_direct: sampleDirect of emitter-list entry k (a point or a spot) at the reference points ref (n x 3); (n, 8) float32:
@@ -697,7 +747,17 @@ class MultiContext:
             vols.append(rif)
         if p.boundary == P.BOUNDARY_SDF and p.sdf is not None:
             sdf = self.upload_volume(p.sdf, p.sdf_aabb[0], p.sdf_aabb[1], LAYOUT_DENSE, p.sdf_to_world); vols.append(sdf)
-        return self.contexts[0].scene_desc(p, dens, alb, rif, sdf), vols
+        env = _upload_scene_envmap(self, p, vols)
+        return self.contexts[0].scene_desc(p, dens, alb, rif, sdf, env), vols
+
+    def upload_envmap(self, image):
+        """mer_multi_envmap_upload: one handle, valid in every context"""
+        a = np.ascontiguousarray(np.asarray(image, np.float32))
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise MerError("envmap emitter: the image must be float [height][width][3]")
+        h = C.c_int32()
+        self._check(self.lib.mer_multi_envmap_upload(self.h, C.c_int32(a.shape[1]), C.c_int32(a.shape[0]), _fp(a), C.byref(h)))
+        return Volume(self, h.value, None, None)
 
     def destroy_volume(self, vol):
         if vol.handle:

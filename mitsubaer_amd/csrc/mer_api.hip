@@ -209,9 +209,43 @@ static const char *spot_derive(const mer_emitter &e, DSpot &s) {
     return nullptr;
 }
 
-// mer_scene_desc.emitters -> the point / area tables (and the spots' cones, one per point-table slot): each entry checked as the single emitter of its kind is, the rectangles by the exact
+// emitter `envmap`: its record from the uploaded map and the entry's toWorld (a rotation within 1e-5; the translation is ignored -- a direction
+// does not see it) and scale.  Returns an error message or nullptr.
+static const char *envmap_derive(mer_context *ctx, const mer_emitter &e, DEnvMap &E) {
+    auto it = ctx->envmaps.find(e.envmap);
+    if (it == ctx->envmaps.end()) return "envmap emitter: unknown or destroyed envmap handle (mer_envmap_upload)";
+    if (!std::isfinite(e.env_scale) || !(e.env_scale >= 0)) return "envmap emitter: 'scale' must be finite and non-negative";
+    double M[3][3];
+    for (int i = 0; i < 12; i++) { if (!std::isfinite(e.to_world[i])) return "envmap emitter: 'toWorld' must be finite"; if (i % 4 != 3) M[i / 4][i % 4] = e.to_world[i]; }
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const double d = M[r][0] * M[c][0] + M[r][1] * M[c][1] + M[r][2] * M[c][2] - (r == c ? 1.0 : 0.0);
+            if (std::fabs(d) > 1e-5) return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)";
+        }
+    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
+    if (!(det > 0)) return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)";
+    const EnvMap &m = it->second;
+    const unsigned char *b = (const unsigned char *) m.dev;
+    E = DEnvMap{};
+    E.texels = (const uint2 *) b; E.cdf_cols = (const float *) (b + m.off_cols); E.cdf_rows = (const float *) (b + m.off_rows);
+    E.row_weights = (const float *) (b + m.off_weights);
+    E.chk = ctx->chk;
+    E.w = m.w; E.h = m.h; E.norm = m.norm; E.scale = e.env_scale;
+    // trafo.inverse() of a rotation: its inverse matrix (in double, rounded), the rotation itself for the sampled direction (envmap.cpp:382, 537)
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;     // inverse = adjugate / det (cofactor of (c, r))
+            E.w2l[3 * r + c] = (float) ((M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]) / det);
+            E.l2w[3 * r + c] = (float) M[r][c];
+        }
+    E.pix[0] = (float) (2 * M_PI / m.w); E.pix[1] = (float) (M_PI / m.h);           // m_pixelSize (:312)
+    return nullptr;
+}
+
+// mer_scene_desc.emitters -> the point / area tables (and the spots' cones, one per point-table slot; the envmap's record): each entry checked as the single emitter of its kind is, the rectangles by the exact
 // outside test, then every kind's selection pdf = sampling_weight / sum and its CDF
-static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects, std::vector<DSpot> &spots) {
+static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects, std::vector<DSpot> &spots,
+                              std::vector<DEnvMap> &envs) {
     if (sc->n_emitters < 0 || sc->n_emitters > MER_MAX_EMITTERS) return fail(ctx, "emitter list: at most " + std::to_string(MER_MAX_EMITTERS) + " entries (MER_MAX_EMITTERS)");
     if (!sc->emitters) return fail(ctx, "emitter list: n_emitters > 0 but no entries");
     if (!points.empty() || !rects.empty()) return fail(ctx, "emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0");
@@ -248,6 +282,12 @@ static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::v
             if (rect_meets_shape(sc, M)) return fail(ctx, at + "the area emitter's rectangle must lie outside the medium shape");
             for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = e.radiance[i];
             rects.push_back(R); wr.push_back(e.sampling_weight);
+        } else if (e.type == MER_EMITTER_ENVMAP) {    // the environment: its own kind, one at most, sampled at every collision (selection probability 1)
+            if (!envs.empty() || sc->env_radiance[0] != 0 || sc->env_radiance[1] != 0 || sc->env_radiance[2] != 0)
+                return fail(ctx, at + "The scene may only contain one environment emitter (an envmap entry excludes a second one and a non-zero env_radiance)");
+            DEnvMap E;
+            if (const char *err = envmap_derive(ctx, e, E)) return fail(ctx, at + err);
+            envs.push_back(E);
         } else return fail(ctx, at + "unknown emitter type");
     }
     if (!rects.empty())
@@ -419,7 +459,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         // (a signed-distance shape: tested below, where its grid is known)
         if (point && point_in_shape(sc, sc->point_position)) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
-    std::vector<DPoint> points; std::vector<DRect> rects; std::vector<DSpot> spots;
+    std::vector<DPoint> points; std::vector<DRect> rects; std::vector<DSpot> spots; std::vector<DEnvMap> envs;
     const bool legacy_area = sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0;
     const bool legacy_point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
     if (legacy_area) {
@@ -446,7 +486,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         E.pdf = E.cdf = 1.0f;
         points.push_back(E);
     }
-    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects, spots)) return 1;
+    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects, spots, envs)) return 1;
     if (film_frames(ctx, sc, P.frames)) return 1;
     P.film_ch = P.frames * 3 + 2;
     P.mod_phase = (float) (sc->mod_phase_deg * M_PI / 180);                                                   // pathlengthsampler.cpp:15
@@ -491,11 +531,13 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
     ctx->point_outside = false;
     for (const DPoint &E : points) if (sc->boundary != MER_BOUNDARY_SDF && !point_in_shape(sc, E.pos)) ctx->point_outside = true;
     {   // the tables go to device memory when they change; no kernel of this context is in flight here (renders and leaf calls return synchronised)
-        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, off_spot = off + sizeof(DRect) * MER_MAX_EMITTERS, bytes = off_spot + sizeof(DSpot) * MER_MAX_EMITTERS;
+        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, off_spot = off + sizeof(DRect) * MER_MAX_EMITTERS, off_env = off_spot + sizeof(DSpot) * MER_MAX_EMITTERS,
+                     bytes = off_env + sizeof(DEnvMap);
         std::vector<unsigned char> h(bytes, 0);
         if (!points.empty()) std::memcpy(h.data(), points.data(), sizeof(DPoint) * points.size());
         if (!rects.empty()) std::memcpy(h.data() + off, rects.data(), sizeof(DRect) * rects.size());
         if (!spots.empty()) std::memcpy(h.data() + off_spot, spots.data(), sizeof(DSpot) * spots.size());
+        if (!envs.empty()) std::memcpy(h.data() + off_env, envs.data(), sizeof(DEnvMap));
         if (!ctx->etab) HIP_CHECK(ctx, hipMalloc(&ctx->etab, bytes));
         if (ctx->etab_host != h) {
             HIP_CHECK(ctx, hipMemcpy(ctx->etab, h.data(), bytes, hipMemcpyHostToDevice));
@@ -504,6 +546,7 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
         P.n_point = (int32_t) points.size(); P.n_rect = (int32_t) rects.size();
         P.points = (const DPoint *) ctx->etab; P.rects = (const DRect *) ((const unsigned char *) ctx->etab + off);
         P.has_spot = spots.empty() ? 0 : 1;             // the kernels find the cones at off_spot (spot_table)
+        P.has_envmap = envs.empty() ? 0 : 1;            // and the envmap's record at off_env (envmap_rec)
     }
     P.counters = ctx->counters;
     P.work_counter = ctx->counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
@@ -683,6 +726,7 @@ void mer_context_destroy(mer_context *ctx) {
     if (ctx->counters) (void) hipFree(ctx->counters);
     if (ctx->ftable) (void) hipFree(ctx->ftable);
     if (ctx->etab) (void) hipFree(ctx->etab);
+    for (auto &kv : ctx->envmaps) if (kv.second.dev) (void) hipFree(kv.second.dev);
     if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {
         if (pp.slots) (void) hipFree(pp.slots);
@@ -892,12 +936,85 @@ int mer_volume_download_spline(mer_context *ctx, mer_volume h, float *coeff_host
 
 int mer_volume_destroy(mer_context *ctx, mer_volume h) {
     MER_USE_DEVICE(ctx);
+    auto ie = ctx->envmaps.find(h);
+    if (ie != ctx->envmaps.end()) {              // an envmap (mer_envmap_upload)
+        if (ie->second.dev) (void) hipFree(ie->second.dev);
+        ctx->envmaps.erase(ie);
+        return 0;
+    }
     auto it = ctx->volumes.find(h);
     if (it == ctx->volumes.end()) return fail(ctx, "invalid volume handle");
     if (it->second.dense && it->second.owns_dense) (void) hipFree(it->second.dense);
     if (it->second.cell8) (void) hipFree(it->second.cell8);
     if (it->second.coeff) (void) hipFree(it->second.coeff);
     ctx->volumes.erase(it);
+    return 0;
+}
+
+// IEEE binary16, round to nearest even (OpenEXR's half(float), which the reference's SpectrumHalf texels use; overflow -> inf)
+static uint16_t float_to_half(float f) { const _Float16 h = (_Float16) f; uint16_t b; std::memcpy(&b, &h, 2); return b; }
+static float half_to_float(uint16_t b) { _Float16 h; std::memcpy(&h, &b, 2); return (float) h; }
+
+// EnvironmentMap::configure() (src/emitters/envmap.cpp:260-320) on the half-rounded texels: Float = float accumulations in x / y order, the
+// tables stored as float, sin of the double expression, the normalisation formed in double and rounded (the library is built with
+// -ffp-contract=off: each product is rounded as the reference's scalar code rounds it).
+static int envmap_tables(mer_context *ctx, int W, int H, const std::vector<uint16_t> &tex, std::vector<float> &cols, std::vector<float> &rows,
+                         std::vector<float> &weights, float &norm) {
+    cols.assign((size_t) (W + 1) * H, 0.0f); rows.assign((size_t) H + 1, 0.0f); weights.assign((size_t) H, 0.0f);
+    size_t colPos = 0, rowPos = 0;
+    float rowSum = 0.0f;
+    rows[rowPos++] = 0;
+    for (int y = 0; y < H; ++y) {
+        float colSum = 0;
+        cols[colPos++] = 0;
+        for (int x = 0; x < W; ++x) {
+            const uint16_t *t = &tex[((size_t) y * W + x) * 4];
+            const float lum = half_to_float(t[0]) * 0.212671f + half_to_float(t[1]) * 0.715160f + half_to_float(t[2]) * 0.072169f;
+            colSum += lum;
+            cols[colPos++] = colSum;
+        }
+        const float normalization = 1.0f / colSum;
+        for (int x = 1; x < W; ++x) cols[colPos - x - 1] *= normalization;
+        cols[colPos - 1] = 1.0f;
+        const float weight = (float) std::sin((double) (y + 0.5f) * M_PI / H);
+        weights[y] = weight;
+        rowSum += colSum * weight;
+        rows[rowPos++] = rowSum;
+    }
+    const float normalization = 1.0f / rowSum;
+    for (int y = 1; y < H; ++y) rows[rowPos - y - 1] *= normalization;
+    rows[rowPos - 1] = 1.0f;
+    if (rowSum == 0) return fail(ctx, "The environment map is completely black -- this is not allowed.");
+    if (!std::isfinite(rowSum)) return fail(ctx, "The environment map contains an invalid floating point value (nan/inf) -- giving up.");
+    norm = (float) (1.0f / ((double) rowSum * (2 * M_PI / W) * (M_PI / H)));
+    return 0;
+}
+
+int mer_envmap_upload(mer_context *ctx, int32_t width, int32_t height, const float *rgb_host, mer_volume *out) {
+    MER_USE_DEVICE(ctx);
+    if (!out) return fail(ctx, "mer_envmap_upload: no output handle");
+    if (width < 1 || height < 1 || !rgb_host) return fail(ctx, "mer_envmap_upload: the image must have at least one pixel");
+    if (std::max(width, height) > 0xFFFF) return fail(ctx, "Environment maps images must be smaller than 65536 pixels in width and height");
+    const size_t npix = (size_t) width * height;
+    std::vector<uint16_t> tex(npix * 4, 0);
+    for (size_t i = 0; i < npix; ++i)
+        for (int c = 0; c < 3; c++) tex[4 * i + c] = float_to_half(rgb_host[3 * i + c]);
+    EnvMap m; m.w = width; m.h = height;
+    std::vector<float> cols, rows, weights;
+    if (envmap_tables(ctx, width, height, tex, cols, rows, weights, m.norm)) return 1;
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t) 15; };
+    m.off_cols = up16(npix * 8); m.off_rows = up16(m.off_cols + cols.size() * 4); m.off_weights = up16(m.off_rows + rows.size() * 4);
+    const size_t bytes = m.off_weights + weights.size() * 4;
+    std::vector<unsigned char> h(bytes, 0);
+    std::memcpy(h.data(), tex.data(), npix * 8);
+    std::memcpy(h.data() + m.off_cols, cols.data(), cols.size() * 4);
+    std::memcpy(h.data() + m.off_rows, rows.data(), rows.size() * 4);
+    std::memcpy(h.data() + m.off_weights, weights.data(), weights.size() * 4);
+    HIP_CHECK(ctx, hipMalloc(&m.dev, bytes));
+    if (hipMemcpy(m.dev, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void) hipFree(m.dev); return fail(ctx, "mer_envmap_upload: copy to the device failed"); }
+    const int hd = ctx->next_handle++;
+    ctx->envmaps[hd] = m;
+    *out = hd;
     return 0;
 }
 
@@ -1178,6 +1295,36 @@ int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k,
     hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, (const DSpot *) (P.has_spot ? P.rects + MER_MAX_EMITTERS : nullptr), slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
     return r.download(out, n * 32);
+}
+// the scene's envmap record in device memory (make_params has put it behind the spot table), or NULL
+static const DEnvMap *envmap_of(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
+    if (make_params(ctx, scene, P, true)) return nullptr;
+    if (!P.has_envmap) { fail(ctx, std::string(who) + ": the scene's emitter list has no envmap entry"); return nullptr; }
+    return (const DEnvMap *) ((const unsigned char *) (P.rects + MER_MAX_EMITTERS) + sizeof(DSpot) * MER_MAX_EMITTERS);
+}
+int mer_envmap_eval(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_rgb, float *out_pdf) {
+    MER_USE_DEVICE(ctx);
+    Params P;
+    const DEnvMap *E = envmap_of(ctx, scene, P, "mer_envmap_eval");
+    if (!E) return 1;
+    if (n <= 0) return 0;
+    DevBuf a(ctx), v(ctx), q(ctx);
+    if (a.upload(dirs, n * 12) || v.alloc(n * 12) || q.alloc(n * 4)) return 1;
+    hipLaunchKernelGGL(envmap_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, E, a.as<float>(), n, v.as<float>(), q.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    return v.download(out_rgb, n * 12) || q.download(out_pdf, n * 4);
+}
+int mer_envmap_sample(mer_context *ctx, const mer_scene_desc *scene, const float *u2, int64_t n, float *out_dir, float *out_value_over_pdf, float *out_pdf) {
+    MER_USE_DEVICE(ctx);
+    Params P;
+    const DEnvMap *E = envmap_of(ctx, scene, P, "mer_envmap_sample");
+    if (!E) return 1;
+    if (n <= 0) return 0;
+    DevBuf a(ctx), d(ctx), v(ctx), q(ctx);
+    if (a.upload(u2, n * 8) || d.alloc(n * 12) || v.alloc(n * 12) || q.alloc(n * 4)) return 1;
+    hipLaunchKernelGGL(envmap_sample_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, E, a.as<float>(), n, d.as<float>(), v.as<float>(), q.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    return d.download(out_dir, n * 12) || v.download(out_value_over_pdf, n * 12) || q.download(out_pdf, n * 4);
 }
 int mer_rough_dielectric_eval(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *wo, int64_t n,
                               float *out_val, float *out_pdf) {

@@ -40,7 +40,7 @@ __device__ __forceinline__ bool is_zero(f3 a) { return a.x == 0.0f && a.y == 0.0
 // redirected to element 0, so that an out-of-range index is REPORTED (mer_debug_bounds) instead of faulting or, worse, silently
 // reading mapped memory.  The product build compiles the checks away.
 enum { CHK_SLOT = 1, CHK_QUEUE_SEG, CHK_QUEUE_ITEM, CHK_HITQ, CHK_FILM, CHK_PATHOUT, CHK_GRID_DENSE, CHK_GRID_RECORD, CHK_GRID_COEFF,
-       CHK_GRID_RGB, CHK_LIVE_ROW };
+       CHK_GRID_RGB, CHK_LIVE_ROW, CHK_ENVMAP };
 #ifdef MER_BOUNDS_CHECK
 __device__ __forceinline__ uint64_t mer_chk(unsigned long long *chk, int kind, uint64_t idx, uint64_t limit) {
     if (idx < limit) return idx;
@@ -704,7 +704,18 @@ struct DRect { float o2w[12], w2o[12], n[3], inv_area, L[3], pdf, Le[3], cdf; };
 // constructor / configure() do: z row of the inverse of toWorld's linear part, cos(cutoff), cos(beamWidth), cutoff (radians),
 // 1 / (cutoff - beamWidth).  A point emitter's slot holds z = 0 and both cosines -2: its falloff is exactly 1.
 struct DSpot { float z[3], cos_cutoff, cos_beam, cutoff, inv_width, pad; };
-static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144 && sizeof(DSpot) == 32, "emitter records: 16-byte multiples");
+// Emitter `envmap` (src/emitters/envmap.cpp:100-645): one record behind the spot table.  texels = level 0 of the reference's half-float MIP
+// map, [h][w] x (R, G, B, 0) as fp16 (one 8-byte load each); cdf_cols = the conditional CDFs [h][w + 1], cdf_rows = the marginal [h + 1],
+// row_weights [h], all float as configure() stores them (:260-320); norm = m_normalization, scale = `scale`; w2l = the inverse of toWorld's
+// rotation (row-major), l2w = the rotation; pix = m_pixelSize.  make_params / mer_envmap_upload fill it on the host.
+struct DEnvMap {
+    const uint2 *texels; const float *cdf_cols, *cdf_rows, *row_weights;
+    unsigned long long *chk;            // MER_BOUNDS_CHECK: violation record (NULL in the product build)
+    int32_t w, h;
+    float norm, scale, w2l[9], l2w[9], pix[2];
+    float pad[2];
+};
+static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144 && sizeof(DSpot) == 32 && sizeof(DEnvMap) == 144, "emitter records: 16-byte multiples");
 
 // Everything a render / leaf kernel needs, passed by value as the kernel argument.
 struct Params {
@@ -729,6 +740,8 @@ struct Params {
     float *film;                        // float[H][W][film_ch]: RGB per frame, alpha, weight
     int32_t frames, film_ch;            // frames = 1 and film_ch = 5 in steady state
     float mod_phase;                    // path-length modulation phase in radians
+    int32_t has_envmap;                 // 1: the scene has an envmap emitter (EXTRA kernels); its DEnvMap record follows the spot table (envmap_rec).
+                                        // It fills what was padding: Params keeps its size and layout
     float *path_out;                    // per-path radiance (mer_render_paths) or NULL
     unsigned long long *counters;       // MER_C_COUNT
     unsigned long long *work_counter;
@@ -1028,6 +1041,96 @@ __device__ __forceinline__ const DSpot *spot_table(const Params &P) {
 __device__ __forceinline__ float point_falloff(const DSpot *spots, int k, f3 d) {
     return spots ? spot_falloff(spots[k], d) : 1.0f;
 }
+// ---- emitter `envmap` (src/emitters/envmap.cpp).  Level-0 bilinear look-ups everywhere: the reference's EWA filtering of camera rays that keep
+// their differentials (:390-409) is not built.
+// the envmap record (make_params stores it behind the MER_MAX_EMITTERS spot records)
+__device__ __forceinline__ const DEnvMap &envmap_rec(const Params &P) {
+    return *(const DEnvMap *) ((const unsigned char *) (P.rects + MER_MAX_EMITTERS) + sizeof(DSpot) * MER_MAX_EMITTERS);
+}
+// TMIPMap::evalTexel (include/mitsuba/render/mipmap.h:503-560) at level 0: u repeats (ERepeat), v clamps (EClamp)
+__device__ __forceinline__ f3 envmap_texel(const DEnvMap &E, int x, int y) {
+    x %= E.w; if (x < 0) x += E.w;                                         // math::modulo
+    y = min(max(y, 0), E.h - 1);
+    const uint2 q = E.texels[MER_CHK(E.chk, CHK_ENVMAP, (size_t) y * (size_t) E.w + (size_t) x, (size_t) E.w * (size_t) E.h)];
+    const _Float16 *hv = (const _Float16 *) &q;
+    return f3((float) hv[0], (float) hv[1], (float) hv[2]);
+}
+__device__ __forceinline__ float envmap_lum(f3 v) { return v.x * 0.212671f + v.y * 0.715160f + v.z * 0.072169f; }   // spectrum.h:638
+// lat-long coordinates of a local direction (envmap.cpp:385-389, 615-619): (atan2(v.x, -v.z) / 2 pi, safe_acos(v.y) / pi)
+__device__ __forceinline__ void envmap_uv(f3 v, float &u, float &t) {
+    u = atan2f(v.x, -v.z) * (0.5f * MER_INV_PI);
+    t = acosf(fminf(fmaxf(v.y, -1.0f), 1.0f)) * MER_INV_PI;
+}
+__device__ __forceinline__ f3 envmap_to_local(const DEnvMap &E, f3 d) {
+    return f3(E.w2l[0] * d.x + E.w2l[1] * d.y + E.w2l[2] * d.z, E.w2l[3] * d.x + E.w2l[4] * d.y + E.w2l[5] * d.z, E.w2l[6] * d.x + E.w2l[7] * d.y + E.w2l[8] * d.z);
+}
+// the four texels around fractional pixel (x0 + dx1, y0 + dy1), blended per row: value1 = row y0, value2 = row y0 + 1 (envmap.cpp:572-580)
+__device__ __forceinline__ void envmap_rows(const DEnvMap &E, int x0, int y0, float dx1, float dy1, f3 &value1, f3 &value2) {
+    const float dx2 = 1.0f - dx1, dy2 = 1.0f - dy1;
+    value1 = envmap_texel(E, x0, y0) * (dx2 * dy2) + envmap_texel(E, x0 + 1, y0) * (dx1 * dy2);
+    value2 = envmap_texel(E, x0, y0 + 1) * (dx2 * dy1) + envmap_texel(E, x0 + 1, y0 + 1) * (dx1 * dy1);
+}
+// evalEnvironment (envmap.cpp:380-415; evalBilinear, mipmap.h:573-596) and internalPdfDirection (:612-645) at the unit local direction v, which
+// share their four texels.  A non-finite (u, v) gives 0 (evalBilinear's NaN guard).
+__device__ __forceinline__ f3 envmap_eval_local(const DEnvMap &E, f3 v, float &pdf) {
+    float u, t; envmap_uv(v, u, t);
+    pdf = 0.0f;
+    if (!isfinite(u) || !isfinite(t)) return f3(0, 0, 0);
+    const float fu = u * (float) E.w - 0.5f, fv = t * (float) E.h - 0.5f;
+    const int x0 = (int) floorf(fu), y0 = (int) floorf(fv);
+    f3 value1, value2;
+    envmap_rows(E, x0, y0, fu - (float) x0, fv - (float) y0, value1, value2);
+    const float sinTheta = sqrtf(fmaxf(1.0f - v.y * v.y, 0.0f));
+    pdf = (envmap_lum(value1) * E.row_weights[min(max(y0, 0), E.h - 1)] + envmap_lum(value2) * E.row_weights[min(max(y0 + 1, 0), E.h - 1)])
+          * E.norm / fmaxf(fabsf(sinTheta), MER_EPSILON);
+    return (value1 + value2) * E.scale;
+}
+// value (x scale) and pdfDirect of the UNIT world direction d (acos and sin theta take its y component as a cosine)
+__device__ __forceinline__ f3 envmap_eval(const DEnvMap &E, f3 d, float &pdf) { return envmap_eval_local(E, envmap_to_local(E, d), pdf); }
+__device__ __forceinline__ f3 envmap_value(const DEnvMap &E, f3 d) { float pdf; return envmap_eval(E, d, pdf); }
+__device__ __forceinline__ float envmap_pdf(const DEnvMap &E, f3 d) { float pdf; (void) envmap_eval(E, d, pdf); return pdf; }
+// sampleReuse (envmap.cpp:657-662): lower_bound over cdf[0 .. size], index clamped to [0, size - 1], the sample rescaled in place.  The
+// search is bounded by construction (NaN entries of an all-black row cannot move it out of range).
+__device__ __forceinline__ int envmap_sample_reuse(const DEnvMap &E, const float *cdf, int size, float &sample) {
+    int lo = 0, n = size + 1;                                              // first entry >= sample in [0, size + 1)
+    while (n > 0) {
+        const int half = n >> 1;
+        if (cdf[MER_CHK(E.chk, CHK_ENVMAP, lo + half, size + 1)] < sample) { lo += half + 1; n -= half + 1; }
+        else n = half;
+    }
+    const int index = min(max(lo - 1, 0), size - 1);
+    sample = (sample - cdf[index]) / (cdf[index + 1] - cdf[index]);
+    return index;
+}
+__device__ __forceinline__ float interval_to_tent(float s) {              // warp.cpp:143-155
+    float sign;
+    if (s < 0.5f) { sign = 1; s *= 2; } else { sign = -1; s = 2 * (s - 0.5f); }
+    return sign * (1 - sqrtf(s));
+}
+// sampleDirect / internalSampleDirection (envmap.cpp:516-610): returns value x scale / pdf (0 when either is 0), the world direction d and
+// the pdf.  The scene's bounding-sphere test of sampleDirect always passes for a reference point inside the scene and is left out.
+__device__ __forceinline__ f3 envmap_sample(const DEnvMap &E, float sx, float sy, f3 &d, float &pdf) {
+    const int row = envmap_sample_reuse(E, E.cdf_rows, E.h, sy);
+    const int col = envmap_sample_reuse(E, E.cdf_cols + (size_t) row * (size_t) (E.w + 1), E.w, sx);
+    const float px = (float) col + interval_to_tent(sx), py = (float) row + interval_to_tent(sy);
+    const int x0 = (int) floorf(px), y0 = (int) floorf(py);
+    f3 value1, value2;
+    envmap_rows(E, x0, y0, px - (float) x0, py - (float) y0, value1, value2);
+    const f3 value = (value1 + value2) * E.scale;
+    pdf = (envmap_lum(value1) * E.row_weights[min(max(y0, 0), E.h - 1)] + envmap_lum(value2) * E.row_weights[min(max(y0 + 1, 0), E.h - 1)]) * E.norm;
+    const float phi = E.pix[0] * (px + 0.5f), theta = E.pix[1] * (py + 0.5f);
+    const float sinPhi = sinf(phi), cosPhi = cosf(phi), sinTheta = sinf(theta), cosTheta = cosf(theta);
+    const f3 v(sinPhi * sinTheta, cosTheta, -cosPhi * sinTheta);
+    pdf /= fmaxf(fabsf(sinTheta), MER_EPSILON);
+    d = f3(E.l2w[0] * v.x + E.l2w[1] * v.y + E.l2w[2] * v.z, E.l2w[3] * v.x + E.l2w[4] * v.y + E.l2w[5] * v.z, E.l2w[6] * v.x + E.l2w[7] * v.y + E.l2w[8] * v.z);
+    if (!(pdf > 0) || is_zero(value)) { pdf = 0.0f; return f3(0, 0, 0); }
+    return value / pdf;
+}
+// the environment seen along the world direction d: the map in the EXTRA kernels of an envmap scene, else the constant env_radiance
+template <bool EXTRA>
+__device__ __forceinline__ f3 env_along(const Params &P, f3 env, f3 d) {
+    return (EXTRA && P.has_envmap) ? envmap_value(envmap_rec(P), d) : env;
+}
 // AreaLight::eval (area.cpp:102-107): the radiance a ray travelling along d picks up on the rectangle (one-sided)
 __device__ __forceinline__ f3 rect_le(const DRect &R, f3 d) {
     const f3 n(R.n[0], R.n[1], R.n[2]);
@@ -1059,14 +1162,15 @@ __device__ __forceinline__ float rect_pdf_direct(const DRect &R, f3 d, float dis
 // radiance, back side: black, and either way it hides the environment (all-absorbing BSDF, shape.cpp:48-56) -- else the environment.
 // extra = the optical length of the free-space leg to the rectangle (transient films).  AREA is a compile-time switch: the plain kernels
 // carry none of this.
-template <bool AREA>
+// ENV: the envmap is looked up along d (the EXTRA kernels; env_along).
+template <bool AREA, bool ENV = AREA>
 __device__ __forceinline__ f3 escape_radiance(const Params &P, f3 env, f3 o, f3 d, float mint, float &extra) {
     extra = 0.0f;
     if (AREA && P.n_rect) {
         int k; const float t = rect_nearest(P, o, d, mint, MER_INF, k);
         if (t >= 0) { extra = t * P.sc.rif_const; return rect_le(P.rects[k], d); }
     }
-    return env;
+    return env_along<ENV>(P, env, d);
 }
 
 // ImageBlock::put (include/mitsuba/render/imageblock.h:124-205) with one block = the whole image;

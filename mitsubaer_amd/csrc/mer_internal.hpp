@@ -24,6 +24,15 @@ struct Volume {
     size_t bytes_dense = 0;
 };
 
+// emitter `envmap` (mer_envmap_upload): one device buffer -- texels [h][w] (4 x fp16), then the float tables cdf_cols [h][w + 1], cdf_rows [h + 1],
+// row_weights [h] at the given byte offsets -- and the normalisation.  Its handle shares the volumes' numbering.
+struct EnvMap {
+    void *dev = nullptr;
+    int32_t w = 0, h = 0;
+    float norm = 0;
+    size_t off_cols = 0, off_rows = 0, off_weights = 0;
+};
+
 #define MER_MAX_PIPES 4
 struct Pipe {
     hipStream_t stream = nullptr, own_stream = nullptr;      // pipeline 0 runs on the context stream
@@ -69,6 +78,7 @@ struct mer_context {
     hipStream_t stream = nullptr;
     std::string error;
     std::map<int, mer::Volume> volumes;
+    std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds

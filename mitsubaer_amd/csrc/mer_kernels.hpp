@@ -162,6 +162,19 @@ __global__ void emitter_direct_kernel(const DPoint *points, const DSpot *spots, 
     float *o = out + 8 * i;
     o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dist; o[7] = fall;
 }
+// EnvironmentMap::evalEnvironment / pdfDirect (envmap.cpp:385-415, 531-645) and sampleDirect (:516-610): the render kernels' device functions
+__global__ void envmap_eval_kernel(const DEnvMap *E, const float *dirs, int64_t n, float *val, float *pdf) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float p; const f3 v = envmap_eval(*E, normalize(f3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2])), p);      // the ABI takes any length
+    val[3 * i] = v.x; val[3 * i + 1] = v.y; val[3 * i + 2] = v.z; pdf[i] = p;
+}
+__global__ void envmap_sample_kernel(const DEnvMap *E, const float *u2, int64_t n, float *dir, float *vop, float *pdf) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 d; float p; const f3 v = envmap_sample(*E, u2[2 * i], u2[2 * i + 1], d, p);
+    dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z; vop[3 * i] = v.x; vop[3 * i + 1] = v.y; vop[3 * i + 2] = v.z; pdf[i] = p;
+}
 __global__ void rough_eval_kernel(int type, float alpha, int visible, const float *eta, const float *wi, const float *wo, int64_t n, float *val, float *pdf) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -140,6 +140,18 @@ int mer_multi_volume_upload(mer_multi *m, const mer_grid_desc *desc, const void 
     *out = h0;
     return 0;
 }
+int mer_multi_envmap_upload(mer_multi *m, int32_t width, int32_t height, const float *rgb_host, mer_volume *out) {
+    if (!m || !out) return 1;
+    mer_volume h0 = 0;
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        mer_volume h = 0;
+        if (mer_envmap_upload(m->ctx[i], width, height, rgb_host, &h)) return mfail(m, mer_last_error(m->ctx[i]));
+        if (i == 0) h0 = h;
+        else if (h != h0) return mfail(m, "mer_multi_envmap_upload: the contexts' handles differ (volumes created through mer_multi_context()?)");
+    }
+    *out = h0;
+    return 0;
+}
 int mer_multi_volume_build_spline(mer_multi *m, mer_volume v) {
     if (!m) return 1;
     for (mer_context *c : m->ctx) if (mer_volume_build_spline(c, v)) return mfail(m, mer_last_error(c));

@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                 // the area emitter's rectangle in front of the medium shape (or hit instead of it): its.isEmitter() => Le, then the all-absorbing BSDF ends the path
                 int kRect = 0; const float tRect = (EXTRA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
                 if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P.rects[kRect], d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
-                else if (itsT < 0) { if (!S.hide_emitters) L = env; }
+                else if (itsT < 0) { if (!S.hide_emitters) L = env_along<EXTRA>(P, env, d); }
                 else if (1 >= maxDepth && maxDepth != -1) { }
                 else if (EXTRA && S.boundary_bsdf != MER_BSDF_NULL) hit = true;      // Fresnel / microfacet sampling at the surface: K_event
                 else {
@@ -593,7 +593,10 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
     constexpr bool rough = ROUGH;                 // hroughdielectric (the host selects this instance for it): the surface vertex samples the point emitter
     const bool dielectric = EXTRA && (rough || S.boundary_bsdf == MER_BSDF_HDIELECTRIC);
     // a dielectric boundary blocks emitter sampling and look-ups from inside: the environment is reached by refracting out
-    const bool hasEnv = !is_zero(env) && !dielectric;
+    const bool envmap = EXTRA && P.has_envmap;    // an envmap emitter takes the constant environment's place (env_along, envmap_*)
+    const bool hasEnv = (!is_zero(env) || envmap) && !dielectric;
+    // the map's luminaire sample and look-up (behind a dielectric boundary there are none: the ROUGH instances compile them out)
+    const bool envLight = envmap && !dielectric;
     const bool hasEmission = S.emission[0] != 0 || S.emission[1] != 0 || S.emission[2] != 0;
     const bool hasPoint = EXTRA && P.n_point > 0;
     const int maxDepth = S.max_depth;
@@ -689,7 +692,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 ev = EV_PATH_DONE;
             } else
             if (itsT < 0) {
-                if (!S.hide_emitters) { L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen); }   // volpath.cpp:194-201
+                if (!S.hide_emitters) { const f3 Le = T * env_along<EXTRA>(P, env, d); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }   // volpath.cpp:194-201
                 ev = EV_PATH_DONE;
             } else if (depth >= maxDepth && maxDepth != -1) ev = EV_PATH_DONE;
             else if (dielectric) {
@@ -703,7 +706,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     if (!is_zero(Le)) { const float pl = plen + edge_length(P, eLen); L = L + mod_weight<EXTRA>(P, Le, pl); film_contribute(P, px, py, Le, pl); }
                 } else enters = dielectric_event<CURVED, RIF, BND>(P, rng, o, d, itsT, false, T, etaPath, x, wo);
                 if (!enters) {
-                    L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen);
+                    const f3 Le = T * env_along<EXTRA>(P, env, wo);
+                    L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen);
                     ev = EV_PATH_DONE;
                 } else {
                     ps = x; dsave = wo;
@@ -750,6 +754,9 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             ev = W.on_arrived(P, rng, C, sigma);
         } else if (ev == EV_EXITED) {
             if (CURVED && W.kind != K_FREE) trOpt = W.opt;     // this transmittance walk reached the boundary
+            // envmap, curved rays: the map is looked up where the walk leaves the shape.  The luminaire sample keeps its exit
+            // direction in dsave, the look-up in dd: neither is read again before the path's next phase sample / luminaire sample
+            if (CURVED && envLight && W.kind != K_FREE) { const f3 dx = normalize(W.v); if (W.kind == K_NEE) dsave = dx; else dd = dx; }
             ev = (W.kind == K_FREE) ? EV_FAIL : EV_WALK_END;
         } else if (ev == EV_GATE_FAIL) {
             if (W.kind == K_FREE) ev = EV_PATH_DONE;          // transmittance 0 => nothing further contributes
@@ -790,9 +797,16 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 const int interactions = maxDepth - depth - 1;
                 const float s2x = rng.next1D(), s2y = rng.next1D();
                 dd = square_to_uniform_sphere(s2x, s2y);
+                bool skip = false;
+                if (envLight) {                                                       // EnvironmentMap::sampleDirect (envmap.cpp:516-551) replaces it
+                    float epdf; const f3 v = envmap_sample(envmap_rec(P), s2x, s2y, dd, epdf);
+                    skip = is_zero(v);                                                // a sample of value 0 skips its transmittance walk
+                    if (CURVED) dsave = dd;                                           // the walk's exit direction until it reports one (EV_EXITED)
+                }
                 W.kind = K_NEE;
                 trOpt = 0.0f;
-                if (interactions != 0) {                                              // scene.cpp:619-678: one null crossing
+                if (skip) { trv = f3(0, 0, 0); ev = EV_TR_DONE; }
+                else if (interactions != 0) {                                         // scene.cpp:619-678: one null crossing
                     float tExit = 0.0f;
                     if (!CURVED) tExit = intersect_shape_b<BND>(P, ps, dd, 0.0f, MER_INF);
                     if (tExit >= 0) {
@@ -833,8 +847,14 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             if (flags & F_FORKED) { rng.state = prng; SET_FLAG(F_FORKED, false); }           // the side walk is over: back on the path's own stream
             f3 tr = trv;
             if (W.kind == K_NEE) {
-                const float dpdf = MER_INV_FOURPI;
+                float dpdf = MER_INV_FOURPI;
                 f3 value = env / dpdf;
+                if (envLight) {                                                       // value(exit direction) / pdfDirect(d0); straight rays: exit = d0
+                    const DEnvMap &E = envmap_rec(P);
+                    value = envmap_eval(E, dd, dpdf);
+                    if (CURVED) value = envmap_value(E, dsave);
+                    value = dpdf > 0 ? value / dpdf : f3(0, 0, 0);
+                }
                 // any rectangle shadows the environment (Scene::evalTransmittance stops at a non-null surface); tested after the walk so that the sampler draws stay the oracle's
                 if (EXTRA && P.n_rect && rect_blocks(P, ps, dd, 0.0f, MER_INF, -1)) tr = f3(0, 0, 0);
                 value = value * tr;
@@ -855,6 +875,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 if (!blocked && !is_zero(tr)) {
                     f3 value = tr * env;
                     float emitterPdf = MER_INV_FOURPI, extra = 0.0f;
+                    if (envLight) {                                                   // the map at the exit direction, pdfDirect at d0
+                        const DEnvMap &E = envmap_rec(P);
+                        value = tr * envmap_eval(E, dsave, emitterPdf);
+                        if (CURVED) value = tr * envmap_value(E, dd);
+                    }
                     if (EXTRA && P.n_rect) {
                         // rayIntersectAndLookForEmitter (volpath.cpp:370-428): beyond the null boundary the ray meets the nearest rectangle or the environment;
                         // the MIS partner's pdf is that of sampling this rectangle: its selection probability x its solid-angle pdf
@@ -935,6 +960,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             else { itsT = intersect_shape_b<BND>(P, ps, wo, 0.0f, MER_INF); SET_FLAG(F_ITSVALID, itsT >= 0); }
             if (hasEnv || (EXTRA && P.n_rect)) {
                 W.kind = K_LOOKUP;
+                if (CURVED && envLight) dd = wo;                                        // the walk's exit direction until it reports one (EV_EXITED)
                 trOpt = (!CURVED && itsValid) ? itsT * S.rif_const : 0.0f;
                 if (!CURVED && !itsValid) { trv = f3(1, 1, 1); ev = EV_TR_DONE; }
                 else {
@@ -996,7 +1022,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     if (!is_zero(Le)) { const float pl = plen + edge_length(P, eLen); L = L + mod_weight<EXTRA>(P, Le, pl); film_contribute(P, px, py, Le, pl); }
                 } else stays = dielectric_event<CURVED, RIF, BND>(P, rng, ro, rd, tHit, true, T, etaPath, x, wo);
                 if (!stays) {
-                    L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen);
+                    const f3 Le = T * env_along<EXTRA>(P, env, wo);
+                    L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen);
                 } else {
                     ps = x; dsave = wo;
                     if (CURVED) itsT = 0;
@@ -1004,11 +1031,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     if (CURVED || itsValid) ev = EV_AFTER_LOOKUP;
                 }
             } else if (dielectric) {
-                if (!itsValid && emitted && (!S.hide_emitters || scattered)) { L = L + mod_weight<EXTRA>(P, T * env, plen); film_contribute(P, px, py, T * env, plen); }
+                if (!itsValid && emitted && (!S.hide_emitters || scattered)) { const f3 Le = T * env_along<EXTRA>(P, env, dsave); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }
             } else
             if (!itsValid) {
                 if (emitted && (!S.hide_emitters || scattered)) {
-                    float extra; const f3 Le = escape_radiance<EXTRA && !CURVED>(P, env, ps, dsave, 0.0f, extra);
+                    float extra; const f3 Le = escape_radiance<EXTRA && !CURVED, EXTRA>(P, env, ps, dsave, 0.0f, extra);
                     const float pl = plen + (S.decomposition != MER_DECOMPOSITION_BOUNCE ? extra : 0.0f);
                     L = L + mod_weight<EXTRA>(P, T * Le, pl); film_contribute(P, px, py, T * Le, pl);
                 }
@@ -1019,7 +1046,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 if (depth <= maxDepth || maxDepth < 0)
                     if (emitted && (!S.hide_emitters || scattered)) {
                         // outside the (convex) shape now: the environment, or the area emitter's rectangle (straight rays: from the exit point ps + itsT dsave)
-                        float extra; const f3 Le = escape_radiance<EXTRA && !CURVED>(P, env, ps + dsave * itsT, dsave, 0.0f, extra);
+                        // (curved rays: the map at the direction in which the path left the shape)
+                        float extra; const f3 Le = escape_radiance<EXTRA && !CURVED, EXTRA>(P, env, ps + dsave * itsT, (CURVED && envLight) ? normalize(m.d) : dsave, 0.0f, extra);
                         const float pl = plen + (S.decomposition != MER_DECOMPOSITION_BOUNCE ? extra : 0.0f);
                         L = L + mod_weight<EXTRA>(P, T * Le, pl); film_contribute(P, px, py, T * Le, pl);
                     }

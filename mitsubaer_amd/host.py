@@ -54,6 +54,18 @@ def render_xml(path, defines=None, device=0, spp=0, seed=0, layout=capi.LAYOUT_A
     return film
 
 
+def read_envmap_image(path):
+    """merhost::readEnvmapImage: the image an `envmap` emitter loads (.pfm, or uncompressed scan-line OpenEXR with HALF / FLOAT R, G, B)
+    -> float32 [h][w][3]"""
+    w = C.c_int32(); h = C.c_int32()
+    if lib().merhost_read_envmap_image(path.encode(), C.byref(w), C.byref(h), None) != 0:
+        raise HostError(lib().merhost_last_error().decode())
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    if lib().merhost_read_envmap_image(path.encode(), C.byref(w), C.byref(h), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HostError(lib().merhost_last_error().decode())
+    return out
+
+
 def write_exr(path, rgb):
     """rgb: float32 [h][w][3] -> uncompressed scan-line OpenEXR (merhost::writeExr)"""
     a = np.ascontiguousarray(rgb, np.float32)

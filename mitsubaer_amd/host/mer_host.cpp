@@ -7,6 +7,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <iterator>
 #include <sstream>
 
 namespace merhost {
@@ -482,7 +483,27 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             if (!(std::fabs(det) > 0)) Log_EError("spot emitter: 'toWorld' is singular");
             for (int i = 0; i < 3; i++) if (!(o->radiance.c[i] >= 0)) Log_EError("spot emitter: intensity must be non-negative");
             o->position = Vec3{M[3], M[7], M[11]};
-        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, point, spot, area)");
+        } else if (type == "envmap") {                                   // src/emitters/envmap.cpp:103-187
+            o->kind = Emitter::EEnvmap;
+            const std::string fn = resolve(props.getString("filename"));
+            { std::ifstream f(fn); if (!f) Log_EError("Environment map file \"" + fn + "\" could not be found!"); }
+            if (props.hasProperty("gamma") && props.getFloat("gamma") != 0) Log_EError("envmap emitter: 'gamma' is not supported on the GPU path (LDR images are not read)");
+            if (props.hasProperty("cache")) (void) props.getBoolean("cache");        // the MIP-map cache file: not used
+            if (props.hasProperty("intensityScale")) Log_EError("The 'intensityScale' parameter has been deprecated and is now called scale.");
+            o->scale = props.getFloat("scale", 1.0f);
+            if (!std::isfinite(o->scale) || o->scale < 0) Log_EError("envmap emitter: 'scale' must be finite and non-negative");
+            props.getTransform("toWorld", o->toWorld);
+            const float *M = o->toWorld;                                  // a rotation (the translation is ignored): mer_render's check
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) {
+                    const double d = (double) M[4 * r] * M[4 * c] + (double) M[4 * r + 1] * M[4 * c + 1] + (double) M[4 * r + 2] * M[4 * c + 2] - (r == c ? 1.0 : 0.0);
+                    if (!(std::fabs(d) <= 1e-5)) Log_EError("envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)");
+                }
+            const double det = (double) M[0] * ((double) M[5] * M[10] - (double) M[6] * M[9]) - (double) M[1] * ((double) M[4] * M[10] - (double) M[6] * M[8]) +
+                               (double) M[2] * ((double) M[4] * M[9] - (double) M[5] * M[8]);
+            if (!(det > 0)) Log_EError("envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)");
+            o->image = readEnvmapImage(fn, o->imageW, o->imageH);
+        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, envmap, point, spot, area)");
         o->samplingWeight = props.getFloat("samplingWeight", 1.0f);     // src/librender/emitter.cpp:103
         if (!(o->samplingWeight > 0) || !std::isfinite(o->samplingWeight)) Log_EError("emitter \"" + type + "\": samplingWeight must be positive");
         out = o;
@@ -788,7 +809,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     d.tr_estimator = m.trEstimator; d.method = m.method; d.het_stepsize = m.hetStepSize;
     // point emitters and the area emitters of `rectangle` shapes, in scene order (rectangles first).  At most one of each kind: the single-emitter
     // fields of the scene desc; more: the emitter list (scene.emitterList), each entry with its samplingWeight
-    int nconst = 0, npoint = 0, narea = 0, nspot = 0;
+    int nconst = 0, npoint = 0, narea = 0, nspot = 0, nenv = 0;
     std::vector<mer_emitter> &list = scene.emitterList;
     list.clear();
     for (int i = 0; i < 3; i++) { d.env_radiance[i] = 0; d.point_intensity[i] = 0; d.point_position[i] = 0; d.emission[i] = m.emission.c[i]; d.area_radiance[i] = 0; }
@@ -815,13 +836,20 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
             for (int i = 0; i < 3; i++) { q.intensity[i] = e->radiance.c[i]; q.position[i] = e->toWorld[4 * i + 3]; }
             q.cutoff_angle_deg = e->cutoffAngle; q.beam_width_deg = e->beamWidth;
             list.push_back(q); ++nspot;
+        } else if (e->kind == Emitter::EEnvmap) {                        // always a list entry; render() uploads the image and sets the handle
+            if (nconst + nenv > 0) Log_EError("The scene may only contain one environment emitter");       // src/librender/scene.cpp:512
+            mer_emitter q{}; q.type = MER_EMITTER_ENVMAP; q.sampling_weight = e->samplingWeight;
+            for (int i = 0; i < 12; i++) q.to_world[i] = e->toWorld[i];
+            q.envmap = 0; q.env_scale = e->scale; q.env_reserved = 0;
+            list.push_back(q); ++nenv;
         } else {
+            if (nenv > 0) Log_EError("The scene may only contain one environment emitter");
             if (++nconst > 1) Log_EError("Only one constant emitter is supported on the GPU path");
             for (int i = 0; i < 3; i++) d.env_radiance[i] = e->radiance.c[i];
         }
     }
     if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point, spot and area emitters are supported on the GPU path");
-    if (npoint <= 1 && narea <= 1 && nspot == 0) {
+    if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0) {
         for (const mer_emitter &e : list) {
             if (e.type == MER_EMITTER_AREA) { for (int i = 0; i < 12; i++) d.area_to_world[i] = e.to_world[i]; for (int i = 0; i < 3; i++) d.area_radiance[i] = e.radiance[i]; }
             else for (int i = 0; i < 3; i++) { d.point_position[i] = e.position[i]; d.point_intensity[i] = e.intensity[i]; }
@@ -833,7 +861,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
         if (npoint == 1 && point_inside_shape(d, m, d.point_position))
             Log_EError("hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
         for (const mer_emitter &e : list)
-            if (e.type != MER_EMITTER_AREA && point_inside_shape(d, m, e.position))
+            if ((e.type == MER_EMITTER_POINT || e.type == MER_EMITTER_SPOT) && point_inside_shape(d, m, e.position))
                 Log_EError(std::string("hroughdielectric: the ") + (e.type == MER_EMITTER_SPOT ? "spot" : "point") +
                            " emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
     }
@@ -878,6 +906,15 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
         if (m.rif->isSpline() && mer_multi_volume_build_spline(mm, d.rif)) fail();
     }
     if (m.sdf) d.sdf = upload(*m.sdf, MER_LAYOUT_DENSE);
+    {   // the envmap's image (its list entry comes out of flatten with handle 0)
+        size_t k = 0;
+        for (auto &e : scene.emitters) {
+            if (e->kind != Emitter::EEnvmap) continue;
+            while (k < scene.emitterList.size() && scene.emitterList[k].type != MER_EMITTER_ENVMAP) k++;
+            if (k == scene.emitterList.size()) Log_EError("Integrator::render: the envmap emitter has no list entry");
+            if (mer_multi_envmap_upload(mm, e->imageW, e->imageH, e->image.data(), &scene.emitterList[k].envmap)) fail();
+        }
+    }
     if (mer_film_channels(mer_multi_context(mm, 0), &d, &channels)) { std::string msg = mer_last_error(mer_multi_context(mm, 0)); mer_multi_destroy(mm); Log_EError(msg); }
     std::vector<float> film((size_t) d.width * d.height * channels, 0.0f);
     if (mer_multi_render(mm, &d, shardMode, 0, spp, seed, 1, film.data())) fail();
@@ -912,6 +949,91 @@ void writePfm(const std::string &path, const float *rgb, int h, int w) {
     if (!f) Log_EError("Unable to write \"" + path + "\"");
     f << "PF\n" << w << " " << h << "\n-1.0\n";
     for (int y = h - 1; y >= 0; y--) f.write((const char *) (rgb + (size_t) y * w * 3), (std::streamsize) ((size_t) w * 12));
+}
+
+// IEEE binary16 -> float (exact)
+static float half_to_float(uint16_t b) {
+    const int e = (b >> 10) & 0x1f, m = b & 0x3ff;
+    const float v = e == 0 ? std::ldexp((float) m, -24) : e == 31 ? (m ? NAN : INFINITY) : std::ldexp((float) (m | 0x400), e - 25);
+    return (b & 0x8000) ? -v : v;
+}
+// `.pfm` (Bitmap::readPFM, src/libcore/bitmap.cpp: "PF" colour, width height, scale whose sign is the byte order, rows bottom to top) or an
+// OpenEXR 2 scan-line file without compression with R, G, B channels of type HALF or FLOAT (others are ignored): float [h][w][3], top row first
+std::vector<float> readEnvmapImage(const std::string &path, int &w, int &h) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) Log_EError("Environment map file \"" + path + "\" could not be found!");
+    std::string bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    auto bad = [&](const std::string &why) { Log_EError("Environment map file \"" + path + "\": " + why); };
+    std::vector<float> out;
+    if (bytes.size() >= 2 && bytes[0] == 'P' && (bytes[1] == 'F' || bytes[1] == 'f')) {
+        if (bytes[1] != 'F') bad("a greyscale PFM is not supported (RGB 'PF' only)");
+        std::istringstream hs(bytes); std::string magic; double scale = 0;
+        if (!(hs >> magic >> w >> h >> scale) || w < 1 || h < 1 || scale == 0) bad("malformed PFM header");
+        hs.get();                                                         // the single whitespace after the scale
+        const size_t off = (size_t) hs.tellg(), n = (size_t) w * h * 3;
+        if (bytes.size() < off + n * 4) bad("truncated PFM data");
+        out.resize(n);
+        const bool swap = scale > 0;                                      // positive scale: big endian
+        for (int y = 0; y < h; y++)
+            for (size_t i = 0; i < (size_t) w * 3; i++) {
+                uint32_t v; std::memcpy(&v, bytes.data() + off + ((size_t) (h - 1 - y) * w * 3 + i) * 4, 4);
+                if (swap) v = __builtin_bswap32(v);
+                std::memcpy(&out[(size_t) y * w * 3 + i], &v, 4);
+            }
+        return out;
+    }
+    size_t p = 0;
+    auto rd32 = [&](void) -> uint32_t { if (p + 4 > bytes.size()) bad("truncated OpenEXR file"); uint32_t v; std::memcpy(&v, bytes.data() + p, 4); p += 4; return v; };
+    auto rdstr = [&](void) -> std::string { const size_t e = bytes.find('\0', p); if (e == std::string::npos) bad("truncated OpenEXR header"); std::string r = bytes.substr(p, e - p); p = e + 1; return r; };
+    if (rd32() != 20000630u) bad("not a .pfm or OpenEXR file (other formats are not read on the GPU path)");
+    const uint32_t ver = rd32();
+    if ((ver & 0xffu) != 2u || (ver & 0x1e00u) != 0u) bad("only single-part scan-line OpenEXR files are supported");
+    struct Ch { std::string name; int type; };
+    std::vector<Ch> chans; int compression = -1; int32_t box[4] = {0, 0, -1, -1};
+    for (;;) {
+        const std::string name = rdstr();
+        if (name.empty()) break;
+        const std::string type = rdstr(); const uint32_t size = rd32();
+        if (p + size > bytes.size()) bad("truncated OpenEXR header");
+        const char *a = bytes.data() + p;
+        if (name == "channels") {
+            size_t q = 0;
+            while (q < size && a[q]) { std::string cn(a + q); q += cn.size() + 1; int32_t t; std::memcpy(&t, a + q, 4); q += 16; chans.push_back({cn, t}); }
+        } else if (name == "compression") compression = (unsigned char) a[0];
+        else if (name == "dataWindow") std::memcpy(box, a, 16);
+        p += size;
+    }
+    if (compression != 0) bad("only uncompressed OpenEXR files are supported");
+    w = box[2] - box[0] + 1; h = box[3] - box[1] + 1;
+    if (w < 1 || h < 1) bad("empty OpenEXR data window");
+    int idx[3] = {-1, -1, -1}; size_t lineBytes = 0;
+    std::vector<size_t> chOff;
+    for (size_t c = 0; c < chans.size(); c++) {
+        const int t = chans[c].type;
+        if (t != 1 && t != 2) bad("channel \"" + chans[c].name + "\": only HALF and FLOAT channels are supported");
+        chOff.push_back(lineBytes); lineBytes += (size_t) w * (t == 1 ? 2 : 4);
+        if (chans[c].name == "R") idx[0] = (int) c; else if (chans[c].name == "G") idx[1] = (int) c; else if (chans[c].name == "B") idx[2] = (int) c;
+    }
+    if (idx[0] < 0 || idx[1] < 0 || idx[2] < 0) bad("the R, G and B channels are required");
+    std::vector<uint64_t> offsets((size_t) h);
+    for (int y = 0; y < h; y++) { const uint32_t lo = rd32(), hi = rd32(); offsets[y] = (uint64_t) lo | ((uint64_t) hi << 32); }
+    out.assign((size_t) w * h * 3, 0.0f);
+    for (int y = 0; y < h; y++) {
+        p = (size_t) offsets[y];
+        const int32_t line = (int32_t) rd32(); const uint32_t size = rd32();
+        const int row = line - box[1];
+        if (row < 0 || row >= h || size != lineBytes || p + size > bytes.size()) bad("malformed scan line");
+        for (int k = 0; k < 3; k++) {
+            const Ch &c = chans[idx[k]];
+            for (int x = 0; x < w; x++) {
+                float v;
+                if (c.type == 2) std::memcpy(&v, bytes.data() + p + chOff[idx[k]] + (size_t) x * 4, 4);
+                else { uint16_t hb; std::memcpy(&hb, bytes.data() + p + chOff[idx[k]] + (size_t) x * 2, 2); v = half_to_float(hb); }
+                out[((size_t) row * w + x) * 3 + k] = v;
+            }
+        }
+    }
+    return out;
 }
 
 void writeExr(const std::string &path, const float *rgb, int h, int w) {
@@ -968,6 +1090,15 @@ int merhost_write_exr(const char *path, const float *rgb, int32_t h, int32_t w) 
     try { merhost::writeExr(path, rgb, h, w); return 0; } catch (const std::exception &e) { g_host_error = e.what(); return 1; }
 }
 const char *merhost_last_error(void) { return g_host_error.c_str(); }
+int merhost_read_envmap_image(const char *path, int32_t *w, int32_t *h, float *out) {
+    try {
+        int W = 0, H = 0;
+        const std::vector<float> img = merhost::readEnvmapImage(path, W, H);
+        *w = W; *h = H;
+        if (out) std::memcpy(out, img.data(), img.size() * sizeof(float));
+        return 0;
+    } catch (const std::exception &e) { g_host_error = e.what(); return 1; }
+}
 int merhost_flatten_xml(const char *path, const char *defines, mer_scene_desc *out, int32_t *spp) {
     try {
         auto scene = merhost::loadScene(path, parseDefines(defines));

@@ -183,12 +183,14 @@ public:
 class Emitter : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "Emitter"; }
-    enum Kind { EConstant, EPoint, EArea, ESpot } kind = EConstant;
+    enum Kind { EConstant, EPoint, EArea, ESpot, EEnvmap } kind = EConstant;
     Spectrum radiance{};                        // constant / area: radiance ; point / spot: intensity
     Vec3 position{0, 0, 0};                     // point (src/emitters/point.cpp:60-68)
     float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // spot: its frame (src/emitters/spot.cpp:124-131)
     float cutoffAngle = 20, beamWidth = 15;     // spot: degrees (spot.cpp:68-73)
     float samplingWeight = 1.0f;                // `samplingWeight` (src/librender/emitter.cpp:103): selection weight among the emitters of its kind
+    std::vector<float> image; int imageW = 0, imageH = 0;      // envmap: the lat-long image as loaded, float [h][w][3] (src/emitters/envmap.cpp:116-160)
+    float scale = 1.0f;                         // envmap: `scale`
 };
 
 class Scene;
@@ -231,12 +233,16 @@ void writePfm(const std::string &path, const float *rgb, int h, int w);
 /// OpenEXR 2 scan-line file, uncompressed, three float32 channels B, G, R (what HDRFilm::develop writes through OpenEXR,
 /// src/films/hdrfilm.cpp:527; no OpenEXR library is needed for this subset)
 void writeExr(const std::string &path, const float *rgb, int h, int w);
+/// the image of an `envmap` emitter: a `.pfm` or an uncompressed scan-line OpenEXR file with float32 or half R, G, B channels -> float [h][w][3]
+std::vector<float> readEnvmapImage(const std::string &path, int &w, int &h);
 
 }  // namespace merhost
 
 extern "C" {
 /* C entry points of libmer_host.so for non-C++ callers (tests): return 0 / 1, message via merhost_last_error() */
 const char *merhost_last_error(void);
+/* merhost::readEnvmapImage: *w, *h of the file; out = float[h][w][3] when not NULL (query the size first) */
+int merhost_read_envmap_image(const char *path, int32_t *w, int32_t *h, float *out);
 /* parse + validate only: fills the flat scene (volumes = 0 handles) and width/height/spp; out->emitters (several point or area emitters)
    points to storage of the library that stays valid until the next merhost_flatten_xml call */
 int merhost_flatten_xml(const char *path, const char *defines /* "k=v;k=v" */, mer_scene_desc *out, int32_t *spp);

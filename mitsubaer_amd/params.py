@@ -135,6 +135,7 @@ class SceneParams:
 EMITTER_POINT = 1
 EMITTER_AREA = 2
 EMITTER_SPOT = 3
+EMITTER_ENVMAP = 4
 MAX_EMITTERS = 32
 
 
@@ -179,6 +180,49 @@ def spot_emitter(to_world, intensity, cutoff_deg=20.0, beam_deg=None, weight=1.0
         raise ValueError(err)
     return {"type": EMITTER_SPOT, "to_world": to_world, "intensity": [float(v) for v in intensity],
             "cutoff_deg": float(cutoff_deg), "beam_deg": float(beam_deg), "sampling_weight": float(weight)}
+
+
+def envmap_error(image, to_world, scale, sampling_weight):
+    """why mer_render / mer_envmap_upload refuse an envmap emitter with these parameters (None: accepted).  The image checks are
+    configure()'s (src/emitters/envmap.cpp:260-320) on the half-rounded texels."""
+    import numpy as np
+    a = np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+        return "envmap emitter: the image must be float [height][width][3]"
+    if max(a.shape[0], a.shape[1]) > 0xFFFF:
+        return "Environment maps images must be smaller than 65536 pixels in width and height"
+    with np.errstate(over="ignore", invalid="ignore"):
+        h = a.astype(np.float32).astype(np.float16).astype(np.float32)
+        lum = h[..., 0] * np.float32(0.212671) + h[..., 1] * np.float32(0.715160) + h[..., 2] * np.float32(0.072169)
+    if not np.all(np.isfinite(lum)):
+        return "The environment map contains an invalid floating point value (nan/inf) -- giving up."
+    w = np.sin((np.arange(a.shape[0]) + 0.5) * np.pi / a.shape[0]).astype(np.float32)
+    if not float(np.sum(lum.sum(axis=1, dtype=np.float64) * w)) != 0:
+        return "The environment map is completely black -- this is not allowed."
+    if not (np.isfinite(float(scale)) and float(scale) >= 0):
+        return "envmap emitter: 'scale' must be finite and non-negative"
+    if not (np.isfinite(float(sampling_weight)) and float(sampling_weight) > 0):
+        return "samplingWeight must be positive"
+    m = np.asarray(to_world if to_world is not None else np.eye(4), np.float64)
+    if m.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(m)):
+        return "envmap emitter: 'toWorld' must be a finite 3x4 or 4x4 transform"
+    R = m[:3, :3].astype(np.float32).astype(np.float64)
+    if np.max(np.abs(R @ R.T - np.eye(3))) > 1e-5 or not np.linalg.det(R) > 0:
+        return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)"
+    return None
+
+
+def envmap_emitter(image, to_world=None, scale=1.0, sampling_weight=1.0):
+    """an entry of SceneParams.emitters: emitter `envmap` (src/emitters/envmap.cpp), the lat-long image float [height][width][3] (u = x
+    along atan2(v.x, -v.z), v = y from the +y pole), its `toWorld` (a rotation; the translation is ignored), `scale` and `samplingWeight`.
+    Context.upload_scene uploads the image (mer_envmap_upload).  The scene's env_radiance must be zero.  ValueError for what mer_render
+    refuses."""
+    import numpy as np
+    a = np.ascontiguousarray(np.asarray(image, np.float32))
+    err = envmap_error(a, to_world, scale, sampling_weight)
+    if err:
+        raise ValueError(err)
+    return {"type": EMITTER_ENVMAP, "image": a, "to_world": to_world, "scale": float(scale), "sampling_weight": float(sampling_weight)}
 
 
 def spot_position(e):

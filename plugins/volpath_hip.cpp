@@ -242,17 +242,33 @@ public:
         /* ---- medium, phase function, volumes */
         fillMedium(ctx, shape->getInteriorMedium(), d, volumes);
 
-        /* ---- emitters: constant environment, point and spot emitters and area emitters on rectangles.  One point and one area emitter at
-           most and no spot: the single-emitter fields of mer_scene_desc; otherwise the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
+        /* ---- emitters: constant environment or environment map, point and spot emitters and area emitters on rectangles.  One point and one
+           area emitter at most, no spot and no map: the single-emitter fields of mer_scene_desc; otherwise the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
+        std::vector<mer_emitter> list;
+        int npoint = 0, narea = 0, nspot = 0, nenv = 0;
         if (const Emitter *env = scene->getEnvironmentEmitter()) {
-            if (env->getClass()->getName() != "ConstantBackgroundEmitter") Log(EError, "volpath_hip: the environment emitter must be 'constant'");
-            const Spectrum L = env->evalEnvironment(RayDifferential(Point(0.0f), Vector(0, 0, 1), 0));
-            Float r, g, b; L.toLinearRGB(r, g, b);
-            d.env_radiance[0] = r; d.env_radiance[1] = g; d.env_radiance[2] = b;
+            if (env->getClass()->getName() == "EnvironmentMap") {
+                /* `envmap` (src/emitters/envmap.cpp): its level-0 image through getBitmap() (:647-649, the MIP map's top level), `scale` from its
+                   properties (cobject.h:77), its frame from the world transform; the handle joins the volumes that are destroyed below.
+                   Always a list entry. */
+                ref<Bitmap> bmp = env->getBitmap()->convert(Bitmap::ERGB, Bitmap::EFloat32);
+                const Vector2i sz = bmp->getSize();
+                mer_volume h = 0;
+                if (mer_multi_envmap_upload(ctx, sz.x, sz.y, bmp->getFloat32Data(), &h)) fail(ctx);
+                volumes.push_back(h);
+                const Matrix4x4 &M = env->getWorldTransform()->eval(0).getMatrix();
+                mer_emitter m; memset(&m, 0, sizeof(m));
+                m.type = MER_EMITTER_ENVMAP; m.sampling_weight = (float) env->getSamplingWeight();
+                m.envmap = h; m.env_scale = (float) env->getProperties().getFloat("scale", 1.0f);
+                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) m.to_world[4 * r + k] = (float) M.m[r][k];
+                list.push_back(m); ++nenv;
+            } else if (env->getClass()->getName() == "ConstantBackgroundEmitter") {
+                const Spectrum L = env->evalEnvironment(RayDifferential(Point(0.0f), Vector(0, 0, 1), 0));
+                Float r, g, b; L.toLinearRGB(r, g, b);
+                d.env_radiance[0] = r; d.env_radiance[1] = g; d.env_radiance[2] = b;
+            } else Log(EError, "volpath_hip: the environment emitter must be 'constant' or 'envmap'");
         }
         const ref_vector<Emitter> &emitters = scene->getEmitters();
-        std::vector<mer_emitter> list;
-        int npoint = 0, narea = 0, nspot = 0;
         for (size_t i = 0; i < emitters.size(); ++i) {
             const Emitter *e = emitters[i].get();
             if (e->isEnvironmentEmitter()) continue;
@@ -305,7 +321,7 @@ public:
             m.position[0] = pRec.p.x; m.position[1] = pRec.p.y; m.position[2] = pRec.p.z;
             list.push_back(m); ++npoint;
         }
-        if (npoint <= 1 && narea <= 1 && nspot == 0) {
+        if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0) {
             for (size_t i = 0; i < list.size(); ++i) {
                 const mer_emitter &m = list[i];
                 if (m.type == MER_EMITTER_AREA) {
