@@ -92,7 +92,7 @@ typedef struct {
 /* Flat scene: what Integrator::render() (include/mitsuba/render/integrator.h:74) sees through
    Scene/Sensor/Film/Medium/PhaseFunction/VolumeDataSource/Emitter objects. */
 typedef struct {
-    /* sensor `perspective` + film `hdrfilm` (src/sensors/perspective.cpp:130-158,247-269) */
+    /* sensor `perspective` + film `hdrfilm` (src/sensors/perspective.cpp:130-158,247-269); the other sensor kinds: `sensor` below */
     int32_t width, height;
     float   fov_x_deg, near_clip, far_clip;
     float   cam_to_world[12];       /* row-major 3x4, columns (left,newUp,dir,origin): Transform::lookAt */
@@ -176,6 +176,18 @@ typedef struct {
        against rectangles).  Rectangles are all-absorbing occluders: the nearest one ends a camera ray, look-up or escaping path; any one
        blocks the environment's luminaire sample; an area sample on rectangle k is blocked by every other rectangle in front of it. */
     const mer_emitter *emitters; int32_t n_emitters;
+    /* the sensor (src/sensors/): MER_SENSOR_PERSPECTIVE (0, the pinhole above), MER_SENSOR_ORTHOGRAPHIC (orthographic.cpp:107-155: parallel
+       rays, o = T (nearP.x, nearP.y, 0), d = normalize(T (0,0,1)), nearP = (1 - 2 sx, (1 - 2 sy) / aspect); mint = near_clip, maxt = far_clip,
+       not rescaled, as the reference has it), MER_SENSOR_THINLENS (thinlens.cpp:293-322: the pinhole with an aperture of world-space radius
+       aperture_radius focused at focus_distance) or MER_SENSOR_TELECENTRIC (telecentric.cpp:140-222: the orthographic view with an aperture
+       of radius aperture_radius / |T e_x| focused at focus_distance / |T e_z|).  T = cam_to_world; fov_x_deg is read by the two
+       perspective kinds only, and for the two parallel kinds the extent of the view is T's scale: cam_to_world may carry a non-uniform
+       scale for them; it must be invertible for every kind but the pinhole, which is not checked.  The two lens
+       kinds draw their aperture sample (nextSample2D, mapped by squareToUniformDiskConcentric) directly after the pixel sample
+       (src/librender/integrator.cpp:147-179, ENeedsApertureSample); the other two draw nothing more.  aperture_radius >= 0 (the XML
+       front end turns a thin lens's 0 into Epsilon as the reference does; here 0 is the pinhole's / orthographic ray on two more draws)
+       and focus_distance > 0 for the lens kinds; both are ignored otherwise.  sensor_reserved = 0.  All zero = the pinhole.  Placed before the rough_* fields: no padding. */
+    int32_t sensor; float aperture_radius, focus_distance; int32_t sensor_reserved;
     /* boundary_bsdf = MER_BSDF_HROUGHDIELECTRIC (src/bsdfs/hroughdielectric.cpp: microfacet dielectric whose eta is the RIF at the hit point,
        exterior index 1, eta taken as for hdielectric): MER_MICROFACET_* distribution, one isotropic roughness alpha (the XML default is 0.1;
        clamped to >= 1e-4 as src/bsdfs/microfacet.h:131-136), and visible-normal sampling (Heitz & d'Eon 2014) or the full distribution with
@@ -185,6 +197,7 @@ typedef struct {
     int32_t rough_distribution; float rough_alpha; int32_t rough_sample_visible;
 } mer_scene_desc;
 enum { MER_METHOD_WOODCOCK = 0, MER_METHOD_SIMPSON = 1 };
+enum { MER_SENSOR_PERSPECTIVE = 0, MER_SENSOR_ORTHOGRAPHIC = 1, MER_SENSOR_THINLENS = 2, MER_SENSOR_TELECENTRIC = 3 };
 enum { MER_BSDF_NULL = 0, MER_BSDF_HDIELECTRIC = 1, MER_BSDF_HROUGHDIELECTRIC = 2 };
 enum { MER_MICROFACET_BECKMANN = 0, MER_MICROFACET_GGX = 1, MER_MICROFACET_PHONG = 2 };   /* MicrofacetDistribution::EType order (microfacet.h) */
 enum { MER_MODULATION_NONE = 0, MER_MODULATION_SINE, MER_MODULATION_SQUARE, MER_MODULATION_HAMILTONIAN, MER_MODULATION_MSEQ,
@@ -352,6 +365,12 @@ int  mer_rough_dielectric_sample(mer_context *ctx, const mer_scene_desc *scene, 
                                  float *wo, float *weight, float *pdf);
 /* PerspectiveCamera::sampleRay (src/sensors/perspective.cpp:247-269) */
 int  mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, int64_t n, float *o, float *d);
+/* Sensor::sampleRay of the scene's sensor kind (perspective.cpp:247-269, orthographic.cpp:137-155, thinlens.cpp:293-322,
+   telecentric.cpp:195-222): pos2[2*i..] = the film position in pixels, aperture2[2*i..] = the aperture sample in [0,1)^2 (read by the two
+   lens kinds only; may be NULL for the other two); o, d [3*i..], mint, maxt [i].  The render kernels' own device function; for
+   MER_SENSOR_PERSPECTIVE o and d are those of mer_camera_rays bit for bit. */
+int  mer_sensor_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, const float *aperture2, int64_t n, float *o, float *d,
+                     float *mint, float *maxt);
 /* PathLengthSampler::correlationFunction for the scene's modulation (src/librender/pathlengthsampler.cpp:68-114) */
 int  mer_correlation(mer_context *ctx, const mer_scene_desc *scene, const float *path_length, int64_t n, float *out);
 /* per-path radiance Li of sample `sample_index` for every pixel: out[(y*w+x)*3] (no filter) */

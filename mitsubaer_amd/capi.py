@@ -23,7 +23,7 @@ SYMBOLS = [
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
     "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_envmap_upload", "mer_envmap_eval", "mer_envmap_sample", "mer_multi_envmap_upload", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
-    "mer_rough_dielectric_sample", "mer_camera_rays",
+    "mer_rough_dielectric_sample", "mer_camera_rays", "mer_sensor_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
@@ -88,6 +88,7 @@ class SceneDesc(C.Structure):
         ("method", C.c_int32), ("het_stepsize", C.c_float),
         ("area_to_world", C.c_float * 12), ("area_radiance", C.c_float * 3),
         ("emitters", C.POINTER(EmitterDesc)), ("n_emitters", C.c_int32),
+        ("sensor", C.c_int32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("sensor_reserved", C.c_int32),
         ("rough_distribution", C.c_int32), ("rough_alpha", C.c_float), ("rough_sample_visible", C.c_int32),
     ]
 
@@ -120,6 +121,23 @@ def _sdf_value(p, x):
                 w = (f[0] if dx else 1 - f[0]) * (f[1] if dy else 1 - f[1]) * (f[2] if dz else 1 - f[2])
                 v += w * g[i[2] + dz, i[1] + dy, i[0] + dx]
     return v
+
+
+def validate_sensor(p):
+    """The refusals of the sensor fields (mer_render / the host parser): MerError.  No GPU needed."""
+    if p.sensor not in (P.SENSOR_PERSPECTIVE, P.SENSOR_ORTHOGRAPHIC, P.SENSOR_THINLENS, P.SENSOR_TELECENTRIC):
+        raise MerError("sensor: unknown sensor kind (perspective, orthographic, thinlens, telecentric)")
+    if p.sensor == P.SENSOR_PERSPECTIVE:
+        return
+    m = np.asarray(p.cam_to_world, np.float64)[:3, :3]
+    if not (np.all(np.isfinite(np.asarray(p.cam_to_world, np.float64))) and abs(np.linalg.det(m)) > 1e-12):
+        raise MerError("sensor: cam_to_world is singular")
+    if p.sensor == P.SENSOR_ORTHOGRAPHIC:
+        return
+    if not (np.isfinite(p.aperture_radius) and p.aperture_radius >= 0):
+        raise MerError("sensor: aperture_radius must be finite and non-negative")
+    if not (np.isfinite(p.focus_distance) and p.focus_distance > 0):
+        raise MerError("sensor: focus_distance must be finite and positive")
 
 
 def validate_rough(p):
@@ -421,6 +439,11 @@ class Context:
         s.fov_x_deg, s.near_clip, s.far_clip = p.fov_x_deg, p.near_clip, p.far_clip
         s.cam_to_world[:] = [float(v) for v in np.asarray(p.cam_to_world, np.float32).reshape(-1)]
         s.rfilter, s.rfilter_param = p.rfilter, p.rfilter_param
+        validate_sensor(p)
+        s.sensor = int(p.sensor); s.sensor_reserved = 0
+        lens = p.sensor in (P.SENSOR_THINLENS, P.SENSOR_TELECENTRIC)
+        s.aperture_radius = float(p.aperture_radius) if lens else 0.0
+        s.focus_distance = float(p.focus_distance) if lens else 0.0
         s.max_depth, s.rr_depth, s.hide_emitters = p.max_depth, p.rr_depth, int(p.hide_emitters)
         s.boundary = p.boundary
         s.bmin[:] = p.bmin; s.bmax[:] = p.bmax
@@ -675,6 +698,17 @@ class Context:
         o = np.empty((n, 3), np.float32); d = np.empty((n, 3), np.float32)
         self._check(self.lib.mer_camera_rays(self.h, C.byref(scene), _fp(pos2), C.c_int64(n), _fp(o), _fp(d)))
         return o, d
+
+    def sensor_rays(self, scene, pos2, aperture2=None):
+        """mer_sensor_rays: o, d, mint, maxt of the scene's sensor kind; aperture2 = the aperture samples (the two lens kinds need them)"""
+        pos2 = _f32(pos2); n = pos2.shape[0]
+        ap = None if aperture2 is None else _f32(aperture2)
+        if ap is not None and ap.shape != pos2.shape:
+            raise MerError("sensor_rays: one aperture sample per film position")
+        o = np.empty((n, 3), np.float32); d = np.empty((n, 3), np.float32); mint = np.empty(n, np.float32); maxt = np.empty(n, np.float32)
+        self._check(self.lib.mer_sensor_rays(self.h, C.byref(scene), _fp(pos2), _fp(ap) if ap is not None else None, C.c_int64(n),
+                                             _fp(o), _fp(d), _fp(mint), _fp(maxt)))
+        return o, d, mint, maxt
 
     def correlation(self, scene, path_length):
         t = _f32(path_length); n = t.shape[0]

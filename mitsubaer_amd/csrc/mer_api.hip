@@ -434,9 +434,31 @@ int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allo
     }
     if (sc->sigma_mode == MER_SIGMA_HOMOGENEOUS && !(sT[0] > 0 && sT[1] > 0 && sT[2] > 0) && sc->strategy == MER_STRATEGY_BALANCE)
         return fail(ctx, "homogeneous medium: sigmaT must be positive in every channel for the balance strategy");
-    for (int i = 0; i < 12; i++) P.cam[i] = sc->cam_to_world[i];
     P.aspect = (float) sc->width / (float) sc->height;
     P.cot_half_fov = 1.0f / std::tan((sc->fov_x_deg / 2.0f) * (MER_PI / 180.0f));
+    for (int i = 0; i < 3; i++) P.par_dir[i] = P.sensor_pad[i] = 0.0f;
+    P.lens_radius = P.lens_focus = 0.0f;
+    if (sc->sensor < MER_SENSOR_PERSPECTIVE || sc->sensor > MER_SENSOR_TELECENTRIC) return fail(ctx, "sensor: unknown sensor kind (perspective, orthographic, thinlens, telecentric)");
+    if (sc->sensor_reserved != 0) return fail(ctx, "sensor: sensor_reserved must be 0");
+    if (sc->sensor != MER_SENSOR_PERSPECTIVE) {
+        // what the sensors' constructors / configure() derive from toWorld (orthographic.cpp:133, telecentric.cpp:140-147), in float
+        const float *m = sc->cam_to_world;
+        bool finite = true;
+        for (int i = 0; i < 12; i++) finite = finite && std::isfinite(m[i]);
+        const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8])
+                         + (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
+        if (!finite || !(std::fabs(det) > 1e-12)) return fail(ctx, "sensor: cam_to_world is singular");
+        float len[3];
+        for (int c = 0; c < 3; c++) len[c] = std::sqrt(m[c] * m[c] + m[4 + c] * m[4 + c] + m[8 + c] * m[8 + c]);
+        for (int r = 0; r < 3; r++) P.par_dir[r] = m[4 * r + 2] / len[2];
+        if (sc->sensor != MER_SENSOR_ORTHOGRAPHIC) {
+            if (!(sc->aperture_radius >= 0) || !std::isfinite(sc->aperture_radius)) return fail(ctx, "sensor: aperture_radius must be finite and non-negative");
+            if (!(sc->focus_distance > 0) || !std::isfinite(sc->focus_distance)) return fail(ctx, "sensor: focus_distance must be finite and positive");
+            const bool tele = sc->sensor == MER_SENSOR_TELECENTRIC;
+            P.lens_radius = tele ? sc->aperture_radius / len[0] : sc->aperture_radius;
+            P.lens_focus = tele ? sc->focus_distance / len[2] : sc->focus_distance;
+        }
+    }
     P.inv_res_x = 1.0f / sc->width; P.inv_res_y = 1.0f / sc->height;
     if (sc->rfilter != MER_FILTER_BOX && sc->rfilter != MER_FILTER_GAUSSIAN) return fail(ctx, "unknown reconstruction filter");
     if (!(sc->rfilter_param > 0)) return fail(ctx, "reconstruction filter radius/stddev must be positive");
@@ -1361,6 +1383,23 @@ int mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float *
     HIP_CHECK(ctx, hipGetLastError());
     if (b.download(o, n * 12)) return 1;
     return c.download(d, n * 12);
+}
+int mer_sensor_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, const float *aperture2, int64_t n, float *o, float *d,
+                    float *mint, float *maxt) {
+    MER_USE_DEVICE(ctx);
+    Params P;
+    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST;
+    if (make_params(ctx, &sc, P)) return 1;
+    const bool lens = sc.sensor == MER_SENSOR_THINLENS || sc.sensor == MER_SENSOR_TELECENTRIC;
+    if (lens && !aperture2) return fail(ctx, "mer_sensor_rays: a thinlens / telecentric sensor needs the aperture samples");
+    DevBuf a(ctx), u(ctx), b(ctx), c(ctx), e(ctx), f(ctx);
+    if (a.upload(pos2, n * 8) || b.alloc(n * 12) || c.alloc(n * 12) || e.alloc(n * 4) || f.alloc(n * 4)) return 1;
+    if (lens && u.upload(aperture2, n * 8)) return 1;
+    hipLaunchKernelGGL(sensor_rays_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<float>(), lens ? u.as<float>() : (const float *) nullptr, n,
+                       b.as<float>(), c.as<float>(), e.as<float>(), f.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    if (b.download(o, n * 12) || c.download(d, n * 12) || e.download(mint, n * 4)) return 1;
+    return f.download(maxt, n * 4);
 }
 int mer_correlation(mer_context *ctx, const mer_scene_desc *scene, const float *path_length, int64_t n, float *out) {
     MER_USE_DEVICE(ctx);

@@ -727,7 +727,12 @@ struct Params {
     MaxExp maxexp;                      // strategy = maximum
     float inv_max_density;
     float het_step;               // method = simpson: the heterogeneous medium's stepSize (given, or inferred from the grids)
-    float cam[12], aspect, cot_half_fov, inv_res_x, inv_res_y;
+    // sensor: the camera-to-world matrix is sc.cam_to_world.  par_dir = normalize(T e_z) (the parallel kinds' ray direction), lens_radius =
+    // apertureRadius (thinlens) or apertureRadius / |T e_x| (telecentric), lens_focus = focusDistance or focusDistance / |T e_z| -- what the
+    // reference's constructors / configure() precompute (make_params).  These 40 bytes and the 16 the sensor fields add to sc take the
+    // place of a 56-byte copy of the matrix: Params keeps its size
+    float aspect, cot_half_fov, par_dir[3], lens_radius, lens_focus, sensor_pad[3];
+    float inv_res_x, inv_res_y;
     const float *ftable;                // reconstruction-filter table, 33 floats in device memory: a table INSIDE this struct, indexed per lane, makes the
                                         // compiler copy the whole 2.3 KB kernel-argument struct into scratch (K_connect, the EXTRA K_event)
     float fradius, fscale;
@@ -811,16 +816,80 @@ __device__ __forceinline__ float intersect_shape(const mer_scene_desc &s, f3 o, 
 // PerspectiveCamera::sampleRay (src/sensors/perspective.cpp:247-269) with the analytic inverse of
 // cameraToSample at the near plane (perspective.cpp:150-155, transform.cpp:99-123)
 __device__ __forceinline__ void sample_ray(const Params &P, float px, float py, f3 &o, f3 &d, float &mint, float &maxt) {
+    const float *cam = P.sc.cam_to_world;
     const float sx = px * P.inv_res_x, sy = py * P.inv_res_y;
     const f3 nearP((1.0f - 2.0f * sx) * P.sc.near_clip / P.cot_half_fov,
                    (1.0f - 2.0f * sy) / P.aspect * P.sc.near_clip / P.cot_half_fov, P.sc.near_clip);
     const f3 dl = normalize(nearP);
     const float invZ = 1.0f / dl.z;
     mint = P.sc.near_clip * invZ; maxt = P.sc.far_clip * invZ;
-    o = f3(P.cam[3], P.cam[7], P.cam[11]);
-    d = f3(P.cam[0] * dl.x + P.cam[1] * dl.y + P.cam[2] * dl.z,
-           P.cam[4] * dl.x + P.cam[5] * dl.y + P.cam[6] * dl.z,
-           P.cam[8] * dl.x + P.cam[9] * dl.y + P.cam[10] * dl.z);
+    o = f3(cam[3], cam[7], cam[11]);
+    d = f3(cam[0] * dl.x + cam[1] * dl.y + cam[2] * dl.z,
+           cam[4] * dl.x + cam[5] * dl.y + cam[6] * dl.z,
+           cam[8] * dl.x + cam[9] * dl.y + cam[10] * dl.z);
+}
+
+// warp::squareToUniformDiskConcentric (src/libcore/warp.cpp:81-100)
+__device__ __forceinline__ void square_to_disk_concentric(float u1, float u2, float &x, float &y) {
+    const float r1 = 2.0f * u1 - 1.0f, r2 = 2.0f * u2 - 1.0f;
+    float phi, r;                                                   // phi in units of pi: sincospif reduces its argument exactly, without sincosf's large-argument path
+    if (r1 == 0 && r2 == 0) { r = phi = 0; }
+    else if (r1 * r1 > r2 * r2) { r = r1; phi = 0.25f * (r2 / r1); }
+    else { r = r2; phi = 0.5f - (r1 / r2) * 0.25f; }
+    float sinPhi, cosPhi;
+    sincospif(phi, &sinPhi, &cosPhi);
+    x = r * cosPhi; y = r * sinPhi;
+}
+
+// Sensor::sampleRay of the other three projective sensors (P.sc.sensor: a scene constant, so the switch is wave-uniform): `orthographic`
+// (src/sensors/orthographic.cpp:137-155), `thinlens` (thinlens.cpp:293-322), `telecentric` (telecentric.cpp:195-222).  (u1, u2) = the
+// aperture sample, read by the two lens kinds.  mint / maxt of the parallel kinds are the clip distances, not rescaled: the reference's.
+__device__ __forceinline__ void sample_ray_sensor(const Params &P, float px, float py, float u1, float u2, f3 &o, f3 &d, float &mint, float &maxt) {
+    const float *cam = P.sc.cam_to_world;
+    const float sx = px * P.inv_res_x, sy = py * P.inv_res_y;
+    f3 orig, dl;                                                    // camera space
+    if (P.sc.sensor == MER_SENSOR_THINLENS) {
+        const f3 nearP((1.0f - 2.0f * sx) * P.sc.near_clip / P.cot_half_fov,
+                       (1.0f - 2.0f * sy) / P.aspect * P.sc.near_clip / P.cot_half_fov, P.sc.near_clip);
+        float ax, ay;
+        square_to_disk_concentric(u1, u2, ax, ay);
+        orig = f3(ax * P.lens_radius, ay * P.lens_radius, 0.0f);    // apertureP
+        const f3 focusP = nearP * (P.lens_focus / nearP.z);
+        dl = normalize(focusP - orig);
+        const float invZ = 1.0f / dl.z;
+        mint = P.sc.near_clip * invZ; maxt = P.sc.far_clip * invZ;
+    } else {
+        const float nx = 1.0f - 2.0f * sx, ny = (1.0f - 2.0f * sy) / P.aspect;     // sampleToCamera (sx, sy, 0): orthographic.cpp:107-114
+        mint = P.sc.near_clip; maxt = P.sc.far_clip;
+        if (P.sc.sensor == MER_SENSOR_TELECENTRIC) {
+            float ax, ay;
+            square_to_disk_concentric(u1, u2, ax, ay);
+            ax *= P.lens_radius; ay *= P.lens_radius;               // diskSample
+            orig = f3(ax + nx, ay + ny, 0.0f);
+            dl = f3(-ax, -ay, P.lens_focus);                        // focusP - orig
+        } else {
+            o = f3(cam[0] * nx + cam[1] * ny + cam[3], cam[4] * nx + cam[5] * ny + cam[7], cam[8] * nx + cam[9] * ny + cam[11]);
+            d = f3(P.par_dir[0], P.par_dir[1], P.par_dir[2]);
+            return;
+        }
+    }
+    o = f3(cam[0] * orig.x + cam[1] * orig.y + cam[3], cam[4] * orig.x + cam[5] * orig.y + cam[7], cam[8] * orig.x + cam[9] * orig.y + cam[11]);
+    d = f3(cam[0] * dl.x + cam[1] * dl.y + cam[2] * dl.z,
+           cam[4] * dl.x + cam[5] * dl.y + cam[6] * dl.z,
+           cam[8] * dl.x + cam[9] * dl.y + cam[10] * dl.z);
+    if (P.sc.sensor == MER_SENSOR_TELECENTRIC) d = normalize(d);
+}
+
+// The primary ray of a path (SamplingIntegrator::renderBlock, src/librender/integrator.cpp:147-179): a sensor with ENeedsApertureSample --
+// `thinlens`, `telecentric` -- draws nextSample2D() directly after the pixel sample, the other two draw nothing.  The three kinds beside the
+// pinhole live in the EXTRA kernels (mer_render selects them for such a scene): the others keep their code and registers.
+template <bool EXTRA, class RNG>
+__device__ __forceinline__ void primary_ray(const Params &P, RNG &rng, float px, float py, f3 &o, f3 &d, float &mint, float &maxt) {
+    if (EXTRA && P.sc.sensor != MER_SENSOR_PERSPECTIVE) {
+        float u1 = 0.5f, u2 = 0.5f;
+        if (P.sc.sensor != MER_SENSOR_ORTHOGRAPHIC) { u1 = rng.next1D(); u2 = rng.next1D(); }
+        sample_ray_sensor(P, px, py, u1, u2, o, d, mint, maxt);
+    } else sample_ray(P, px, py, o, d, mint, maxt);
 }
 
 __device__ __forceinline__ f3 albedo_at(const Params &P, f3 p) {

@@ -199,6 +199,16 @@ __global__ void camera_rays_kernel(const Params P, const float *pos2, int64_t n,
     sample_ray(P, pos2[2 * i], pos2[2 * i + 1], oo, dd, a, b);
     o[3 * i] = oo.x; o[3 * i + 1] = oo.y; o[3 * i + 2] = oo.z; d[3 * i] = dd.x; d[3 * i + 1] = dd.y; d[3 * i + 2] = dd.z;
 }
+// mer_sensor_rays: the four-way sensor the EXTRA render kernels start their paths with
+__global__ void sensor_rays_kernel(const Params P, const float *pos2, const float *ap2, int64_t n, float *o, float *d, float *mint, float *maxt) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 oo, dd; float a, b;
+    if (P.sc.sensor == MER_SENSOR_PERSPECTIVE) sample_ray(P, pos2[2 * i], pos2[2 * i + 1], oo, dd, a, b);
+    else sample_ray_sensor(P, pos2[2 * i], pos2[2 * i + 1], ap2 ? ap2[2 * i] : 0.5f, ap2 ? ap2[2 * i + 1] : 0.5f, oo, dd, a, b);
+    o[3 * i] = oo.x; o[3 * i + 1] = oo.y; o[3 * i + 2] = oo.z; d[3 * i] = dd.x; d[3 * i + 1] = dd.y; d[3 * i + 2] = dd.z;
+    mint[i] = a; maxt[i] = b;
+}
 __global__ void correlation_kernel(const Params P, const float *t, int64_t n, float *out) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

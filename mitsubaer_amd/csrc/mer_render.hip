@@ -134,10 +134,11 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
 
     const bool has_point = P.n_point > 0;            // the legacy point / area fields or the emitter list (make_params)
     const bool curved = scene->rif_mode != MER_RIF_CONST;
-    // EXTRA kernels carry the point emitter, the envmap, the modulated film and the dielectric boundary; the signed-distance boundary exists in
+    // EXTRA kernels carry the point emitter, the envmap, the modulated film, the dielectric boundary and the sensors beside the pinhole; the signed-distance boundary exists in
     // the EXTRA kernels only
     const bool has_area = P.n_rect > 0;
-    const bool extra = scene->boundary == MER_BOUNDARY_SDF || has_point || has_area || P.has_envmap || scene->modulation != MER_MODULATION_NONE || scene->boundary_bsdf != MER_BSDF_NULL;
+    const bool extra = scene->boundary == MER_BOUNDARY_SDF || has_point || has_area || P.has_envmap || scene->modulation != MER_MODULATION_NONE || scene->boundary_bsdf != MER_BSDF_NULL
+                       || scene->sensor != MER_SENSOR_PERSPECTIVE;       // the other three sensor kinds start their paths in the EXTRA kernels (primary_ray)
     KernelSet ks{};
     if (!pick_kernels(ctx, scene, extra, ks)) {
         if (scene->boundary == MER_BOUNDARY_SDF && curved) return fail(ctx, "signed-distance boundary: no kernel for this RIF layout (MER_LAYOUT_BRICK125 is not built with it)");

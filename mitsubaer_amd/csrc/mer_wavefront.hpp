@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                 const float sx = rng.next1D(), sy = rng.next1D();
                 const float px = (float) x + sx, py = (float) y + sy;
                 f3 o, d; float mint, maxt;
-                sample_ray(P, px, py, o, d, mint, maxt);
+                primary_ray<EXTRA>(P, rng, px, py, o, d, mint, maxt);
                 f3 L(0, 0, 0);
                 float plen = 0.0f;                                   // transient film: optical path length so far
                 const float itsT = intersect_shape_b<BND>(P, o, d, mint, maxt);
@@ -680,7 +680,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             const float sx = rng.next1D(), sy = rng.next1D();
             px = (float) px_i + sx; py = (float) py_i + sy;
             f3 o, d; float mint, maxt;
-            sample_ray(P, px, py, o, d, mint, maxt);
+            primary_ray<EXTRA>(P, rng, px, py, o, d, mint, maxt);
             L = f3(0, 0, 0); T = f3(1, 1, 1); depth = 1; flags = F_EMITTED;
             plen = 0.0f; trOpt = 0.0f; etaPath = 1.0f;
             C.paths++;

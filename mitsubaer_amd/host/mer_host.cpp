@@ -375,13 +375,40 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
         } else Log_EError("shape \"" + type + "\" is not supported on the GPU path (cube, sphere, obj bounding box; rectangle with an area emitter)");
         out = o;
     } else if (tag == "sensor") {
-        if (type != "perspective") Log_EError("sensor \"" + type + "\" is not supported on the GPU path (perspective)");
         auto o = std::make_shared<Sensor>();
-        if (props.hasProperty("focalLength")) Log_EError("Please specify either a focal length ('focalLength') or a field of view ('fov')!");
-        o->fov = props.getFloat("fov", 50.0f); o->fovAxis = lower(props.getString("fovAxis", "x"));
+        if (type == "perspective") o->kind = MER_SENSOR_PERSPECTIVE;
+        else if (type == "orthographic") o->kind = MER_SENSOR_ORTHOGRAPHIC;
+        else if (type == "thinlens") o->kind = MER_SENSOR_THINLENS;
+        else if (type == "telecentric") o->kind = MER_SENSOR_TELECENTRIC;
+        else Log_EError("sensor \"" + type + "\" is not supported on the GPU path (perspective, orthographic, thinlens, telecentric)");
+        const bool persp = o->kind == MER_SENSOR_PERSPECTIVE || o->kind == MER_SENSOR_THINLENS;
+        if (persp) {                                                                                     // perspective.cpp / sensor.cpp:225-260; the parallel kinds have no fov
+            if (props.hasProperty("focalLength")) Log_EError("Please specify either a focal length ('focalLength') or a field of view ('fov')!");
+            o->fov = props.getFloat("fov", 50.0f); o->fovAxis = lower(props.getString("fovAxis", "x"));
+        }
         o->nearClip = props.getFloat("nearClip", 1e-2f); o->farClip = props.getFloat("farClip", 1e4f);
-        (void) props.getFloat("focusDistance", 0.0f);
+        if (o->kind != MER_SENSOR_PERSPECTIVE) {                                                         // sensor.cpp:165-169 (the pinhole keeps what it accepted)
+            if (o->nearClip <= 0) Log_EError("The 'nearClip' parameter must be greater than zero!");
+            if (o->nearClip >= o->farClip) Log_EError("The 'nearClip' parameter must be smaller than 'farClip'.");
+        }
+        o->focusDistance = props.getFloat("focusDistance", o->farClip);                                  // sensor.cpp:162
+        if (o->kind == MER_SENSOR_THINLENS) {
+            o->apertureRadius = props.getFloat("apertureRadius");                                        // required: thinlens.cpp:132
+            if (o->apertureRadius == 0) {                                                                // :134-137
+                std::fprintf(stderr, "WARN: Can't have a zero aperture radius -- setting to %f\n", 1e-4f);
+                o->apertureRadius = 1e-4f;
+            }
+        } else if (o->kind == MER_SENSOR_TELECENTRIC) o->apertureRadius = props.getFloat("apertureRadius", 0.0f);    // telecentric.cpp:81
+        if (o->apertureRadius < 0) Log_EError("sensor \"" + type + "\": 'apertureRadius' must not be negative");
+        if ((o->kind == MER_SENSOR_THINLENS || o->kind == MER_SENSOR_TELECENTRIC) && !(o->focusDistance > 0))
+            Log_EError("sensor \"" + type + "\": 'focusDistance' must be positive");
         props.getTransform("toWorld", o->toWorld);
+        if (o->kind != MER_SENSOR_PERSPECTIVE) {
+            const float *m = o->toWorld;
+            const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8])
+                             + (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
+            if (!std::isfinite(det) || !(std::fabs(det) > 1e-12)) Log_EError("sensor \"" + type + "\": the 'toWorld' transformation is singular");
+        }
         out = o;
     } else if (tag == "film") {
         auto o = std::make_shared<Film>();
@@ -761,6 +788,9 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     else if (axis == "y") d.fov_x_deg = (float) (2.0 * std::atan(std::tan(0.5 * se.fov * M_PI / 180.0) * aspect) * 180.0 / M_PI);
     else Log_EError("The 'fovAxis' parameter must be set to one of 'smaller', 'larger', 'diagonal', 'x', or 'y'!");
     d.near_clip = se.nearClip; d.far_clip = se.farClip;
+    d.sensor = se.kind; d.sensor_reserved = 0;
+    const bool lens = se.kind == MER_SENSOR_THINLENS || se.kind == MER_SENSOR_TELECENTRIC;
+    d.aperture_radius = lens ? se.apertureRadius : 0.0f; d.focus_distance = lens ? se.focusDistance : 0.0f;
     for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) d.cam_to_world[r * 4 + c] = se.toWorld[r * 4 + c];
     d.rfilter = fi.rfilter->kind; d.rfilter_param = fi.rfilter->param;
     d.max_depth = maxDepth; d.rr_depth = rrDepth; d.hide_emitters = hideEmitters;

@@ -8,7 +8,7 @@
 //   PhaseFunction         hg | isotropic                             include/mitsuba/render/phase.h:117-241
 //   Medium                homogeneous | heterogeneous | heterogeneousrefractive   include/mitsuba/render/medium.h:113-234
 //   Shape                 cube | sphere | obj (bounding box), `interior` medium, null BSDF   src/librender/shape.cpp:48-70,166-190
-//   Sensor / Film / ReconstructionFilter / Sampler      perspective, hdrfilm, gaussian | box, independent | ldsampler
+//   Sensor / Film / ReconstructionFilter / Sampler      perspective | orthographic | thinlens | telecentric, hdrfilm, gaussian | box, independent | ldsampler
 //   Emitter               constant | point | area (on a rectangle shape)
 //   Integrator            volpath -> render() flattens the scene to mer_scene_desc and calls mer_render
 //   SceneHandler          scene-XML subset with $param substitution    src/librender/scenehandler.cpp, src/mitsuba/mitsuba.cpp:58,168-173
@@ -177,6 +177,8 @@ public:
     const char *getClassName() const override { return "Sensor"; }
     void addChild(const std::string &name, ObjRef child) override;
     float fov = 50.0f; std::string fovAxis = "x"; float nearClip = 1e-2f, farClip = 1e4f;
+    int kind = MER_SENSOR_PERSPECTIVE;          // perspective | orthographic | thinlens | telecentric (src/sensors/)
+    float apertureRadius = 0.0f, focusDistance = 1e4f;   // the lens kinds: world-space radius (thinlens.cpp:132, telecentric.cpp:81), `focusDistance` (sensor.cpp:162: farClip)
     float toWorld[16];
     std::shared_ptr<Film> film; std::shared_ptr<Sampler> sampler;
 };

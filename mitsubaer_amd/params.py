@@ -2,7 +2,8 @@
 
 Vocabulary follows the reference's plugins: a `heterogeneous` /
 `homogeneous` / `heterogeneousrefractive` medium with `density` / `albedo` / `rif` volumes,
-an `hg` / `isotropic` phase function, a `perspective` sensor with an `hdrfilm`, a
+an `hg` / `isotropic` phase function, a `perspective` (or `orthographic` / `thinlens` /
+`telecentric`) sensor with an `hdrfilm`, a
 `volpath` integrator and a `constant` environment emitter.
 """
 import numpy as np
@@ -23,6 +24,7 @@ DECOMPOSITION_NONE, DECOMPOSITION_TRANSIENT, DECOMPOSITION_BOUNCE = 0, 1, 2
 METHOD_WOODCOCK, METHOD_SIMPSON = 0, 1
 BSDF_NULL, BSDF_HDIELECTRIC, BSDF_HROUGHDIELECTRIC = 0, 1, 2
 MICROFACET_BECKMANN, MICROFACET_GGX, MICROFACET_PHONG = 0, 1, 2
+SENSOR_PERSPECTIVE, SENSOR_ORTHOGRAPHIC, SENSOR_THINLENS, SENSOR_TELECENTRIC = 0, 1, 2, 3      # src/sensors/: the projective family
 MODULATION_NONE, MODULATION_SINE, MODULATION_SQUARE, MODULATION_HAMILTONIAN, MODULATION_MSEQ, MODULATION_DEPTHSELECTIVE = 0, 1, 2, 3, 4, 5
 
 
@@ -69,6 +71,10 @@ class SceneParams:
         self.width = 512; self.height = 512
         self.fov_x_deg = 95.8402; self.near_clip = 1e-2; self.far_clip = 1e4
         self.cam_to_world = look_at([-3, 0, 0], [-2, 0, 0], [0, 1, 0])
+        # the sensor kind (SENSOR_*): orthographic / telecentric take the extent of their view from the scale in cam_to_world; thinlens and
+        # telecentric have a world-space aperture_radius and a focus_distance (`apertureRadius`, `focusDistance`) and draw an aperture sample
+        # after the pixel sample.  The defaults are the pinhole
+        self.sensor = SENSOR_PERSPECTIVE; self.aperture_radius = 0.0; self.focus_distance = 0.0
         self.rfilter = FILTER_GAUSSIAN; self.rfilter_param = 0.5
         # integrator volpath (src/librender/integrator.cpp:190-225)
         self.max_depth = -1; self.rr_depth = 5; self.hide_emitters = False

@@ -153,14 +153,28 @@ public:
         mer_scene_desc d; memset(&d, 0, sizeof(d));
         std::vector<mer_volume> volumes;
 
-        /* ---- sensor + film (src/sensors/perspective.cpp:130-158, src/librender/film.cpp) */
+        /* ---- sensor + film (src/sensors/{perspective,orthographic,thinlens,telecentric}.cpp, src/librender/film.cpp).  The lens classes keep
+           m_apertureRadius private: it is read back from the Properties the sensor was made from (ConfigurableObject::getProperties), with the
+           constructors' own defaults and the thin lens's Epsilon rule (thinlens.cpp:132-137, telecentric.cpp:81) */
         const Sensor *sensor = scene->getSensor();
-        if (sensor->getClass()->getName() != "PerspectiveCamera") Log(EError, "volpath_hip: the sensor must be 'perspective'");
-        const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor);
+        const std::string sensorClass = sensor->getClass()->getName();
+        if (sensorClass == "PerspectiveCamera") d.sensor = MER_SENSOR_PERSPECTIVE;
+        else if (sensorClass == "OrthographicCamera") d.sensor = MER_SENSOR_ORTHOGRAPHIC;
+        else if (sensorClass == "ThinLens") d.sensor = MER_SENSOR_THINLENS;
+        else if (sensorClass == "TelecentricLensCamera") d.sensor = MER_SENSOR_TELECENTRIC;
+        else Log(EError, "volpath_hip: the sensor must be 'perspective', 'orthographic', 'thinlens' or 'telecentric' (got %s)", sensorClass.c_str());
+        const ProjectiveCamera *cam = static_cast<const ProjectiveCamera *>(sensor);
+        d.sensor_reserved = 0; d.aperture_radius = 0; d.focus_distance = 0;
+        if (d.sensor == MER_SENSOR_THINLENS || d.sensor == MER_SENSOR_TELECENTRIC) {
+            d.aperture_radius = (float) sensor->getProperties().getFloat("apertureRadius", 0.0f);
+            if (d.sensor == MER_SENSOR_THINLENS && d.aperture_radius == 0) d.aperture_radius = (float) Epsilon;
+            d.focus_distance = (float) cam->getFocusDistance();
+        }
         Film *film = const_cast<Film *>(sensor->getFilm());
         d.width = film->getCropSize().x; d.height = film->getCropSize().y;
         if (film->getCropSize() != film->getSize()) Log(EError, "volpath_hip: crop windows are not supported");
-        d.fov_x_deg = cam->getXFov(); d.near_clip = cam->getNearClip(); d.far_clip = cam->getFarClip();
+        d.fov_x_deg = (d.sensor == MER_SENSOR_PERSPECTIVE || d.sensor == MER_SENSOR_THINLENS) ? static_cast<const PerspectiveCamera *>(sensor)->getXFov() : 0.0f;
+        d.near_clip = cam->getNearClip(); d.far_clip = cam->getFarClip();
         const Matrix4x4 &tw = cam->getWorldTransform(0).getMatrix();
         for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) d.cam_to_world[4 * r + c] = (float) tw(r, c);
         const ReconstructionFilter *rf = film->getReconstructionFilter();
