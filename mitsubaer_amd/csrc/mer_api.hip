@@ -1,4 +1,5 @@
-// mer_api.hip -- libmer.so: C-ABI (include/mer.h) over the gfx950 kernels in mer_kernels.hpp.
+// mer_api.hip -- libmer.so: C-ABI (include/mer.h) over the gfx950 kernels in mer_kernels.hpp: the context and its options, volumes,
+// envmap upload, film, render entry points and the leaf calls.  A scene becomes kernel arguments in mer_scene.hip (make_params).
 // Host side is plain HIP runtime: device memory, one stream, HIP events.  No CPU compute path exists:
 // every entry point that computes launches a kernel, and fails loudly when no device is present.
 #include "mer_internal.hpp"
@@ -7,6 +8,7 @@
 #include "mer_kernels.hpp"
 #include <algorithm>
 #include <functional>
+#include <utility>
 
 using namespace mer;
 
@@ -14,576 +16,12 @@ namespace { thread_local std::string g_create_error; }
 
 namespace mer {
 
-// worldToGrid = scale((res-1)/extents) * translate(-min) * toWorld^-1 with toWorld = identity
-// (GridDataSource::configure, src/volume/gridvolume.cpp:188-195).  Float arithmetic as in the reference.
-void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g) {
-    std::memset(&g, 0, sizeof(g));
-    g.data = v.dense; g.cell8 = v.cell8; g.coeff = v.coeff;
-    g.layout = v.cell8 ? v.layout : MER_LAYOUT_DENSE;
-    g.channels = v.desc.channels; g.dtype = v.desc.dtype;
-    const bool brick = v.cell8 && (v.layout == MER_LAYOUT_BRICK27 || v.layout == MER_LAYOUT_BRICK125);
-    g.bshift = v.layout == MER_LAYOUT_BRICK125 ? 2 : 1; g.bw = (1 << g.bshift) + 1; g.recw = v.layout == MER_LAYOUT_BRICK125 ? 128 : 32;
-    const int bc = 1 << g.bshift;                                       // ceil((res-1)/bc) bricks per axis
-    g.nbx = (v.desc.res[0] - 2) / bc + 1; g.nby = (v.desc.res[1] - 2) / bc + 1;
-    {
-        const uint64_t bytes = !v.cell8 ? (uint64_t) v.bytes_dense
-                             : brick ? (uint64_t) g.nbx * g.nby * ((v.desc.res[2] - 2) / bc + 1) * (uint64_t) g.recw * 4ull
-                             : (uint64_t) (v.desc.res[0] - 1) * (v.desc.res[1] - 1) * (v.desc.res[2] - 1) * 32ull;
-        g.buf_bytes = bytes < 0xFFFFFFFFull && ctx->opt.buffer_loads ? (uint32_t) bytes : 0u;
-        g.n_record = v.cell8 ? bytes / 4 : 0;
-        g.n_dense = (uint64_t) v.desc.res[0] * v.desc.res[1] * v.desc.res[2] * (uint64_t) v.desc.channels;
-        g.chk = ctx->chk;
-    }
-    // worldToVolume: the desc's matrix, all zeros = identity
-    float W[12]; bool zero = true;
-    for (int i = 0; i < 12; i++) { W[i] = v.desc.world_to_volume[i]; zero = zero && W[i] == 0.0f; }
-    if (zero) for (int i = 0; i < 12; i++) W[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    g.affine = 0;
-    for (int i = 0; i < 12; i++) { g.w2v[i] = W[i]; if (W[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) g.affine = 1; }
-    for (int i = 0; i < 3; i++) {
-        g.res[i] = v.desc.res[i];
-        g.bmin[i] = v.desc.aabb_min[i]; g.bmax[i] = v.desc.aabb_max[i];
-        const float extent = g.bmax[i] - g.bmin[i];
-        const float s = (float) (g.res[i] - 1) / extent;
-        g.s[i] = s;
-        g.t[i] = s * (-g.bmin[i]);
-        // (scale * translate) * worldToVolume as Mitsuba's 4x4 product forms it (src/libcore/transform.cpp operator*): row i of the
-        // left factor is (s_i e_i, s_i * (-min_i)); the zero terms of the sums add exactly nothing
-        for (int j = 0; j < 3; j++) g.m[i * 4 + j] = s * W[i * 4 + j];
-        g.m[i * 4 + 3] = s * W[i * 4 + 3] + g.t[i];
-        // SplineDataSource interpolatable limits (src/volume/splinevolume.cpp:280-281): stride = 1/xres
-        const float stride = (float) (1.0 / s);
-        g.lim_min[i] = g.bmin[i] + (2.0f * stride + MER_EPSILON);
-        g.lim_max[i] = g.bmax[i] + (-2.0f * stride - MER_EPSILON);
-    }
-    {   // m_aabb: bounding box of the data box's corners under volumeToWorld (gridvolume.cpp:199-203); volumeToWorld = W^-1 by cofactors
-        // in double (the oracle forms it with the same expressions)
-        const double a = W[0], b = W[1], c = W[2], d = W[4], e = W[5], f = W[6], gg = W[8], h = W[9], k = W[10];
-        const double det = a * (e * k - f * h) - b * (d * k - f * gg) + c * (d * h - e * gg);
-        const double inv[9] = {(e * k - f * h) / det, (c * h - b * k) / det, (b * f - c * e) / det,
-                               (f * gg - d * k) / det, (a * k - c * gg) / det, (c * d - a * f) / det,
-                               (d * h - e * gg) / det, (b * gg - a * h) / det, (a * e - b * d) / det};
-        for (int i = 0; i < 3; i++) { g.wmin[i] = std::numeric_limits<float>::infinity(); g.wmax[i] = -std::numeric_limits<float>::infinity(); }
-        for (int corner = 0; corner < 8; corner++) {
-            const double q[3] = {((corner & 1) ? g.bmax[0] : g.bmin[0]) - (double) W[3], ((corner & 2) ? g.bmax[1] : g.bmin[1]) - (double) W[7],
-                                 ((corner & 4) ? g.bmax[2] : g.bmin[2]) - (double) W[11]};
-            for (int i = 0; i < 3; i++) {
-                const float w = (float) (inv[i * 3] * q[0] + inv[i * 3 + 1] * q[1] + inv[i * 3 + 2] * q[2]);
-                g.wmin[i] = std::min(g.wmin[i], w); g.wmax[i] = std::max(g.wmax[i], w);
-            }
-        }
-    }
-}
-
-static void filter_table(int kind, float param, float *values, float &radius, float &scale) {
-    // ReconstructionFilter::configure (src/libcore/rfilter.cpp:40-55), MTS_FILTER_RESOLUTION = 31
-    const int RES = 31;
-    radius = kind == MER_FILTER_BOX ? param + 1e-5f : 4 * param;      // box.cpp:39, gaussian.cpp:42
-    float sum = 0.0f;
-    for (int i = 0; i < RES; ++i) {
-        const float x = (radius * i) / RES;
-        float v;
-        if (kind == MER_FILTER_BOX) v = std::fabs(x) <= radius ? 1.0f : 0.0f;
-        else {
-            const float alpha = -1.0f / (2.0f * param * param);
-            v = std::max(0.0f, std::exp(alpha * x * x) - std::exp(alpha * radius * radius));
-        }
-        values[i] = v; sum += v;
-    }
-    values[RES] = 0.0f; values[RES + 1] = 0.0f;
-    scale = RES / radius;
-    sum *= 2 * radius / RES;
-    const float normalization = 1.0f / sum;
-    for (int i = 0; i < RES; ++i) values[i] *= normalization;
-}
-
-// Validate the scene the way the reference plugins' constructors / configure() do, and flatten it.
-static int film_frames(mer_context *ctx, const mer_scene_desc *sc, int &frames) {
-    frames = 1;
-    if (sc->modulation < MER_MODULATION_NONE || sc->modulation > MER_MODULATION_DEPTHSELECTIVE)            // pathlengthsampler.cpp:33-35
-        return fail(ctx, "The \"modulation\" parameter must be equal toeither \"none\", \"square\", or \"hamiltonian\", or \"mseq\", or \"depthselective\"!");
-    if (sc->modulation != MER_MODULATION_NONE && sc->decomposition != MER_DECOMPOSITION_TRANSIENT)
-        return fail(ctx, "film: a path-length modulation needs decomposition = transient");
-    if (sc->modulation != MER_MODULATION_NONE && (!(sc->mod_lambda > 0) || sc->mod_P < 1 || sc->mod_neighbors < 0))
-        return fail(ctx, "film: modulation needs lambda > 0, P >= 1, neighbors >= 0");
-    if (sc->decomposition == MER_DECOMPOSITION_NONE) return 0;
-    if (sc->decomposition == MER_DECOMPOSITION_TRANSIENT && sc->modulation != MER_MODULATION_NONE) return 0;  // film.cpp:76-78: one frame
-    if (sc->decomposition != MER_DECOMPOSITION_TRANSIENT && sc->decomposition != MER_DECOMPOSITION_BOUNCE)
-        return fail(ctx, "The \"decomposition\" parameter must be equal toeither \"none\", \"transient\", or \"bounce\"!");   // film.cpp:66-68
-    const float f = std::ceil((sc->max_bound - sc->min_bound) / sc->bin_width);                                               // film.cpp:74
-    if (!(f >= 1.0f) || f > 4096.0f) return fail(ctx, "film: a decomposition needs 1 <= ceil((maxBound-minBound)/binWidth) <= 4096 frames");
-    frames = (int) f;
-    return 0;
-}
-// the microfacet parameters of MER_BSDF_HROUGHDIELECTRIC (microfacet.h:100-142: one isotropic alpha, clamped to >= 1e-4 on the device)
-static int check_rough(mer_context *ctx, const mer_scene_desc *sc) {
-    if (sc->rough_distribution < MER_MICROFACET_BECKMANN || sc->rough_distribution > MER_MICROFACET_PHONG)
-        return fail(ctx, "hroughdielectric: distribution must be beckmann, ggx or phong");
-    if (!(sc->rough_alpha >= 0) || !std::isfinite(sc->rough_alpha)) return fail(ctx, "hroughdielectric: alpha must be finite and >= 0");
-    if (sc->rough_sample_visible != 0 && sc->rough_sample_visible != 1) return fail(ctx, "hroughdielectric: sampleVisible must be 0 or 1");
-    return 0;
-}
-// inside test of the cube / sphere medium shape (heterogeneousrefractive.cpp:707-726), as the host applies it to an emitter position
-static bool point_in_shape(const mer_scene_desc *sc, const float q[3]) {
-    if (sc->boundary == MER_BOUNDARY_AABB) { bool in = true; for (int i = 0; i < 3; i++) in = in && q[i] >= sc->bmin[i] && q[i] <= sc->bmax[i]; return in; }
-    if (sc->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (q[i] - sc->sph_center[i]) * (q[i] - sc->sph_center[i]); return d2 < sc->sph_radius * sc->sph_radius; }
-    return false;
-}
-
-// Rectangle::configure (src/shapes/rectangle.cpp:99-110): objectToWorld (row-major 3x4, also returned in M), its inverse, the frame normal
-// and 1 / area of the image of [-1,1]^2 x {0}.  Returns an error message or nullptr.
-static const char *rect_derive(const float to_world[12], DRect &R, double M[3][4]) {
-    double inv[3][3];
-    for (int i = 0; i < 12; i++) { R.o2w[i] = to_world[i]; M[i / 4][i % 4] = to_world[i]; }
-    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    if (!(std::fabs(det) > 0)) return "area emitter: 'toWorld' is singular";
-    inv[0][0] = (M[1][1] * M[2][2] - M[1][2] * M[2][1]) / det; inv[0][1] = (M[0][2] * M[2][1] - M[0][1] * M[2][2]) / det; inv[0][2] = (M[0][1] * M[1][2] - M[0][2] * M[1][1]) / det;
-    inv[1][0] = (M[1][2] * M[2][0] - M[1][0] * M[2][2]) / det; inv[1][1] = (M[0][0] * M[2][2] - M[0][2] * M[2][0]) / det; inv[1][2] = (M[0][2] * M[1][0] - M[0][0] * M[1][2]) / det;
-    inv[2][0] = (M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det; inv[2][1] = (M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det; inv[2][2] = (M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) R.w2o[4 * i + j] = (float) inv[i][j];
-        R.w2o[4 * i + 3] = (float) -(inv[i][0] * M[0][3] + inv[i][1] * M[1][3] + inv[i][2] * M[2][3]);
-    }
-    const double du[3] = {2 * M[0][0], 2 * M[1][0], 2 * M[2][0]}, dv[3] = {2 * M[0][1], 2 * M[1][1], 2 * M[2][1]};
-    const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
-    if (std::fabs((du[0] * dv[0] + du[1] * dv[1] + du[2] * dv[2]) / (lu * lv)) > MER_EPSILON) return "Error: 'toWorld' transformation contains shear!";    // :108-109
-    const double nn[3] = {inv[2][0], inv[2][1], inv[2][2]}, ln = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // o2w(Normal(0,0,1)): inverse transpose
-    for (int i = 0; i < 3; i++) R.n[i] = (float) (nn[i] / ln);
-    R.inv_area = (float) (1.0 / (lu * lv));
-    return nullptr;
-}
-
-// Exact test that the rectangle O + a U + b V (a, b in [-1, 1]; U = column 0, V = column 1, O = column 3 of M; U orthogonal to V) meets
-// the closed medium shape.  Sphere: its point closest to the centre lies inside.  Cube: no separating axis among the box axes, the
-// rectangle's edges and normal, and the nine edge-by-edge cross products.
-static bool rect_meets_shape(const mer_scene_desc *sc, const double M[3][4]) {
-    const double U[3] = {M[0][0], M[1][0], M[2][0]}, V[3] = {M[0][1], M[1][1], M[2][1]}, O[3] = {M[0][3], M[1][3], M[2][3]};
-    auto dot3 = [](const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; };
-    if (sc->boundary == MER_BOUNDARY_SPHERE) {
-        const double d[3] = {sc->sph_center[0] - O[0], sc->sph_center[1] - O[1], sc->sph_center[2] - O[2]};
-        const double a = std::min(1.0, std::max(-1.0, dot3(d, U) / dot3(U, U))), b = std::min(1.0, std::max(-1.0, dot3(d, V) / dot3(V, V)));
-        double d2 = 0;
-        for (int i = 0; i < 3; i++) { const double e = O[i] + a * U[i] + b * V[i] - sc->sph_center[i]; d2 += e * e; }
-        return d2 < (double) sc->sph_radius * sc->sph_radius;
-    }
-    double c[3], h[3];
-    for (int i = 0; i < 3; i++) { c[i] = 0.5 * ((double) sc->bmin[i] + sc->bmax[i]) - O[i]; h[i] = 0.5 * ((double) sc->bmax[i] - sc->bmin[i]); }
-    const double N[3] = {U[1] * V[2] - U[2] * V[1], U[2] * V[0] - U[0] * V[2], U[0] * V[1] - U[1] * V[0]};
-    double axes[13][3];
-    int na = 0;
-    for (int i = 0; i < 3; i++) { axes[na][0] = axes[na][1] = axes[na][2] = 0; axes[na][i] = 1; na++; }
-    for (const double *w : {U, V, N}) { for (int i = 0; i < 3; i++) axes[na][i] = w[i]; na++; }
-    for (int i = 0; i < 3; i++)
-        for (const double *w : {U, V}) {
-            const double e[3] = {i == 0 ? 1.0 : 0.0, i == 1 ? 1.0 : 0.0, i == 2 ? 1.0 : 0.0};
-            axes[na][0] = e[1] * w[2] - e[2] * w[1]; axes[na][1] = e[2] * w[0] - e[0] * w[2]; axes[na][2] = e[0] * w[1] - e[1] * w[0]; na++;
-        }
-    for (int k = 0; k < na; k++) {
-        const double *L = axes[k];
-        const double rBox = h[0] * std::fabs(L[0]) + h[1] * std::fabs(L[1]) + h[2] * std::fabs(L[2]);
-        const double rRect = std::fabs(dot3(U, L)) + std::fabs(dot3(V, L));
-        if (std::fabs(dot3(c, L)) > rBox + rRect) return false;           // separated (touching counts as meeting: the cube is closed)
-    }
-    return true;
-}
-
-// emitter `spot` (src/emitters/spot.cpp:68-95): the cone record of its point-table slot, in float as the reference derives it (degToRad in
-// float, util.h:293; std::cos of the float angle).  The z row of the inverse linear part is computed in double and rounded.  Returns an
-// error message or nullptr.
-static const char *spot_derive(const mer_emitter &e, DSpot &s) {
-    const float cdeg = e.cutoff_angle_deg, bdeg = e.beam_width_deg;
-    if (!std::isfinite(cdeg) || !std::isfinite(bdeg) || cdeg < 0 || bdeg < 0) return "spot emitter: cutoffAngle and beamWidth must be finite and non-negative";
-    if (cdeg > 180) return "spot emitter: cutoffAngle must not exceed 180 degrees";
-    if (bdeg > cdeg) return "spot emitter: beamWidth must not exceed cutoffAngle (Assert(m_cutoffAngle >= m_beamWidth))";
-    double M[3][3];
-    for (int i = 0; i < 12; i++) { if (!std::isfinite(e.to_world[i])) return "spot emitter: 'toWorld' must be finite"; if (i % 4 != 3) M[i / 4][i % 4] = e.to_world[i]; }
-    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return "spot emitter: 'toWorld' is singular";
-    s.z[0] = (float) ((M[1][0] * M[2][1] - M[1][1] * M[2][0]) / det);       // row 2 of the inverse
-    s.z[1] = (float) ((M[0][1] * M[2][0] - M[0][0] * M[2][1]) / det);
-    s.z[2] = (float) ((M[0][0] * M[1][1] - M[0][1] * M[1][0]) / det);
-    const float beam = (float) (bdeg * (M_PI / 180.0f)), cutoff = (float) (cdeg * (M_PI / 180.0f));
-    s.cos_beam = std::cos(beam); s.cos_cutoff = std::cos(cutoff);
-    s.cutoff = cutoff; s.inv_width = 1.0f / (cutoff - beam);
-    s.pad = 0;
-    return nullptr;
-}
-
-// emitter `envmap`: its record from the uploaded map and the entry's toWorld (a rotation within 1e-5; the translation is ignored -- a direction
-// does not see it) and scale.  Returns an error message or nullptr.
-static const char *envmap_derive(mer_context *ctx, const mer_emitter &e, DEnvMap &E) {
-    auto it = ctx->envmaps.find(e.envmap);
-    if (it == ctx->envmaps.end()) return "envmap emitter: unknown or destroyed envmap handle (mer_envmap_upload)";
-    if (!std::isfinite(e.env_scale) || !(e.env_scale >= 0)) return "envmap emitter: 'scale' must be finite and non-negative";
-    double M[3][3];
-    for (int i = 0; i < 12; i++) { if (!std::isfinite(e.to_world[i])) return "envmap emitter: 'toWorld' must be finite"; if (i % 4 != 3) M[i / 4][i % 4] = e.to_world[i]; }
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            const double d = M[r][0] * M[c][0] + M[r][1] * M[c][1] + M[r][2] * M[c][2] - (r == c ? 1.0 : 0.0);
-            if (std::fabs(d) > 1e-5) return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)";
-        }
-    const double det = M[0][0] * (M[1][1] * M[2][2] - M[1][2] * M[2][1]) - M[0][1] * (M[1][0] * M[2][2] - M[1][2] * M[2][0]) + M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
-    if (!(det > 0)) return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)";
-    const EnvMap &m = it->second;
-    const unsigned char *b = (const unsigned char *) m.dev;
-    E = DEnvMap{};
-    E.texels = (const uint2 *) b; E.cdf_cols = (const float *) (b + m.off_cols); E.cdf_rows = (const float *) (b + m.off_rows);
-    E.row_weights = (const float *) (b + m.off_weights);
-    E.chk = ctx->chk;
-    E.w = m.w; E.h = m.h; E.norm = m.norm; E.scale = e.env_scale;
-    // trafo.inverse() of a rotation: its inverse matrix (in double, rounded), the rotation itself for the sampled direction (envmap.cpp:382, 537)
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) {
-            const int r1 = (c + 1) % 3, r2 = (c + 2) % 3, c1 = (r + 1) % 3, c2 = (r + 2) % 3;     // inverse = adjugate / det (cofactor of (c, r))
-            E.w2l[3 * r + c] = (float) ((M[r1][c1] * M[r2][c2] - M[r1][c2] * M[r2][c1]) / det);
-            E.l2w[3 * r + c] = (float) M[r][c];
-        }
-    E.pix[0] = (float) (2 * M_PI / m.w); E.pix[1] = (float) (M_PI / m.h);           // m_pixelSize (:312)
-    return nullptr;
-}
-
-// mer_scene_desc.emitters -> the point / area tables (and the spots' cones, one per point-table slot; the envmap's record): each entry checked as the single emitter of its kind is, the rectangles by the exact
-// outside test, then every kind's selection pdf = sampling_weight / sum and its CDF
-static int build_emitter_list(mer_context *ctx, const mer_scene_desc *sc, std::vector<DPoint> &points, std::vector<DRect> &rects, std::vector<DSpot> &spots,
-                              std::vector<DEnvMap> &envs) {
-    if (sc->n_emitters < 0 || sc->n_emitters > MER_MAX_EMITTERS) return fail(ctx, "emitter list: at most " + std::to_string(MER_MAX_EMITTERS) + " entries (MER_MAX_EMITTERS)");
-    if (!sc->emitters) return fail(ctx, "emitter list: n_emitters > 0 but no entries");
-    if (!points.empty() || !rects.empty()) return fail(ctx, "emitter list: the point_* / area_* emitter fields must be zero when n_emitters > 0");
-    std::vector<double> wp, wr;
-    bool any_spot = false;
-    for (int j = 0; j < sc->n_emitters; ++j) {
-        const mer_emitter &e = sc->emitters[j];
-        const std::string at = "emitter list, entry " + std::to_string(j) + ": ";
-        if (!(e.sampling_weight > 0) || !std::isfinite(e.sampling_weight)) return fail(ctx, at + "samplingWeight must be positive");
-        if (e.type == MER_EMITTER_POINT) {
-            for (int i = 0; i < 3; i++) if (!(e.intensity[i] >= 0) || !std::isfinite(e.position[i])) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
-            if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point_in_shape(sc, e.position))
-                return fail(ctx, at + "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
-            DPoint E{};
-            for (int i = 0; i < 3; i++) { E.pos[i] = e.position[i]; E.Ie[i] = e.intensity[i]; }
-            points.push_back(E); wp.push_back(e.sampling_weight);
-            DSpot none{}; none.cos_cutoff = none.cos_beam = -2.0f; spots.push_back(none);         // falloff 1
-        } else if (e.type == MER_EMITTER_SPOT) {      // a point emitter at toWorld's origin with a cone: it joins the point table
-            DSpot cone{};
-            if (const char *err = spot_derive(e, cone)) return fail(ctx, at + err);
-            DPoint E{};
-            for (int i = 0; i < 3; i++) { E.pos[i] = e.to_world[4 * i + 3]; E.Ie[i] = e.intensity[i]; }
-            for (int i = 0; i < 3; i++) if (!(e.intensity[i] >= 0) || !std::isfinite(e.intensity[i])) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
-            if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC && point_in_shape(sc, E.pos))
-                return fail(ctx, at + "hroughdielectric: the spot emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
-            points.push_back(E); wp.push_back(e.sampling_weight); spots.push_back(cone);
-            any_spot = true;
-        } else if (e.type == MER_EMITTER_AREA) {
-            if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, at + "the area emitter is built for straight rays (rif_mode = CONST)");
-            if (sc->boundary_bsdf != MER_BSDF_NULL || sc->boundary == MER_BOUNDARY_SDF) return fail(ctx, at + "the area emitter needs an index-matched cube / sphere boundary");
-            for (int i = 0; i < 3; i++) if (!(e.radiance[i] >= 0)) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
-            DRect R{}; double M[3][4];
-            if (const char *err = rect_derive(e.to_world, R, M)) return fail(ctx, at + err);
-            if (rect_meets_shape(sc, M)) return fail(ctx, at + "the area emitter's rectangle must lie outside the medium shape");
-            for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = e.radiance[i];
-            rects.push_back(R); wr.push_back(e.sampling_weight);
-        } else if (e.type == MER_EMITTER_ENVMAP) {    // the environment: its own kind, one at most, sampled at every collision (selection probability 1)
-            if (!envs.empty() || sc->env_radiance[0] != 0 || sc->env_radiance[1] != 0 || sc->env_radiance[2] != 0)
-                return fail(ctx, at + "The scene may only contain one environment emitter (an envmap entry excludes a second one and a non-zero env_radiance)");
-            DEnvMap E;
-            if (const char *err = envmap_derive(ctx, e, E)) return fail(ctx, at + err);
-            envs.push_back(E);
-        } else return fail(ctx, at + "unknown emitter type");
-    }
-    if (!rects.empty())
-        for (const DPoint &E : points)
-            if (!point_in_shape(sc, E.pos))
-                return fail(ctx, "emitter list: a point or spot emitter outside the medium shape cannot be combined with an area emitter (point samples are not tested against rectangles)");
-    if (!any_spot) spots.clear();                 // point-only scenes carry no cone table: the kernels skip the falloff
-    // selection pdf and CDF of every kind; the sample of emitter k is divided by its pdf on the host (intensity / pdf, radiance / pdf)
-    double sum = 0, cum = 0;
-    for (double w : wp) sum += w;
-    for (size_t k = 0; k < points.size(); ++k) {
-        cum += wp[k];
-        DPoint &E = points[k];
-        E.pdf = (float) (wp[k] / sum); E.cdf = k + 1 == points.size() ? 1.0f : (float) (cum / sum);
-        for (int i = 0; i < 3; i++) E.Ie[i] = E.Ie[i] / E.pdf;
-    }
-    sum = 0; cum = 0;
-    for (double w : wr) sum += w;
-    for (size_t k = 0; k < rects.size(); ++k) {
-        cum += wr[k];
-        DRect &R = rects[k];
-        R.pdf = (float) (wr[k] / sum); R.cdf = k + 1 == rects.size() ? 1.0f : (float) (cum / sum);
-        for (int i = 0; i < 3; i++) R.Le[i] = R.L[i] / R.pdf;
-    }
-    return 0;
-}
-
-int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf) {
-    std::memset(&P, 0, sizeof(P));
-    P.sc = *sc;
-    if (sc->width <= 0 || sc->height <= 0) return fail(ctx, "film: width/height must be positive");
-    if (sc->rr_depth <= 0) return fail(ctx, "'rrDepth' must be set to a value greater than zero!");                 // integrator.cpp:217
-    if (sc->max_depth <= 0 && sc->max_depth != -1)
-        return fail(ctx, "'maxDepth' must be set to -1 (infinite) or a value greater than zero!");                  // integrator.cpp:220
-    if (sc->phase == MER_PHASE_HG && (sc->g >= 1 || sc->g <= -1))
-        return fail(ctx, "The asymmetry parameter must lie in the interval (-1, 1)!");                              // hg.cpp:52-53
-    if (sc->sigma_mode == MER_SIGMA_GRID) {
-        auto it = ctx->volumes.find(sc->density);
-        if (it == ctx->volumes.end()) return fail(ctx, "No density specified!");                                    // heterogeneous.cpp:229-230
-        if (it->second.desc.channels != 1) return fail(ctx, "density volume must support float lookups");           // :270
-        if (it->second.layout == MER_LAYOUT_BRICK27 || it->second.layout == MER_LAYOUT_BRICK125) return fail(ctx, "the BRICK layouts are for the refractive-index field only");
-        fill_dgrid(ctx, it->second, P.density);
-        if (!(sc->density_scale > 0)) return fail(ctx, "heterogeneous medium: 'scale' must be positive");
-        // m_maxDensity = m_scale * getMaximumFloatValue() (= 1.0 for gridvolume): heterogeneous.cpp:239-242
-        P.inv_max_density = 1.0f / (sc->density_scale * 1.0f);
-        if (sc->method != MER_METHOD_WOODCOCK && sc->method != MER_METHOD_SIMPSON) return fail(ctx, "Unsupported integration method!");    // heterogeneous.cpp:195-202
-        if (sc->method == MER_METHOD_SIMPSON) {
-            if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, "method = simpson belongs to the heterogeneous medium (straight rays)");
-            auto step_of = [](const mer_grid_desc &g) {                      // gridvolume.cpp:196-198
-                float s = std::numeric_limits<float>::infinity();
-                for (int i = 0; i < 3; i++) s = std::min(s, 0.5f * (g.aabb_max[i] - g.aabb_min[i]) / (float) (g.res[i] - 1));
-                return s;
-            };
-            float h = sc->het_stepsize;                                      // heterogeneous.cpp:245-257
-            if (h == 0) {
-                h = step_of(ctx->volumes.find(sc->density)->second.desc);
-                if (sc->albedo_mode == MER_ALBEDO_GRID) { auto ia = ctx->volumes.find(sc->albedo_grid); if (ia != ctx->volumes.end()) h = std::min(h, step_of(ia->second.desc)); }
-            }
-            if (!(h > 0) || !std::isfinite(h))
-                return fail(ctx, "Unable to infer a suitable step size for deterministic integration, please specify one manually using the 'stepSize' parameter.");
-            P.het_step = h;
-            P.sc.tr_estimator = MER_TR_RATIO;        // one walk per transmittance query (the estimator choice is the Woodcock method's)
-        }
-    }
-    if (sc->albedo_mode == MER_ALBEDO_GRID) {
-        auto it = ctx->volumes.find(sc->albedo_grid);
-        if (it == ctx->volumes.end()) return fail(ctx, "No albedo specified!");                                     // heterogeneous.cpp:231-232
-        if (it->second.desc.channels != 3) return fail(ctx, "albedo volume must support spectrum lookups");
-        Volume tmp = it->second; tmp.cell8 = nullptr;
-        fill_dgrid(ctx, tmp, P.albedo);
-    }
-    if (sc->rif_mode == MER_RIF_ACOUSTIC) {
-        // acousticrifvolume: analytic, no grid (src/volume/acousticrifvolume.cpp:101-106)
-        if (!(sc->stepsize > 0)) return fail(ctx, "heterogeneousrefractive: 'stepsize' must be positive");
-        if (!(sc->ac_k_r > 0) || !(sc->ac_n_o > 0) || sc->ac_mode < 0 || !std::isfinite(sc->ac_n_max)) return fail(ctx, "acousticrifvolume: n_o and k_r = 2 pi freq / speed must be positive, mode non-negative");
-        std::memset(&P.rif, 0, sizeof(P.rif));
-        P.rif.ac_n_o = sc->ac_n_o; P.rif.ac_n_max = sc->ac_n_max; P.rif.ac_k_r = sc->ac_k_r; P.rif.ac_mode = sc->ac_mode;
-        P.rif.res[0] = P.rif.res[1] = P.rif.res[2] = 2;
-    } else if (sc->rif_mode != MER_RIF_CONST) {
-        if (sc->rif_mode != MER_RIF_TRILINEAR && sc->rif_mode != MER_RIF_BSPLINE3) return fail(ctx, "unknown rif_mode");
-        auto it = ctx->volumes.find(sc->rif);
-        if (it == ctx->volumes.end()) return fail(ctx, "No RIF specified!");                                        // heterogeneousrefractive.cpp:368-369
-        if (it->second.desc.channels != 1 || it->second.desc.dtype != MER_VOL_F32)
-            return fail(ctx, "RIF volume must be a 1-channel float32 grid");
-        if (sc->rif_mode == MER_RIF_BSPLINE3 && !it->second.coeff)
-            return fail(ctx, "RIF volume has no spline coefficients (call mer_volume_build_spline)");
-        if (!(sc->stepsize > 0)) return fail(ctx, "heterogeneousrefractive: 'stepsize' must be positive");
-        fill_dgrid(ctx, it->second, P.rif);
-        // the fetch index (z * res_y + y) * res_x + x is formed with 24-bit multiplies (v_mul_u32_u24)
-        if ((int64_t) P.rif.res[1] * P.rif.res[2] > ((int64_t) 1 << 24) || P.rif.res[0] > (1 << 24))
-            return fail(ctx, "RIF volume: res_y * res_z must not exceed 2^24 (index arithmetic of the trilinear fetch)");
-        if ((int64_t) P.rif.res[0] * P.rif.res[1] * P.rif.res[2] >= ((int64_t) 1 << 31))
-            return fail(ctx, "RIF volume: more than 2^31 nodes (the cell id of the trilinear fetch is a 32-bit integer)");
-        if (P.rif.affine && it->second.cell8)
-            return fail(ctx, "RIF volume with a toWorld transform: upload it in the dense layout (the CELL8 / BRICK record layouts carry no transform)");
-        if (sc->rif_mode == MER_RIF_BSPLINE3) {
-            for (int i = 0; i < 3; i++) if (P.rif.res[i] < 5) return fail(ctx, "splinevolume needs at least 5 nodes per axis");
-            // the medium must lie inside the spline-safe box (gate: heterogeneousrefractive.cpp:461-466)
-        }
-    }
-    for (int i = 0; i < 3; i++) {
-        if (sc->sigma_a[i] < 0 || sc->sigma_s[i] < 0) return fail(ctx, "sigmaA / sigmaS must be non-negative");
-    }
-    P.sigA = f3(sc->sigma_a[0], sc->sigma_a[1], sc->sigma_a[2]);
-    P.sigS = f3(sc->sigma_s[0], sc->sigma_s[1], sc->sigma_s[2]);
-    P.sigT = f3(sc->sigma_a[0] + sc->sigma_s[0], sc->sigma_a[1] + sc->sigma_s[1], sc->sigma_a[2] + sc->sigma_s[2]);
-    const float sT[3] = {P.sigT.x, P.sigT.y, P.sigT.z}, sS[3] = {P.sigS.x, P.sigS.y, P.sigS.z};
-    // mediumSamplingWeight: homogeneous.cpp:172-190 == heterogeneousrefractive.cpp:239-255
-    float w = sc->medium_sampling_weight;
-    if (w == -1) {
-        for (int i = 0; i < 3; ++i) {
-            const float albedo = sS[i] / sT[i];
-            if (albedo > w && sT[i] != 0) w = albedo;
-        }
-        if (w > 0) w = std::max(w, 0.5f);
-    }
-    P.medium_sampling_weight = w;
-    P.sampling_density = 0;
-    if (sc->strategy == MER_STRATEGY_SINGLE) {
-        int channel = 0; float smallest = std::numeric_limits<float>::infinity();
-        for (int i = 0; i < 3; ++i) if (sT[i] < smallest) { smallest = sT[i]; channel = i; }
-        if (sc->channel >= 0) { if (sc->channel > 2) return fail(ctx, "channel out of range"); channel = sc->channel; }
-        P.sampling_density = sT[channel];
-    } else if (sc->strategy == MER_STRATEGY_MANUAL) {
-        P.sampling_density = sc->sampling_density;
-    } else if (sc->strategy == MER_STRATEGY_MAXIMUM) {
-        // MaxExpDist's constructor (src/medium/maxexp.h:30-58), in the reference's float arithmetic
-        MaxExp &m = P.maxexp;
-        for (int i = 0; i < 3; i++) m.sigmaT[i] = sT[i];
-        std::sort(m.sigmaT, m.sigmaT + 3, std::greater<float>());
-        m.cdf[0] = 0;
-        for (int i = 0; i < 3; ++i) {
-            if (i > 0 && m.sigmaT[i] == m.sigmaT[i - 1]) return fail(ctx, "Internal error: sigmaT must vary across channels");
-            if (!(m.sigmaT[i] > 0)) return fail(ctx, "strategy maximum: sigmaT must be positive in every channel");
-            const float lower = (i == 0) ? -1 : -std::pow((m.sigmaT[i] / m.sigmaT[i - 1]), -m.sigmaT[i] / (m.sigmaT[i] - m.sigmaT[i - 1]));
-            const float upper = (i == 2) ? 0 : -std::pow((m.sigmaT[i + 1] / m.sigmaT[i]), -m.sigmaT[i] / (m.sigmaT[i + 1] - m.sigmaT[i]));
-            m.cdf[i + 1] = m.cdf[i] + (upper - lower);
-            m.intervalStart[i] = (i == 0) ? 0 : std::log(m.sigmaT[i] / m.sigmaT[i - 1]) / (m.sigmaT[i] - m.sigmaT[i - 1]);
-        }
-        m.normalization = m.cdf[3]; m.invNormalization = 1 / m.normalization;
-        for (int i = 0; i < 4; ++i) m.cdf[i] *= m.invNormalization;
-    } else if (sc->strategy != MER_STRATEGY_BALANCE) {
-        return fail(ctx, "Specified an unknown sampling strategy");                                                 // homogeneous.cpp:226
-    }
-    if (sc->sigma_mode == MER_SIGMA_HOMOGENEOUS && !(sT[0] > 0 && sT[1] > 0 && sT[2] > 0) && sc->strategy == MER_STRATEGY_BALANCE)
-        return fail(ctx, "homogeneous medium: sigmaT must be positive in every channel for the balance strategy");
-    P.aspect = (float) sc->width / (float) sc->height;
-    P.cot_half_fov = 1.0f / std::tan((sc->fov_x_deg / 2.0f) * (MER_PI / 180.0f));
-    for (int i = 0; i < 3; i++) P.par_dir[i] = P.sensor_pad[i] = 0.0f;
-    P.lens_radius = P.lens_focus = 0.0f;
-    if (sc->sensor < MER_SENSOR_PERSPECTIVE || sc->sensor > MER_SENSOR_TELECENTRIC) return fail(ctx, "sensor: unknown sensor kind (perspective, orthographic, thinlens, telecentric)");
-    if (sc->sensor_reserved != 0) return fail(ctx, "sensor: sensor_reserved must be 0");
-    if (sc->sensor != MER_SENSOR_PERSPECTIVE) {
-        // what the sensors' constructors / configure() derive from toWorld (orthographic.cpp:133, telecentric.cpp:140-147), in float
-        const float *m = sc->cam_to_world;
-        bool finite = true;
-        for (int i = 0; i < 12; i++) finite = finite && std::isfinite(m[i]);
-        const double det = (double) m[0] * ((double) m[5] * m[10] - (double) m[6] * m[9]) - (double) m[1] * ((double) m[4] * m[10] - (double) m[6] * m[8])
-                         + (double) m[2] * ((double) m[4] * m[9] - (double) m[5] * m[8]);
-        if (!finite || !(std::fabs(det) > 1e-12)) return fail(ctx, "sensor: cam_to_world is singular");
-        float len[3];
-        for (int c = 0; c < 3; c++) len[c] = std::sqrt(m[c] * m[c] + m[4 + c] * m[4 + c] + m[8 + c] * m[8 + c]);
-        for (int r = 0; r < 3; r++) P.par_dir[r] = m[4 * r + 2] / len[2];
-        if (sc->sensor != MER_SENSOR_ORTHOGRAPHIC) {
-            if (!(sc->aperture_radius >= 0) || !std::isfinite(sc->aperture_radius)) return fail(ctx, "sensor: aperture_radius must be finite and non-negative");
-            if (!(sc->focus_distance > 0) || !std::isfinite(sc->focus_distance)) return fail(ctx, "sensor: focus_distance must be finite and positive");
-            const bool tele = sc->sensor == MER_SENSOR_TELECENTRIC;
-            P.lens_radius = tele ? sc->aperture_radius / len[0] : sc->aperture_radius;
-            P.lens_focus = tele ? sc->focus_distance / len[2] : sc->focus_distance;
-        }
-    }
-    P.inv_res_x = 1.0f / sc->width; P.inv_res_y = 1.0f / sc->height;
-    if (sc->rfilter != MER_FILTER_BOX && sc->rfilter != MER_FILTER_GAUSSIAN) return fail(ctx, "unknown reconstruction filter");
-    if (!(sc->rfilter_param > 0)) return fail(ctx, "reconstruction filter radius/stddev must be positive");
-    {   // the table goes to device memory once per (kind, parameter); no kernel of this context is in flight here (renders and leaf calls return synchronised)
-        float fv[33];
-        filter_table(sc->rfilter, sc->rfilter_param, fv, P.fradius, P.fscale);
-        if (!ctx->ftable) HIP_CHECK(ctx, hipMalloc((void **) &ctx->ftable, sizeof(fv)));
-        if (ctx->ftable_kind != sc->rfilter || ctx->ftable_param != sc->rfilter_param) {
-            HIP_CHECK(ctx, hipMemcpy(ctx->ftable, fv, sizeof(fv), hipMemcpyHostToDevice));
-            ctx->ftable_kind = sc->rfilter; ctx->ftable_param = sc->rfilter_param;
-        }
-        P.ftable = ctx->ftable;
-    }
-    if (P.fradius > 7.0f) return fail(ctx, "reconstruction filter radius too large");
-    if (sc->boundary_bsdf != MER_BSDF_NULL && sc->boundary_bsdf != MER_BSDF_HDIELECTRIC && sc->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC)
-        return fail(ctx, "boundary BSDF must be null, hdielectric or hroughdielectric");
-    if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {
-        if (check_rough(ctx, sc)) return 1;
-        const bool point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
-        // (a signed-distance shape: tested below, where its grid is known)
-        if (point && point_in_shape(sc, sc->point_position)) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
-    }
-    std::vector<DPoint> points; std::vector<DRect> rects; std::vector<DSpot> spots; std::vector<DEnvMap> envs;
-    const bool legacy_area = sc->area_radiance[0] != 0 || sc->area_radiance[1] != 0 || sc->area_radiance[2] != 0;
-    const bool legacy_point = sc->point_intensity[0] != 0 || sc->point_intensity[1] != 0 || sc->point_intensity[2] != 0;
-    if (legacy_area) {
-        if (sc->rif_mode != MER_RIF_CONST) return fail(ctx, "the area emitter is built for straight rays (rif_mode = CONST)");
-        if (sc->boundary_bsdf != MER_BSDF_NULL || sc->boundary == MER_BOUNDARY_SDF) return fail(ctx, "the area emitter needs an index-matched cube / sphere boundary");
-        DRect R{}; double M[3][4];
-        if (const char *e = rect_derive(sc->area_to_world, R, M)) return fail(ctx, e);
-        // the rectangle must lie outside the (convex) medium shape: corners and centre are tested
-        for (int k = 0; k < 5; k++) {
-            const float lx = k == 4 ? 0.0f : (k & 1 ? 1.0f : -1.0f), ly = k == 4 ? 0.0f : (k & 2 ? 1.0f : -1.0f);
-            const float q[3] = {(float) (M[0][0] * lx + M[0][1] * ly + M[0][3]), (float) (M[1][0] * lx + M[1][1] * ly + M[1][3]), (float) (M[2][0] * lx + M[2][1] * ly + M[2][3])};
-            bool in = true;
-            if (sc->boundary == MER_BOUNDARY_SPHERE) { float d2 = 0; for (int i = 0; i < 3; i++) d2 += (q[i] - sc->sph_center[i]) * (q[i] - sc->sph_center[i]); in = d2 < sc->sph_radius * sc->sph_radius; }
-            else for (int i = 0; i < 3; i++) in = in && q[i] >= sc->bmin[i] && q[i] <= sc->bmax[i];
-            if (in) return fail(ctx, "the area emitter's rectangle must lie outside the medium shape");
-        }
-        for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = sc->area_radiance[i];
-        R.pdf = R.cdf = 1.0f;
-        rects.push_back(R);
-    }
-    if (legacy_point) {
-        DPoint E{};
-        for (int i = 0; i < 3; i++) { E.pos[i] = sc->point_position[i]; E.Ie[i] = sc->point_intensity[i]; }
-        E.pdf = E.cdf = 1.0f;
-        points.push_back(E);
-    }
-    if (sc->n_emitters != 0 && build_emitter_list(ctx, sc, points, rects, spots, envs)) return 1;
-    if (film_frames(ctx, sc, P.frames)) return 1;
-    P.film_ch = P.frames * 3 + 2;
-    P.mod_phase = (float) (sc->mod_phase_deg * M_PI / 180);                                                   // pathlengthsampler.cpp:15
-    if (sc->boundary == MER_BOUNDARY_AABB) {
-        for (int i = 0; i < 3; i++) if (!(sc->bmin[i] < sc->bmax[i])) return fail(ctx, "medium shape: empty bounding box");
-    } else if (sc->boundary == MER_BOUNDARY_SPHERE) {
-        if (!(sc->sph_radius > 0)) return fail(ctx, "medium shape: sphere radius must be positive");
-    } else if (sc->boundary == MER_BOUNDARY_SDF) {
-        if (!allow_sdf) return fail(ctx, "the signed-distance boundary is known to mer_render only (leaf entry points: cube / sphere)");
-        auto it = ctx->volumes.find(sc->sdf);
-        if (it == ctx->volumes.end()) return fail(ctx, "heterogeneousrefractive: no sdf volume (boundary = sdf)");
-        if (it->second.desc.channels != 1 || it->second.desc.dtype != MER_VOL_F32) return fail(ctx, "heterogeneousrefractive: the sdf must be a 1-channel float32 grid");
-        if (it->second.layout == MER_LAYOUT_BRICK27 || it->second.layout == MER_LAYOUT_BRICK125) return fail(ctx, "the BRICK layouts are for the refractive-index field only");
-        fill_dgrid(ctx, it->second, P.sdf);
-        float d2 = 0; for (int i = 0; i < 3; i++) d2 += (P.sdf.bmax[i] - P.sdf.bmin[i]) * (P.sdf.bmax[i] - P.sdf.bmin[i]);
-        P.sdf_eps = 1e-4f * std::sqrt(d2);
-        for (const DPoint &E : points) if (sc->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) {      // an emitter inside the signed-distance shape: the grid's value there (sdf_value)
-            const DGrid &g = P.sdf; const float *q = E.pos;
-            float c[3];
-            for (int i = 0; i < 3; i++) c[i] = g.m[4 * i] * q[0] + g.m[4 * i + 1] * q[1] + g.m[4 * i + 2] * q[2] + g.m[4 * i + 3];
-            const int x1 = (int) std::floor(c[0]), y1 = (int) std::floor(c[1]), z1 = (int) std::floor(c[2]);
-            if (x1 >= 0 && y1 >= 0 && z1 >= 0 && x1 < g.res[0] - 1 && y1 < g.res[1] - 1 && z1 < g.res[2] - 1) {     // off the grid: outside
-                float v = 0;
-                for (int k = 0; k < 8; k++) {
-                    const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-                    float corner;
-                    HIP_CHECK(ctx, hipMemcpy(&corner, (const float *) g.data + ((size_t) (z1 + dz) * g.res[1] + (y1 + dy)) * g.res[0] + (x1 + dx), 4, hipMemcpyDeviceToHost));
-                    const float fx = c[0] - x1, fy = c[1] - y1, fz = c[2] - z1;
-                    v += (dx ? fx : 1 - fx) * (dy ? fy : 1 - fy) * (dz ? fz : 1 - fz) * corner;
-                }
-                if (v < 0) return fail(ctx, "hroughdielectric: the point emitter must lie outside the medium shape (a curved connection that starts on the boundary is not built)");
-            }
-        }
-    } else return fail(ctx, "unknown medium boundary");
-    if (sc->aggressive_tracing) {
-        if (sc->boundary != MER_BOUNDARY_SDF) return fail(ctx, "aggressivetracing needs the signed-distance boundary (the medium's sdf volume)");
-        if (sc->rif_mode == MER_RIF_CONST) return fail(ctx, "aggressivetracing is a property of curved-ray tracing (heterogeneousrefractive)");
-        if (!(sc->sdf_max_error >= 0)) return fail(ctx, "aggressivetracing: sdf_max_error must be non-negative");
-    }
-    for (int i = 0; i < 3; i++) if (sc->point_intensity[i] < 0 || sc->env_radiance[i] < 0) return fail(ctx, "emitter radiance / intensity must be non-negative");
-    // curved rays reach a point emitter outside the shape through the boundary (Connector::path_lengths, cross = true)
-    ctx->point_outside = false;
-    for (const DPoint &E : points) if (sc->boundary != MER_BOUNDARY_SDF && !point_in_shape(sc, E.pos)) ctx->point_outside = true;
-    {   // the tables go to device memory when they change; no kernel of this context is in flight here (renders and leaf calls return synchronised)
-        const size_t off = sizeof(DPoint) * MER_MAX_EMITTERS, off_spot = off + sizeof(DRect) * MER_MAX_EMITTERS, off_env = off_spot + sizeof(DSpot) * MER_MAX_EMITTERS,
-                     bytes = off_env + sizeof(DEnvMap);
-        std::vector<unsigned char> h(bytes, 0);
-        if (!points.empty()) std::memcpy(h.data(), points.data(), sizeof(DPoint) * points.size());
-        if (!rects.empty()) std::memcpy(h.data() + off, rects.data(), sizeof(DRect) * rects.size());
-        if (!spots.empty()) std::memcpy(h.data() + off_spot, spots.data(), sizeof(DSpot) * spots.size());
-        if (!envs.empty()) std::memcpy(h.data() + off_env, envs.data(), sizeof(DEnvMap));
-        if (!ctx->etab) HIP_CHECK(ctx, hipMalloc(&ctx->etab, bytes));
-        if (ctx->etab_host != h) {
-            HIP_CHECK(ctx, hipMemcpy(ctx->etab, h.data(), bytes, hipMemcpyHostToDevice));
-            ctx->etab_host.swap(h);
-        }
-        P.n_point = (int32_t) points.size(); P.n_rect = (int32_t) rects.size();
-        P.points = (const DPoint *) ctx->etab; P.rects = (const DRect *) ((const unsigned char *) ctx->etab + off);
-        P.has_spot = spots.empty() ? 0 : 1;             // the kernels find the cones at off_spot (spot_table)
-        P.has_envmap = envs.empty() ? 0 : 1;            // and the envmap's record at off_env (envmap_rec)
-    }
-    P.counters = ctx->counters;
-    P.work_counter = ctx->counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
-    P.chk = ctx->chk;
-    P.dbg_pixel = (int32_t) ctx->opt.debug_pixel;
-    return 0;
-}
-
-int rif_fetch_kind(mer_context *ctx, const mer_scene_desc *sc) {
-    if (sc->rif_mode != MER_RIF_TRILINEAR) return sc->rif_mode;
-    const Volume &rv = ctx->volumes.find(sc->rif)->second;
-    DGrid tmp; fill_dgrid(ctx, rv, tmp);
-    if (tmp.layout == MER_LAYOUT_BRICK27 || tmp.layout == MER_LAYOUT_BRICK125) return tmp.buf_bytes ? RIFK_BRICK27_BUF : RIFK_BRICK27;
-    if (tmp.layout == MER_LAYOUT_CELL8) return tmp.buf_bytes ? RIFK_CELL8_BUF : RIFK_CELL8;
-    return tmp.buf_bytes ? RIFK_DENSE_BUF : MER_RIF_TRILINEAR;
+// The fetch kinds and steppers the curved-ray leaf kernels are instantiated for, and a run-time value as the std::integral_constant of
+// the listed one it equals: returns f(constant), or false when the value is none of them.
+using FetchKinds = std::integer_sequence<int, RIFK_ACOUSTIC, MER_RIF_TRILINEAR, RIFK_DENSE_BUF, RIFK_CELL8, RIFK_CELL8_BUF, RIFK_BRICK27_BUF, RIFK_BRICK27, MER_RIF_BSPLINE3>;
+using Steppers = std::integer_sequence<int, MER_STEP_VERLET, MER_STEP_RK4>;
+template <int... Ks, typename F> static bool match_constant(std::integer_sequence<int, Ks...>, int value, F &&f) {
+    return ((value == Ks && f(std::integral_constant<int, Ks>())) || ...);
 }
 
 template <typename F> static int dispatch_modes(mer_context *ctx, const mer_scene_desc *sc, F &&f) {
@@ -596,28 +34,15 @@ template <typename F> static int dispatch_modes(mer_context *ctx, const mer_scen
                  std::integral_constant<int, MER_STEP_VERLET>(), std::integral_constant<int, MER_SIGMA_HOMOGENEOUS>(), std::integral_constant<int, 0>());
     }
     // internal fetch kind of the trilinear RIF (mer_device.hpp): layout x {global, buffer} loads
-    const int rifk = rif_fetch_kind(ctx, sc);
-#define MER_CASE(R, S, G)                                                                                         \
-    if (rifk == R && sc->stepper == S && (int) grid == G)                                                         \
-        return f(std::integral_constant<bool, true>(), std::integral_constant<int, R>(), std::integral_constant<int, S>(), \
-                 std::integral_constant<int, G>(), std::integral_constant<int, 0>());
-    MER_CASE(RIFK_ACOUSTIC, MER_STEP_VERLET, 1) MER_CASE(RIFK_ACOUSTIC, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_ACOUSTIC, MER_STEP_VERLET, 0) MER_CASE(RIFK_ACOUSTIC, MER_STEP_RK4, 0)
-    MER_CASE(MER_RIF_TRILINEAR, MER_STEP_VERLET, 1) MER_CASE(MER_RIF_TRILINEAR, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_DENSE_BUF, MER_STEP_VERLET, 1) MER_CASE(RIFK_DENSE_BUF, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_CELL8, MER_STEP_VERLET, 1) MER_CASE(RIFK_CELL8, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_CELL8_BUF, MER_STEP_VERLET, 1) MER_CASE(RIFK_CELL8_BUF, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_BRICK27_BUF, MER_STEP_VERLET, 1) MER_CASE(RIFK_BRICK27_BUF, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_BRICK27, MER_STEP_VERLET, 1) MER_CASE(RIFK_BRICK27, MER_STEP_RK4, 1)
-    MER_CASE(RIFK_BRICK27_BUF, MER_STEP_VERLET, 0) MER_CASE(RIFK_BRICK27_BUF, MER_STEP_RK4, 0)
-    MER_CASE(RIFK_BRICK27, MER_STEP_VERLET, 0) MER_CASE(RIFK_BRICK27, MER_STEP_RK4, 0)
-    MER_CASE(MER_RIF_BSPLINE3, MER_STEP_VERLET, 1) MER_CASE(MER_RIF_BSPLINE3, MER_STEP_RK4, 1)
-    MER_CASE(MER_RIF_TRILINEAR, MER_STEP_VERLET, 0) MER_CASE(MER_RIF_TRILINEAR, MER_STEP_RK4, 0)
-    MER_CASE(RIFK_DENSE_BUF, MER_STEP_VERLET, 0) MER_CASE(RIFK_DENSE_BUF, MER_STEP_RK4, 0)
-    MER_CASE(RIFK_CELL8, MER_STEP_VERLET, 0) MER_CASE(RIFK_CELL8, MER_STEP_RK4, 0)
-    MER_CASE(RIFK_CELL8_BUF, MER_STEP_VERLET, 0) MER_CASE(RIFK_CELL8_BUF, MER_STEP_RK4, 0)
-    MER_CASE(MER_RIF_BSPLINE3, MER_STEP_VERLET, 0) MER_CASE(MER_RIF_BSPLINE3, MER_STEP_RK4, 0)
-#undef MER_CASE
+    int rc = 0;
+    const bool known = match_constant(FetchKinds(), rif_fetch_kind(ctx, sc), [&](auto rif) {
+        return match_constant(Steppers(), sc->stepper, [&](auto stepper) {
+            rc = grid ? f(std::integral_constant<bool, true>(), rif, stepper, std::integral_constant<int, MER_SIGMA_GRID>(), std::integral_constant<int, 0>())
+                      : f(std::integral_constant<bool, true>(), rif, stepper, std::integral_constant<int, MER_SIGMA_HOMOGENEOUS>(), std::integral_constant<int, 0>());
+            return true;
+        });
+    });
+    if (known) return rc;
     return fail(ctx, "unsupported rif_mode / stepper combination");
 }
 }  // namespace mer
@@ -834,38 +259,36 @@ static int check_desc(mer_context *ctx, const mer_grid_desc *d) {
     {   // world_to_volume: all zeros (identity) or an invertible affine map
         const float *W = d->world_to_volume; bool zero = true, finite = true;
         for (int i = 0; i < 12; i++) { zero = zero && W[i] == 0.0f; finite = finite && std::isfinite(W[i]); }
-        const double det = (double) W[0] * ((double) W[5] * W[10] - (double) W[6] * W[9]) - (double) W[1] * ((double) W[4] * W[10] - (double) W[6] * W[8]) +
-                           (double) W[2] * ((double) W[4] * W[9] - (double) W[5] * W[8]);
-        if (!zero && (!finite || !(std::fabs(det) > 1e-12))) return fail(ctx, "volume: the toWorld transform is not invertible");
+        double M[3][3];
+        linear3(W, M);
+        if (!zero && (!finite || !(std::fabs(det3(M)) > 1e-12))) return fail(ctx, "volume: the toWorld transform is not invertible");
     }
     return 0;
 }
 
-int mer_volume_upload(mer_context *ctx, const mer_grid_desc *desc, const void *host_data, int32_t layout, mer_volume *out) {
+// one body for both sources of the dense data: host memory, or device memory of this context's GPU
+static int volume_upload(mer_context *ctx, const mer_grid_desc *desc, const void *data, bool from_device, int32_t layout, mer_volume *out) {
     MER_USE_DEVICE(ctx);
-    if (!ctx || !desc || !host_data || !out) return 1;
+    if (!ctx || !desc || !data || !out) return 1;
     if (check_desc(ctx, desc)) return 1;
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     Volume v; v.desc = *desc;
     const size_t n = (size_t) desc->res[0] * desc->res[1] * desc->res[2] * desc->channels;
     v.bytes_dense = n * (desc->dtype == MER_VOL_F32 ? 4 : 1);
     HIP_CHECK(ctx, hipMalloc(&v.dense, v.bytes_dense));
-    HIP_CHECK(ctx, hipMemcpy(v.dense, host_data, v.bytes_dense, hipMemcpyHostToDevice));
+    if (from_device) {
+        HIP_CHECK(ctx, hipMemcpyAsync(v.dense, data, v.bytes_dense, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        HIP_CHECK(ctx, hipMemcpy(v.dense, data, v.bytes_dense, hipMemcpyHostToDevice));
+    }
     return volume_finish(ctx, v, layout, out);
 }
-
+int mer_volume_upload(mer_context *ctx, const mer_grid_desc *desc, const void *host_data, int32_t layout, mer_volume *out) {
+    return volume_upload(ctx, desc, host_data, false, layout, out);
+}
 int mer_volume_upload_dev(mer_context *ctx, const mer_grid_desc *desc, const void *data_dev, int32_t layout, mer_volume *out) {
-    MER_USE_DEVICE(ctx);
-    if (!ctx || !desc || !data_dev || !out) return 1;
-    if (check_desc(ctx, desc)) return 1;
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    Volume v; v.desc = *desc;
-    const size_t n = (size_t) desc->res[0] * desc->res[1] * desc->res[2] * desc->channels;
-    v.bytes_dense = n * (desc->dtype == MER_VOL_F32 ? 4 : 1);
-    HIP_CHECK(ctx, hipMalloc(&v.dense, v.bytes_dense));
-    HIP_CHECK(ctx, hipMemcpyAsync(v.dense, data_dev, v.bytes_dense, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return volume_finish(ctx, v, layout, out);
+    return volume_upload(ctx, desc, data_dev, true, layout, out);
 }
 
 int mer_volume_build_spline(mer_context *ctx, mer_volume h) {
@@ -1199,19 +622,13 @@ int mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0,
     if (a.upload(p0, n * 12) || b.upload(d0, n * 12) || c.upload(dist, n * 4) || op.alloc(n * 12) || ov.alloc(n * 12) ||
         od.alloc(n * 4) || oo.alloc(n * 4) || ok.alloc(n * 4)) return 1;
     const int rifk = rif_fetch_kind(ctx, scene);
-#define MER_TRACE_CASE(R, S)                                                                                       \
-    if (rifk == R && scene->stepper == S)                                                                          \
-        hipLaunchKernelGGL((er_trace_kernel<R, S>), dim3(nblocks(n, 64)), dim3(64), 0, ctx->stream, P, a.as<float>(), b.as<float>(), \
-                           c.as<float>(), n, op.as<float>(), ov.as<float>(), od.as<float>(), oo.as<float>(), ok.as<int32_t>());
-    MER_TRACE_CASE(MER_RIF_TRILINEAR, MER_STEP_VERLET) MER_TRACE_CASE(MER_RIF_TRILINEAR, MER_STEP_RK4)
-    MER_TRACE_CASE(RIFK_DENSE_BUF, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_DENSE_BUF, MER_STEP_RK4)
-    MER_TRACE_CASE(RIFK_CELL8, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_CELL8, MER_STEP_RK4)
-    MER_TRACE_CASE(RIFK_CELL8_BUF, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_CELL8_BUF, MER_STEP_RK4)
-    MER_TRACE_CASE(RIFK_BRICK27_BUF, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_BRICK27_BUF, MER_STEP_RK4)      // the bench layout (< 4 GiB: buffer loads)
-    MER_TRACE_CASE(RIFK_BRICK27, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_BRICK27, MER_STEP_RK4)
-    MER_TRACE_CASE(MER_RIF_BSPLINE3, MER_STEP_VERLET) MER_TRACE_CASE(MER_RIF_BSPLINE3, MER_STEP_RK4)
-    MER_TRACE_CASE(RIFK_ACOUSTIC, MER_STEP_VERLET) MER_TRACE_CASE(RIFK_ACOUSTIC, MER_STEP_RK4)
-#undef MER_TRACE_CASE
+    match_constant(FetchKinds(), rifk, [&](auto rif) {
+        return match_constant(Steppers(), scene->stepper, [&](auto stepper) {
+            hipLaunchKernelGGL((er_trace_kernel<decltype(rif)::value, decltype(stepper)::value>), dim3(nblocks(n, 64)), dim3(64), 0, ctx->stream, P, a.as<float>(), b.as<float>(),
+                               c.as<float>(), n, op.as<float>(), ov.as<float>(), od.as<float>(), oo.as<float>(), ok.as<int32_t>());
+            return true;
+        });
+    });
     HIP_CHECK(ctx, hipGetLastError());
     if (op.download(out_p, n * 12) || ov.download(out_v, n * 12) || od.download(out_dist_surf, n * 4) || oo.download(out_opt, n * 4) ||
         ok.download(out_success, n * 4)) return 1;
@@ -1314,15 +731,15 @@ int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k,
     const float *I = scene->emitters[k].intensity;
     DevBuf a(ctx), r(ctx);
     if (a.upload(ref, n * 12) || r.alloc(n * 32)) return 1;
-    hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, (const DSpot *) (P.has_spot ? P.rects + MER_MAX_EMITTERS : nullptr), slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
+    hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, P.has_spot ? &ctx->etab->spots[0] : (const DSpot *) nullptr, slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
     return r.download(out, n * 32);
 }
-// the scene's envmap record in device memory (make_params has put it behind the spot table), or NULL
+// the scene's envmap record in device memory (the emitter table's), or NULL
 static const DEnvMap *envmap_of(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
     if (make_params(ctx, scene, P, true)) return nullptr;
     if (!P.has_envmap) { fail(ctx, std::string(who) + ": the scene's emitter list has no envmap entry"); return nullptr; }
-    return (const DEnvMap *) ((const unsigned char *) (P.rects + MER_MAX_EMITTERS) + sizeof(DSpot) * MER_MAX_EMITTERS);
+    return &ctx->etab->env;
 }
 int mer_envmap_eval(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_rgb, float *out_pdf) {
     MER_USE_DEVICE(ctx);

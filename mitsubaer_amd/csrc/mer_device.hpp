@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include "../../include/mer.h"
 
 #define MER_EPSILON 1e-4f                 // include/mitsuba/core/constants.h:25-31 (single precision)
@@ -677,7 +678,7 @@ __device__ __forceinline__ SegQueue pick_queue(const SegQueue (&q)[2], uint32_t 
 }
 
 // MaxExpDist (src/medium/maxexp.h:28-98): the distance distribution proportional to max_i sigma_i exp(-sigma_i t) over the three
-// channels (`strategy = maximum` of homogeneous / heterogeneousrefractive).  Tables built on the host (mer_api.hip) as :30-58.
+// channels (`strategy = maximum` of homogeneous / heterogeneousrefractive).  Tables built on the host (mer_scene.hip) as :30-58.
 struct MaxExp {
     float sigmaT[3], cdf[4], intervalStart[3], normalization, invNormalization;
 };
@@ -716,6 +717,12 @@ struct DEnvMap {
     float pad[2];
 };
 static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144 && sizeof(DSpot) == 32 && sizeof(DEnvMap) == 144, "emitter records: 16-byte multiples");
+// A context's emitter buffer in device memory: Params.points and Params.rects point at its first two tables, and the kernels find the cones
+// and the envmap record by stepping over the rectangles (spot_table, envmap_rec).  The host fills and uploads it as one value (mer_scene.hip).
+struct EmitterTable { DPoint points[MER_MAX_EMITTERS]; DRect rects[MER_MAX_EMITTERS]; DSpot spots[MER_MAX_EMITTERS]; DEnvMap env; };
+static_assert(offsetof(EmitterTable, spots) == offsetof(EmitterTable, rects) + sizeof(DRect) * MER_MAX_EMITTERS, "spot_table: the cones follow the rectangle table");
+static_assert(offsetof(EmitterTable, env) == offsetof(EmitterTable, spots) + sizeof(DSpot) * MER_MAX_EMITTERS, "envmap_rec: the envmap record follows the cones");
+static_assert(sizeof(EmitterTable) == offsetof(EmitterTable, env) + sizeof(DEnvMap), "emitter table: no padding (the host compares it bytewise)");
 
 // Everything a render / leaf kernel needs, passed by value as the kernel argument.
 struct Params {
@@ -1102,7 +1109,7 @@ __device__ __forceinline__ float spot_falloff(const DSpot &s, f3 d) {
     if (cosTheta >= s.cos_beam) return 1.0f;
     return (s.cutoff - acosf(cosTheta)) * s.inv_width;
 }
-// the cones of the point-table slots (make_params stores them behind the MER_MAX_EMITTERS rectangle records), or NULL without a spot emitter
+// the cones of the point-table slots (EmitterTable::spots, behind the MER_MAX_EMITTERS rectangle records), or NULL without a spot emitter
 __device__ __forceinline__ const DSpot *spot_table(const Params &P) {
     return P.has_spot ? (const DSpot *) (P.rects + MER_MAX_EMITTERS) : nullptr;
 }
@@ -1112,7 +1119,7 @@ __device__ __forceinline__ float point_falloff(const DSpot *spots, int k, f3 d) 
 }
 // ---- emitter `envmap` (src/emitters/envmap.cpp).  Level-0 bilinear look-ups everywhere: the reference's EWA filtering of camera rays that keep
 // their differentials (:390-409) is not built.
-// the envmap record (make_params stores it behind the MER_MAX_EMITTERS spot records)
+// the envmap record (EmitterTable::env, behind the MER_MAX_EMITTERS spot records)
 __device__ __forceinline__ const DEnvMap &envmap_rec(const Params &P) {
     return *(const DEnvMap *) ((const unsigned char *) (P.rects + MER_MAX_EMITTERS) + sizeof(DSpot) * MER_MAX_EMITTERS);
 }

@@ -1,6 +1,6 @@
 // mer_internal.hpp -- host-side state of libmer.so shared by its translation units (mer_api.hip: context, volumes, film, leaf entry
-// points; mer_render.hip: the wavefront host loop; mer_render_*.hip: the kernel instantiations, one group per file so that they
-// compile in parallel).  Nothing here is part of the C-ABI (include/mer.h).
+// points; mer_scene.hip: scene flattening, make_params; mer_render.hip: the wavefront host loop; mer_render_*.hip: the kernel
+// instantiations, one group per file so that they compile in parallel).  Nothing here is part of the C-ABI (include/mer.h).
 #pragma once
 #include "mer_device.hpp"
 #include <cstdio>
@@ -82,9 +82,8 @@ struct mer_context {
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
-    // point / area emitter tables on the device (MER_MAX_EMITTERS DPoint records, then as many DRect records), the bytes they hold, and
-    // whether a point emitter of the last make_params lies outside the (cube / sphere) medium shape
-    void *etab = nullptr; std::vector<unsigned char> etab_host; bool point_outside = false;
+    // the emitter table on the device (points, rectangles, spot cones, the envmap record: mer_device.hpp) and the value it holds, once uploaded
+    mer::EmitterTable *etab = nullptr; mer::EmitterTable etab_host; bool etab_valid = false;
     unsigned long long *chk = nullptr;           // MER_BOUNDS_CHECK build: violation record (count, kind, index, limit)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -110,9 +109,16 @@ namespace mer {
 static inline int fail(mer_context *ctx, const std::string &msg) { ctx->error = msg; return 1; }
 static inline unsigned nblocks(int64_t n, int bs = 256) { return (unsigned) std::max<int64_t>(1, (n + bs - 1) / bs); }
 
-// mer_api.hip
+// mer_scene.hip: scene flattening (host only)
+// linear part of a row-major 3x4 float matrix in double; determinant and inverse (returns the determinant) of a 3x3 matrix by cofactors
+static inline void linear3(const float m[12], double M[3][3]) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[i][j] = m[4 * i + j]; }
+double det3(const double M[3][3]);
+double inverse3(const double M[3][3], double inv[3][3]);
 void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g);
-int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf = false);
+// point_outside (optional): a point emitter of the scene lies outside the cube / sphere medium shape (launch_render picks the connect kernel by it)
+int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf = false, bool *point_outside = nullptr);
+int film_frames(mer_context *ctx, const mer_scene_desc *sc, int &frames);
+int check_rough(mer_context *ctx, const mer_scene_desc *sc);
 // internal fetch kind (RIFK_*) of the scene's trilinear RIF volume, or the rif_mode itself for the other modes
 int rif_fetch_kind(mer_context *ctx, const mer_scene_desc *sc);
 

@@ -114,8 +114,8 @@ __global__ void __launch_bounds__(MER_BLOCK) msort_scatter_kernel(const Params P
 
 int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
                   uint64_t n_film, uint64_t n_path_out) {
-    Params P;
-    if (make_params(ctx, scene, P, true)) return 1;
+    Params P; bool point_outside = false;
+    if (make_params(ctx, scene, P, true, &point_outside)) return 1;
     if (!shard || shard->spp_count < 0 || shard->spp_stride <= 0 || shard->tile_count <= 0 || shard->tile_rank < 0 ||
         shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
         return fail(ctx, "invalid shard");
@@ -156,7 +156,7 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     const bool connect_stage = has_point && curved && scene->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC;   // a rough boundary: the surface vertex samples the emitter
     // any point emitter outside the shape is reached through the boundary: the kernel that carries the refraction code (it connects to emitters
     // inside the shape as well; signed-distance shapes: the plain kernel carries it too, the side is tested per connection)
-    if (connect_stage && ctx->point_outside) ks.connect = ks.connect_cross;
+    if (connect_stage && point_outside) ks.connect = ks.connect_cross;
 
     // spawned side walks (mer_wavefront.hpp): the plain curved kernels hand luminaire-sample / look-up walks to side-walk slots -- four per path, behind
     // the path slots -- when the render is a steady-state film with an environment to reach (per-path output keeps every walk in the path's own lane:
