@@ -197,8 +197,9 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
         bool hit = false;
         if (w < P.total_work) {
             int x, y; uint32_t sample;
-            if (P.gen_all) hit = true;
-            else if (decode_work(P, w, x, y, sample)) {
+            const bool inside = decode_work(P, w, x, y, sample);      // a work id of a partial tile may fall outside the image: nobody's sample
+            if (P.gen_all) hit = inside;                               // (K_event replays the id without this test)
+            else if (inside) {
                 Rng rng; rng.seed(P.seed, (uint32_t) (y * S.width + x), sample);
                 const float sx = rng.next1D(), sy = rng.next1D();
                 const float px = (float) x + sx, py = (float) y + sy;
