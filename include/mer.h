@@ -74,9 +74,24 @@ typedef struct {
    env_radiance.  envmap = a handle of mer_envmap_upload, env_scale = its `scale`, env_reserved = 0; to_world = its `toWorld` (row-major 3x4,
    the linear part a rotation within 1e-5, the translation ignored).  It takes the constant environment's place at every site: camera-ray
    and path escapes, the luminaire sample at each collision (its selection probability is 1: sampling_weight must be > 0 but does not
-   scale it) and the phase-sampled look-up, with pdfDirect as the MIS partner.  Curved rays: DESIGN.md section 1. */
+   scale it) and the phase-sampled look-up, with pdfDirect as the MIS partner.  Curved rays: DESIGN.md section 1.
+   MER_EMITTER_AREA_DISK / MER_EMITTER_AREA_SPHERE: emitter `area` on a `disk` (src/shapes/disk.cpp:101-255) or a `sphere`
+   (src/shapes/sphere.cpp:108-387) -- list entries only, with the fields of MER_EMITTER_AREA (to_world, radiance, sampling_weight).  The disk
+   is the image of the unit disk in z = 0 under to_world, its normal to_world(Normal(0,0,1)); shear or a u / v scale that differs by more
+   than 1e-3 is refused with the reference's messages; 1 / area = 1 / (pi |to_world e_x|^2).  The sphere has its centre at the translation
+   column and the radius |to_world e_x|; its rotation is irrelevant, and a linear part that is not a uniform scale of a rotation (1e-3) is
+   refused.  A linear part of negative determinant flips the normals (the reference's flipNormals; a rectangle's normal flips the same
+   way): a flipped sphere emits inward.  Rectangles, disks and spheres are ONE kind: one selection CDF over their sampling weights in list
+   order, two sampler numbers per sample, one-sided emission (area.cpp:104-109,158-183), all-absorbing occluders.  A sphere is sampled by
+   Sphere::sampleDirect (the cone of directions from outside, uniformly by area from inside), so its pdfDirect depends on the reference
+   point.  Every shape must be clear of the medium shape: an outward sphere apart from it (sphere boundary: centre distance > the sum of
+   the radii; cube: distance from the centre to the box > radius); a flipped sphere apart from it or around it (centre distance + the
+   boundary's radius < radius; cube: its farthest corner closer than the radius); a disk outside it (sphere boundary: the disk's point
+   closest to the centre lies outside -- exact; cube: the disk's circumscribed square passes the rectangle / box test -- conservative: a
+   disk near a cube's edge or corner can be refused although it does not touch).  Same scope as the rectangle: rif_mode = MER_RIF_CONST,
+   index-matched cube / sphere boundary, no point or spot emitter outside the medium shape in the same list. */
 #define MER_MAX_EMITTERS 32
-enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3, MER_EMITTER_ENVMAP = 4 };
+enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3, MER_EMITTER_ENVMAP = 4, MER_EMITTER_AREA_DISK = 5, MER_EMITTER_AREA_SPHERE = 6 };
 typedef struct {
     int32_t type;
     float   position[3], intensity[3];
@@ -345,6 +360,16 @@ int  mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1,
    spot) at n reference points ref[3*i..]: out stride 8: value RGB (intensity x falloff / dist^2, NOT divided by the selection pdf), the unit
    direction to the emitter [3], the distance, the falloff (1 for a point).  The render kernels' own device function. */
 int  mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, int64_t n, float *out);
+/* AreaLight::sampleDirect (src/emitters/area.cpp:158-173) through Shape / Sphere::sampleDirect (shape.cpp:102-115, sphere.cpp:286-355) of
+   entry k of the scene's emitter list (an area emitter on a rectangle, disk or sphere) at n reference points ref[3*i..] with the samples
+   u2[2*i..]: out stride 12: radiance / pdf RGB (NOT divided by the selection pdf; 0 from the back side), the unit direction d[3], the
+   distance, the solid-angle pdf (0 from the back side), the normal n[3] at the sampled point, 0.  The render kernels' own device function. */
+int  mer_area_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, const float *u2, int64_t n, float *out);
+/* Scene::rayIntersect restricted to the area emitters' shapes, then AreaLight::eval and pdfDirect (area.cpp:104-109,175-183): the nearest
+   rectangle, disk or sphere along o[3*i..] + t d[3*i..], t >= 0 (d need not be unit: t is in its units); out stride 8: the entry's index in
+   the emitter list or -1, t, the radiance seen along d RGB (0 from the back side), pdfDirect of the hit point from the reference point
+   ref[3*i..] in the solid-angle measure (without the selection pdf), 0, 0.  The render kernels' own device functions. */
+int  mer_area_hit(mer_context *ctx, const mer_scene_desc *scene, const float *o, const float *d, const float *ref, int64_t n, float *out);
 /* EnvironmentMap::evalEnvironment (level 0, bilinear) and pdfDirect (envmap.cpp:385-415, 531-645) of the scene's envmap entry for n world
    directions dirs[3*i..] (need not be unit): out_rgb[3*i..] = value x scale, out_pdf[i] = the solid-angle density of the luminaire
    sample.  The render kernels' own device functions. */

@@ -22,7 +22,7 @@ SYMBOLS = [
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
-    "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_envmap_upload", "mer_envmap_eval", "mer_envmap_sample", "mer_multi_envmap_upload", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
+    "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_area_direct", "mer_area_hit", "mer_envmap_upload", "mer_envmap_eval", "mer_envmap_sample", "mer_multi_envmap_upload", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
     "mer_rough_dielectric_sample", "mer_camera_rays", "mer_sensor_rays",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
@@ -185,6 +185,32 @@ def _rect_meets_shape(p, m):
     return True
 
 
+def _disk_outside(p, m):
+    """the disk O + a U + b V, a^2 + b^2 <= 1, lies outside the medium shape: its point closest to the sphere's centre lies outside (exact);
+    against the cube its circumscribed square must pass the rectangle / box test (conservative)"""
+    if p.boundary != P.BOUNDARY_SPHERE:
+        return not _rect_meets_shape(p, m)
+    U, V, O = m[:, 0], m[:, 1], m[:, 3]
+    d = np.asarray(p.sph_center, np.float64) - O
+    a, b = np.dot(d, U) / np.dot(U, U), np.dot(d, V) / np.dot(V, V)
+    r = np.hypot(a, b)
+    if r > 1:
+        a, b = a / r, b / r
+    q = a * U + b * V - d
+    return not float(np.dot(q, q)) < float(p.sph_radius) ** 2
+
+
+def _sphere_clear(p, c, R, flipped):
+    """the sphere (centre c, radius R) is clear of the medium shape: apart from it, or -- flipped only -- around it"""
+    if p.boundary == P.BOUNDARY_SPHERE:
+        d = float(np.linalg.norm(c - np.asarray(p.sph_center, np.float64)))
+        return d > R + p.sph_radius or (flipped and d + p.sph_radius < R)
+    lo, hi = np.asarray(p.bmin, np.float64), np.asarray(p.bmax, np.float64)
+    near = np.maximum(np.maximum(lo - c, c - hi), 0.0)
+    far = np.maximum(np.abs(c - lo), np.abs(c - hi))
+    return float(np.dot(near, near)) > R * R or (flipped and float(np.dot(far, far)) < R * R)
+
+
 def _point_in_shape(p, x):
     x = np.asarray(x, np.float32)
     if p.boundary == P.BOUNDARY_AABB:
@@ -226,14 +252,25 @@ def validate_emitters(p):
             if p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC and inside:
                 raise MerError(at + "hroughdielectric: the spot emitter must lie outside the medium shape")
             outside_point = outside_point or (p.boundary != P.BOUNDARY_SDF and not inside)
-        elif e["type"] == P.EMITTER_AREA:
+        elif e["type"] in P.AREA_TYPES:
             if p.rif_mode != P.RIF_CONST:
                 raise MerError(at + "the area emitter is built for straight rays (rif_mode = CONST)")
             if p.boundary_bsdf != P.BSDF_NULL or p.boundary == P.BOUNDARY_SDF:
                 raise MerError(at + "the area emitter needs an index-matched cube / sphere boundary")
             if not all(v >= 0 for v in e["radiance"]):
                 raise MerError(at + "emitter radiance / intensity must be non-negative")
-            if _rect_meets_shape(p, np.array(_rows3x4(e.get("to_world")), np.float64).reshape(3, 4)):
+            if e["type"] != P.EMITTER_AREA:
+                err = P.area_shape_error(e["type"], e.get("to_world"))
+                if err:
+                    raise MerError(at + err)
+            m = np.array(_rows3x4(e.get("to_world")), np.float64).reshape(3, 4)
+            if e["type"] == P.EMITTER_AREA_SPHERE:
+                if not _sphere_clear(p, m[:, 3], float(np.float32(np.linalg.norm(m[:, 0]))), np.linalg.det(m[:, :3]) < 0):
+                    raise MerError(at + "the area emitter's sphere must be clear of the medium shape (apart from it, or with inward normals around it)")
+            elif e["type"] == P.EMITTER_AREA_DISK:
+                if not _disk_outside(p, m):
+                    raise MerError(at + "the area emitter's disk must lie outside the medium shape")
+            elif _rect_meets_shape(p, m):
                 raise MerError(at + "the area emitter's rectangle must lie outside the medium shape")
             has_rect = True
         elif e["type"] == P.EMITTER_ENVMAP:
@@ -659,6 +696,27 @@ class Context:
         ref = _f32(ref).reshape(-1, 3); n = ref.shape[0]
         out = np.zeros((n, 8), np.float32)
         self._check(self.lib.mer_emitter_direct(self.h, C.byref(scene), C.c_int32(k), _fp(ref), C.c_int64(n), _fp(out)))
+        return out
+
+    def area_direct(self, scene, k, ref, u2):
+        """mer_area_direct: sampleDirect of emitter-list entry k (an area emitter on a rectangle, disk or sphere) at the reference points ref
+        (n x 3) with the samples u2 (n x 2); (n, 12) float32: radiance / pdf RGB (not divided by the selection pdf), d, dist, the solid-angle
+        pdf, the normal at the sampled point, 0"""
+        ref = _f32(ref).reshape(-1, 3); u = _f32(u2).reshape(-1, 2); n = ref.shape[0]
+        if u.shape[0] != n:
+            raise ValueError("area_direct: ref and u2 must have the same length")
+        out = np.zeros((n, 12), np.float32)
+        self._check(self.lib.mer_area_direct(self.h, C.byref(scene), C.c_int32(k), _fp(ref), _fp(u), C.c_int64(n), _fp(out)))
+        return out
+
+    def area_hit(self, scene, o, d, ref):
+        """mer_area_hit: the nearest area-emitter shape along o + t d, t >= 0 (n x 3 each); (n, 8) float32: list index or -1, t, the radiance
+        seen along d RGB, pdfDirect of the hit point from ref (solid angle, without the selection pdf), 0, 0"""
+        o = _f32(o).reshape(-1, 3); d = _f32(d).reshape(-1, 3); ref = _f32(ref).reshape(-1, 3); n = o.shape[0]
+        if d.shape[0] != n or ref.shape[0] != n:
+            raise ValueError("area_hit: o, d and ref must have the same length")
+        out = np.zeros((n, 8), np.float32)
+        self._check(self.lib.mer_area_hit(self.h, C.byref(scene), _fp(o), _fp(d), _fp(ref), C.c_int64(n), _fp(out)))
         return out
 
     def eval_transmittance(self, scene, o, d, maxt, seed):

@@ -735,6 +735,38 @@ int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k,
     HIP_CHECK(ctx, hipGetLastError());
     return r.download(out, n * 32);
 }
+static bool is_area_type(int type) { return type == MER_EMITTER_AREA || type == MER_EMITTER_AREA_DISK || type == MER_EMITTER_AREA_SPHERE; }
+int mer_area_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, const float *u2, int64_t n, float *out) {
+    MER_USE_DEVICE(ctx);
+    if (scene->n_emitters <= 0 || !scene->emitters) return fail(ctx, "mer_area_direct: the scene has no emitter list");
+    if (k < 0 || k >= scene->n_emitters) return fail(ctx, "mer_area_direct: entry index out of range");
+    if (!is_area_type(scene->emitters[k].type)) return fail(ctx, "mer_area_direct: entry k must be an area emitter");
+    int slot = 0;                                   // its slot of the area table: the area entries before it, in list order
+    for (int j = 0; j < k; ++j) slot += is_area_type(scene->emitters[j].type) ? 1 : 0;
+    Params P;
+    if (make_params(ctx, scene, P, true)) return 1;
+    if (n <= 0) return 0;
+    DevBuf a(ctx), b(ctx), r(ctx);
+    if (a.upload(ref, n * 12) || b.upload(u2, n * 8) || r.alloc(n * 48)) return 1;
+    hipLaunchKernelGGL(area_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.rects, slot, a.as<float>(), b.as<float>(), n, r.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    return r.download(out, n * 48);
+}
+int mer_area_hit(mer_context *ctx, const mer_scene_desc *scene, const float *o, const float *d, const float *ref, int64_t n, float *out) {
+    MER_USE_DEVICE(ctx);
+    if (scene->n_emitters <= 0 || !scene->emitters) return fail(ctx, "mer_area_hit: the scene has no emitter list");
+    Params P;
+    if (make_params(ctx, scene, P, true)) return 1;
+    if (!P.n_rect) return fail(ctx, "mer_area_hit: the scene's emitter list has no area emitter");
+    if (n <= 0) return 0;
+    int32_t list_index[MER_MAX_EMITTERS] = {0};
+    for (int j = 0, slot = 0; j < scene->n_emitters; ++j) if (is_area_type(scene->emitters[j].type)) list_index[slot++] = j;
+    DevBuf a(ctx), b(ctx), c(ctx), x(ctx), r(ctx);
+    if (a.upload(o, n * 12) || b.upload(d, n * 12) || c.upload(ref, n * 12) || x.upload(list_index, sizeof(list_index)) || r.alloc(n * 32)) return 1;
+    hipLaunchKernelGGL(area_hit_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, x.as<int32_t>(), a.as<float>(), b.as<float>(), c.as<float>(), n, r.as<float>());
+    HIP_CHECK(ctx, hipGetLastError());
+    return r.download(out, n * 32);
+}
 // the scene's envmap record in device memory (the emitter table's), or NULL
 static const DEnvMap *envmap_of(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
     if (make_params(ctx, scene, P, true)) return nullptr;

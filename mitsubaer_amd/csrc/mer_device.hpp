@@ -699,8 +699,12 @@ __device__ __forceinline__ float maxexp_cdf(const MaxExp &m, float t) {         
 // One point emitter of a context's device table (make_params): position, intensity / pdf, the probability pdf with which it is selected
 // among the point emitters (sampling_weight / sum), and the upper end of its interval of the selection CDF.
 struct DPoint { float pos[3], Ie[3], pdf, cdf; };
-// One area emitter (`rectangle`): objectToWorld, its inverse, the frame normal, 1 / area, radiance, selection pdf, radiance / pdf, CDF bound.
-struct DRect { float o2w[12], w2o[12], n[3], inv_area, L[3], pdf, Le[3], cdf; };
+// One area emitter: objectToWorld, its inverse, the frame normal, 1 / area, radiance, selection pdf, radiance / pdf, CDF bound, and the shape
+// that carries it (the record keeps the name of its first shape).  AREA_RECT: the image of [-1,1]^2 x {0}; AREA_DISK: of the unit disk in
+// z = 0; AREA_SPHERE: centre = the translation column of o2w, `radius`, flip = -1 when the normals point inward (else +1); its w2o and n
+// are not read.
+enum { AREA_RECT = 0, AREA_DISK = 1, AREA_SPHERE = 2 };
+struct DRect { float o2w[12], w2o[12], n[3], inv_area, L[3], pdf, Le[3], cdf; int32_t shape; float radius, flip, pad; };
 // The cone of the point-table slot with the same index (emitter `spot`, src/emitters/spot.cpp:66-118), derived in float as SpotEmitter's
 // constructor / configure() do: z row of the inverse of toWorld's linear part, cos(cutoff), cos(beamWidth), cutoff (radians),
 // 1 / (cutoff - beamWidth).  A point emitter's slot holds z = 0 and both cosines -2: its falloff is exactly 1.
@@ -716,7 +720,7 @@ struct DEnvMap {
     float norm, scale, w2l[9], l2w[9], pix[2];
     float pad[2];
 };
-static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 144 && sizeof(DSpot) == 32 && sizeof(DEnvMap) == 144, "emitter records: 16-byte multiples");
+static_assert(sizeof(DPoint) == 32 && sizeof(DRect) == 160 && sizeof(DSpot) == 32 && sizeof(DEnvMap) == 144, "emitter records: 16-byte multiples");
 // A context's emitter buffer in device memory: Params.points and Params.rects point at its first two tables, and the kernels find the cones
 // and the envmap record by stepping over the rectangles (spot_table, envmap_rec).  The host fills and uploads it as one value (mer_scene.hip).
 struct EmitterTable { DPoint points[MER_MAX_EMITTERS]; DRect rects[MER_MAX_EMITTERS]; DSpot spots[MER_MAX_EMITTERS]; DEnvMap env; };
@@ -1058,18 +1062,36 @@ __device__ __forceinline__ bool dielectric_event(const Params &P, Rng &rng, f3 r
     return cosT < 0;
 }
 
-// ---- emitter `area` on a `rectangle` shape (src/emitters/area.cpp:67-187, src/shapes/rectangle.cpp:99-222, src/librender/shape.cpp:102-126)
-// Rectangle::rayIntersect (:125-148): t in [mint, maxt] or -1
+// ---- emitter `area` on a `rectangle`, `disk` or `sphere` shape (src/emitters/area.cpp:67-187, src/shapes/rectangle.cpp:99-222, disk.cpp:101-255,
+// sphere.cpp:108-387, src/librender/shape.cpp:102-126).  R.shape is the same for all lanes wherever a loop over the table reads it.
+// Sphere::rayIntersect (sphere.cpp:163-187), in double as the reference solves it: the near root, or the far one when the near one lies
+// before mint; t in [mint, maxt] or -1
+__device__ __forceinline__ float sphere_intersect(const DRect &R, f3 o, f3 d, float mint, float maxt) {
+    const double ox = (double) o.x - (double) R.o2w[3], oy = (double) o.y - (double) R.o2w[7], oz = (double) o.z - (double) R.o2w[11];
+    const double dx = d.x, dy = d.y, dz = d.z;
+    const double A = dx * dx + dy * dy + dz * dz, B = 2 * (ox * dx + oy * dy + oz * dz), C = ox * ox + oy * oy + oz * oz - (double) R.radius * (double) R.radius;
+    const double discrim = B * B - 4 * A * C;
+    if (!(A > 0) || !(discrim >= 0)) return -1.0f;
+    const double root = sqrt(discrim), temp = -0.5 * (B < 0 ? B - root : B + root);          // the root of larger magnitude first (util.cpp:487-525)
+    double nearT = temp / A, farT = C / temp;
+    if (nearT > farT) { const double s = nearT; nearT = farT; farT = s; }
+    if (!(nearT <= (double) maxt && farT >= (double) mint)) return -1.0f;
+    if (nearT < (double) mint) return farT > (double) maxt ? -1.0f : (float) farT;
+    return (float) nearT;
+}
+// Rectangle::rayIntersect (:125-148), Disk::rayIntersect (disk.cpp:139-162), Sphere::rayIntersect: t in [mint, maxt] or -1
 __device__ __forceinline__ float rect_intersect(const DRect &R, f3 o, f3 d, float mint, float maxt) {
+    if (R.shape == AREA_SPHERE) return sphere_intersect(R, o, d, mint, maxt);
     const float *W = R.w2o;
     const float oz = W[8] * o.x + W[9] * o.y + W[10] * o.z + W[11], dz = W[8] * d.x + W[9] * d.y + W[10] * d.z;
     const float hit = -oz / dz;
     if (!(hit >= mint && hit <= maxt)) return -1.0f;
     const float lx = (W[0] * o.x + W[1] * o.y + W[2] * o.z + W[3]) + hit * (W[0] * d.x + W[1] * d.y + W[2] * d.z),
                 ly = (W[4] * o.x + W[5] * o.y + W[6] * o.z + W[7]) + hit * (W[4] * d.x + W[5] * d.y + W[6] * d.z);
+    if (R.shape == AREA_DISK) return lx * lx + ly * ly <= 1 ? hit : -1.0f;
     return (fabsf(lx) <= 1 && fabsf(ly) <= 1) ? hit : -1.0f;
 }
-// the nearest of the scene's rectangles along o + t d, t in [mint, maxt]: t or -1, and its index in k (ties: the first listed).  The loop
+// the nearest of the scene's area-emitter shapes along o + t d, t in [mint, maxt]: t or -1, and its index in k (ties: the first listed).  The loop
 // index is wave-uniform, so all lanes of a wave read the same record address; the compiler emits vector loads with a uniform address (not
 // s_load: the kernels also write global memory, so the table is not provably invariant) -- one cache line per wave and record.
 __device__ __forceinline__ float rect_nearest(const Params &P, f3 o, f3 d, float mint, float maxt, int &k) {
@@ -1080,7 +1102,7 @@ __device__ __forceinline__ float rect_nearest(const Params &P, f3 o, f3 d, float
     }
     return best;
 }
-// does any rectangle other than `skip` cross o + t d, t in [mint, maxt]?  (skip = -1: any rectangle)
+// does any area-emitter shape other than `skip` cross o + t d, t in [mint, maxt]?  (skip = -1: any shape)
 __device__ __forceinline__ bool rect_blocks(const Params &P, f3 o, f3 d, float mint, float maxt, int skip) {
     bool hit = false;
     for (int j = 0; j < P.n_rect; ++j)
@@ -1207,36 +1229,94 @@ template <bool EXTRA>
 __device__ __forceinline__ f3 env_along(const Params &P, f3 env, f3 d) {
     return (EXTRA && P.has_envmap) ? envmap_value(envmap_rec(P), d) : env;
 }
-// AreaLight::eval (area.cpp:102-107): the radiance a ray travelling along d picks up on the rectangle (one-sided)
-__device__ __forceinline__ f3 rect_le(const DRect &R, f3 d) {
-    const f3 n(R.n[0], R.n[1], R.n[2]);
+// the shape's normal at its surface point p: the frame normal of a rectangle or disk (p is not read), normalize(p - centre) x flip of a sphere
+__device__ __forceinline__ f3 area_normal(const DRect &R, f3 p) {
+    if (R.shape == AREA_SPHERE) return normalize(f3(p.x - R.o2w[3], p.y - R.o2w[7], p.z - R.o2w[11])) * R.flip;
+    return f3(R.n[0], R.n[1], R.n[2]);
+}
+// AreaLight::eval (area.cpp:104-109): the radiance a ray travelling along d picks up at the shape's point p (one-sided)
+__device__ __forceinline__ f3 rect_le(const DRect &R, f3 p, f3 d) {
+    const f3 n = area_normal(R, p);
     return dot(n, -d) <= 0 ? f3(0, 0, 0) : f3(R.L[0], R.L[1], R.L[2]);
 }
-// Shape::sampleDirect + AreaLight::sampleDirect (shape.cpp:102-115, area.cpp:162-177) for a reference point inside a medium (refN = 0):
-// radiance / pdf (0 on the back side), direction, distance, solid-angle pdf -- of the rectangle selected with probability R.pdf: the
-// radiance is R.Le = L / R.pdf and the pdf includes R.pdf (AreaLight's dRec.pdf *= emPdf; value /= emPdf)
-__device__ __forceinline__ f3 rect_sample_direct(const DRect &R, f3 ref, float sx, float sy, f3 &d, float &dist, float &pdf) {
-    const float *M = R.o2w; const float lx = sx * 2 - 1, ly = sy * 2 - 1;
-    const f3 p(M[0] * lx + M[1] * ly + M[3], M[4] * lx + M[5] * ly + M[7], M[8] * lx + M[9] * ly + M[11]);
-    const f3 n(R.n[0], R.n[1], R.n[2]);
-    d = p - ref;
-    const float distSquared = dot(d, d);
-    dist = sqrtf(distSquared);
-    d = d / dist;
-    const float dp = fabsf(dot(d, n));
-    pdf = R.inv_area * (dp != 0 ? (distSquared / dp) : 0.0f);
+// Sphere::sampleDirect (sphere.cpp:286-355): a reference point outside (sinAlpha < 1 - Epsilon) samples the cone of directions that contains
+// the sphere (warp.cpp:54-63) and finds the point from the plane through the centre (baseT) with the closest-approach fallback; one inside
+// samples the area uniformly (warp.cpp:25-31).  Returns the solid-angle pdf, d, dist and the (flipped) normal n.
+__device__ __forceinline__ float sphere_sample_direct(const DRect &R, f3 ref, float sx, float sy, f3 &d, float &dist, f3 &n) {
+    const f3 c(R.o2w[3], R.o2w[7], R.o2w[11]);
+    const f3 refToCenter = c - ref;
+    const float refDist2 = dot(refToCenter, refToCenter), invRefDist = 1.0f / sqrtf(refDist2), sinAlpha = R.radius * invRefDist;
+    float pdf;
+    if (sinAlpha < 1 - MER_EPSILON) {
+        const float cosAlpha = safe_sqrt(1.0f - sinAlpha * sinAlpha);
+        const float cosTheta = (1 - sx) + sx * cosAlpha, sinTheta = safe_sqrt(1.0f - cosTheta * cosTheta);
+        const float phi = 2.0f * MER_PI * sy, sinPhi = sinf(phi), cosPhi = cosf(phi);
+        const f3 a = refToCenter * invRefDist; f3 s, t;
+        coordinate_system(a, s, t);
+        d = s * (cosPhi * sinTheta) + t * (sinPhi * sinTheta) + a * cosTheta;
+        pdf = (0.5f * MER_INV_PI) / (1 - cosAlpha);                                     // squareToUniformConePdf
+        const float projDist = dot(refToCenter, d), baseT = refDist2 / projDist;
+        const f3 queryToCenter = c - (ref + d * baseT);
+        const float queryDist2 = dot(queryToCenter, queryToCenter), queryProjDist = dot(queryToCenter, d);
+        const float B = -2 * queryProjDist, C = queryDist2 - R.radius * R.radius, discrim = B * B - 4.0f * C;
+        float nearT = queryProjDist;                                                    // no root by roundoff: the closest point of the ray
+        if (discrim >= 0) {
+            const float root = sqrtf(discrim), temp = -0.5f * (B < 0 ? B - root : B + root);
+            nearT = fminf(temp, C / temp);
+        }
+        dist = baseT + nearT;
+        n = normalize(d * nearT - queryToCenter);
+    } else {
+        n = square_to_uniform_sphere(sx, sy);
+        d = c + n * R.radius - ref;
+        const float dist2 = dot(d, d);
+        dist = sqrtf(dist2);
+        d = d / dist;
+        pdf = R.inv_area * dist2 / fabsf(dot(d, n));
+    }
+    n = n * R.flip;
+    return pdf;
+}
+// Shape::sampleDirect + AreaLight::sampleDirect (shape.cpp:102-115, area.cpp:158-173) for a reference point inside a medium (refN = 0):
+// radiance / pdf (0 on the back side), direction, distance, solid-angle pdf, the normal at the sampled point -- of the shape selected with
+// probability R.pdf: the radiance is R.Le = L / R.pdf and the pdf includes R.pdf (AreaLight's dRec.pdf *= emPdf; value /= emPdf).  A
+// rectangle maps (sx, sy) to [-1,1]^2, a disk through the concentric map (disk.cpp:247-255), a sphere has its own sampleDirect.
+__device__ __forceinline__ f3 rect_sample_direct(const DRect &R, f3 ref, float sx, float sy, f3 &d, float &dist, float &pdf, f3 &n) {
+    if (R.shape == AREA_SPHERE) pdf = sphere_sample_direct(R, ref, sx, sy, d, dist, n);
+    else {
+        const float *M = R.o2w; float lx = sx * 2 - 1, ly = sy * 2 - 1;
+        if (R.shape == AREA_DISK) square_to_disk_concentric(sx, sy, lx, ly);
+        const f3 p(M[0] * lx + M[1] * ly + M[3], M[4] * lx + M[5] * ly + M[7], M[8] * lx + M[9] * ly + M[11]);
+        n = f3(R.n[0], R.n[1], R.n[2]);
+        d = p - ref;
+        const float distSquared = dot(d, d);
+        dist = sqrtf(distSquared);
+        d = d / dist;
+        const float dp = fabsf(dot(d, n));
+        pdf = R.inv_area * (dp != 0 ? (distSquared / dp) : 0.0f);
+    }
     if (dot(d, n) < 0 && pdf != 0) { const f3 v = f3(R.Le[0], R.Le[1], R.Le[2]) / pdf; pdf = pdf * R.pdf; return v; }
     pdf = 0.0f;
     return f3(0, 0, 0);
 }
-// AreaLight::pdfDirect (area.cpp:179-187) for a hit at distance dist along d
-__device__ __forceinline__ float rect_pdf_direct(const DRect &R, f3 d, float dist) {
-    const f3 n(R.n[0], R.n[1], R.n[2]);
-    return dot(d, n) < 0 ? R.inv_area * (dist * dist) / fabsf(dot(d, n)) : 0.0f;
+__device__ __forceinline__ f3 rect_sample_direct(const DRect &R, f3 ref, float sx, float sy, f3 &d, float &dist, float &pdf) {
+    f3 n; return rect_sample_direct(R, ref, sx, sy, d, dist, pdf, n);
 }
-// what a ray sees that has left the convex medium shape for good (or never meets it): the nearest rectangle if one is hit -- front side: its
+// AreaLight::pdfDirect (area.cpp:175-183) of the shape's point ref + dist d seen from ref: Shape::pdfDirect (shape.cpp:117-126), or
+// Sphere::pdfDirect (sphere.cpp:357-384), whose density depends on where ref lies
+__device__ __forceinline__ float rect_pdf_direct(const DRect &R, f3 ref, f3 d, float dist) {
+    const f3 n = area_normal(R, ref + d * dist);
+    if (!(dot(d, n) < 0)) return 0.0f;
+    if (R.shape == AREA_SPHERE) {
+        const f3 refToCenter(R.o2w[3] - ref.x, R.o2w[7] - ref.y, R.o2w[11] - ref.z);
+        const float sinAlpha = R.radius * (1.0f / sqrtf(dot(refToCenter, refToCenter)));
+        if (sinAlpha < 1 - MER_EPSILON) return (0.5f * MER_INV_PI) / (1 - safe_sqrt(1.0f - sinAlpha * sinAlpha));
+    }
+    return R.inv_area * (dist * dist) / fabsf(dot(d, n));
+}
+// what a ray sees that has left the convex medium shape for good (or never meets it): the nearest area-emitter shape if one is hit -- front side: its
 // radiance, back side: black, and either way it hides the environment (all-absorbing BSDF, shape.cpp:48-56) -- else the environment.
-// extra = the optical length of the free-space leg to the rectangle (transient films).  AREA is a compile-time switch: the plain kernels
+// extra = the optical length of the free-space leg to that shape (transient films).  AREA is a compile-time switch: the plain kernels
 // carry none of this.
 // ENV: the envmap is looked up along d (the EXTRA kernels; env_along).
 template <bool AREA, bool ENV = AREA>
@@ -1244,7 +1324,7 @@ __device__ __forceinline__ f3 escape_radiance(const Params &P, f3 env, f3 o, f3 
     extra = 0.0f;
     if (AREA && P.n_rect) {
         int k; const float t = rect_nearest(P, o, d, mint, MER_INF, k);
-        if (t >= 0) { extra = t * P.sc.rif_const; return rect_le(P.rects[k], d); }
+        if (t >= 0) { extra = t * P.sc.rif_const; return rect_le(P.rects[k], o + d * t, d); }
     }
     return env_along<ENV>(P, env, d);
 }

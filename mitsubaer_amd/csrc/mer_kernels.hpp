@@ -162,6 +162,34 @@ __global__ void emitter_direct_kernel(const DPoint *points, const DSpot *spots, 
     float *o = out + 8 * i;
     o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dist; o[7] = fall;
 }
+// mer_area_direct: rect_sample_direct of area-table slot k; the value is multiplied back by the selection pdf (R.Le = L / R.pdf) and the
+// pdf divided by it, so neither carries the selection
+__global__ void area_direct_kernel(const DRect *rects, int k, const float *ref, const float *u2, int64_t n, float *out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DRect &R = rects[k];
+    f3 d, nn; float dist, pdf;
+    const f3 v = rect_sample_direct(R, f3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), u2[2 * i], u2[2 * i + 1], d, dist, pdf, nn) * R.pdf;
+    float *o = out + 12 * i;
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dist; o[7] = pdf / R.pdf;
+    o[8] = nn.x; o[9] = nn.y; o[10] = nn.z; o[11] = 0.0f;
+}
+// mer_area_hit: rect_nearest, rect_le and rect_pdf_direct as the camera rays and the phase-sampled look-up use them; list_index[slot] = the
+// entry's position in the scene's emitter list
+__global__ void area_hit_kernel(const Params P, const int32_t *list_index, const float *o, const float *d, const float *ref, int64_t n, float *out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 oo(o[3 * i], o[3 * i + 1], o[3 * i + 2]), dd(d[3 * i], d[3 * i + 1], d[3 * i + 2]), rr(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]);
+    int k; const float t = rect_nearest(P, oo, dd, 0.0f, MER_INF, k);
+    float *r = out + 8 * i;
+    for (int j = 0; j < 8; ++j) r[j] = 0.0f;
+    r[0] = -1.0f; r[1] = t;
+    if (t < 0) return;
+    const DRect &R = P.rects[k];
+    const f3 p = oo + dd * t, Le = rect_le(R, p, dd);
+    f3 dr = p - rr; const float dist = sqrtf(dot(dr, dr)); dr = dr / dist;
+    r[0] = (float) list_index[k]; r[2] = Le.x; r[3] = Le.y; r[4] = Le.z; r[5] = rect_pdf_direct(R, rr, dr, dist);
+}
 // EnvironmentMap::evalEnvironment / pdfDirect (envmap.cpp:385-415, 531-645) and sampleDirect (:516-610): the render kernels' device functions
 __global__ void envmap_eval_kernel(const DEnvMap *E, const float *dirs, int64_t n, float *val, float *pdf) {
     const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;

@@ -195,24 +195,60 @@ struct Emitters {
     double wp[MER_MAX_EMITTERS], wr[MER_MAX_EMITTERS];
 };
 
-// Rectangle::configure (src/shapes/rectangle.cpp:99-110): objectToWorld (row-major 3x4, also returned in M), its inverse, the frame normal
-// and 1 / area of the image of [-1,1]^2 x {0}.  Returns an error message or nullptr.
-static const char *rect_derive(const float to_world[12], DRect &R, double M[3][4]) {
+// objectToWorld (row-major 3x4, also returned in M), its inverse and the frame normal toWorld(Normal(0,0,1)) of a planar shape; returns the
+// determinant of the linear part (0: singular, nothing else is valid)
+static double frame_derive(const float to_world[12], DRect &R, double M[3][4]) {
     double A[3][3], inv[3][3];
     for (int i = 0; i < 12; i++) { R.o2w[i] = to_world[i]; M[i / 4][i % 4] = to_world[i]; }
     linear3(to_world, A);
     const double det = inverse3(A, inv);
-    if (!(std::fabs(det) > 0)) return "area emitter: 'toWorld' is singular";
+    if (!(std::fabs(det) > 0)) return 0;
     for (int i = 0; i < 3; i++) {
         for (int j = 0; j < 3; j++) R.w2o[4 * i + j] = (float) inv[i][j];
         R.w2o[4 * i + 3] = (float) -(inv[i][0] * M[0][3] + inv[i][1] * M[1][3] + inv[i][2] * M[2][3]);
     }
+    const double nn[3] = {inv[2][0], inv[2][1], inv[2][2]}, ln = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // o2w(Normal(0,0,1)): inverse transpose
+    for (int i = 0; i < 3; i++) R.n[i] = (float) (nn[i] / ln);
+    return det;
+}
+static double col_length(const double M[3][4], int c) { return std::sqrt(M[0][c] * M[0][c] + M[1][c] * M[1][c] + M[2][c] * M[2][c]); }
+static double col_dot(const double M[3][4], int a, int b) { return M[0][a] * M[0][b] + M[1][a] * M[1][b] + M[2][a] * M[2][b]; }
+// Rectangle::configure (src/shapes/rectangle.cpp:99-110): the frame and 1 / area of the image of [-1,1]^2 x {0}.  Returns an error message
+// or nullptr.
+static const char *rect_derive(const float to_world[12], DRect &R, double M[3][4]) {
+    if (frame_derive(to_world, R, M) == 0) return "area emitter: 'toWorld' is singular";
     const double du[3] = {2 * M[0][0], 2 * M[1][0], 2 * M[2][0]}, dv[3] = {2 * M[0][1], 2 * M[1][1], 2 * M[2][1]};
     const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
     if (std::fabs((du[0] * dv[0] + du[1] * dv[1] + du[2] * dv[2]) / (lu * lv)) > MER_EPSILON) return "Error: 'toWorld' transformation contains shear!";    // :108-109
-    const double nn[3] = {inv[2][0], inv[2][1], inv[2][2]}, ln = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // o2w(Normal(0,0,1)): inverse transpose
-    for (int i = 0; i < 3; i++) R.n[i] = (float) (nn[i] / ln);
     R.inv_area = (float) (1.0 / (lu * lv));
+    R.shape = AREA_RECT;
+    return nullptr;
+}
+// Disk::configure (src/shapes/disk.cpp:101-115): the frame and 1 / area = 1 / (pi |dpdu|^2) of the image of the unit disk in z = 0
+static const char *disk_derive(const float to_world[12], DRect &R, double M[3][4]) {
+    if (frame_derive(to_world, R, M) == 0) return "area emitter: 'toWorld' is singular";
+    const double lu = col_length(M, 0), lv = col_length(M, 1);
+    if (std::fabs(col_dot(M, 0, 1) / (lu * lv)) > 1e-3) return "Error: 'toWorld' transformation contains shear!";                     // :108-109
+    if (std::fabs(lu / lv - 1) > 1e-3) return "Error: 'toWorld' transformation contains a non-uniform scale!";                        // :111-112
+    R.inv_area = (float) (1.0 / (M_PI * lu * lu));
+    R.shape = AREA_DISK;
+    return nullptr;
+}
+// Sphere's constructor (src/shapes/sphere.cpp:108-132): centre = the translation column, radius = |toWorld e_x|; the rotation is not kept.  A
+// linear part of negative determinant means inward normals (flipNormals).  The reference reads the scale off e_x alone; here a linear part
+// that is no uniform scale of a rotation (column lengths or angles off by more than 1e-3) is refused.
+static const char *sphere_derive(const float to_world[12], DRect &R, double M[3][4]) {
+    const double det = frame_derive(to_world, R, M);
+    if (det == 0) return "area emitter: 'toWorld' is singular";
+    const double l[3] = {col_length(M, 0), col_length(M, 1), col_length(M, 2)};
+    for (int a = 0; a < 3; a++) {
+        const int b = (a + 1) % 3;
+        if (std::fabs(l[a] / l[b] - 1) > 1e-3 || std::fabs(col_dot(M, a, b) / (l[a] * l[b])) > 1e-3) return "sphere: 'toWorld' transformation contains a non-uniform scale!";
+    }
+    R.radius = (float) l[0];
+    R.flip = det < 0 ? -1.0f : 1.0f;
+    R.inv_area = (float) (1.0 / (4 * M_PI * l[0] * l[0]));
+    R.shape = AREA_SPHERE;
     return nullptr;
 }
 
@@ -259,6 +295,36 @@ static bool rect_outside(const mer_scene_desc &sc, const double M[3][4], bool ex
         if (sc.boundary == MER_BOUNDARY_SPHERE ? point_in_sphere(sc, q) : point_in_box(sc, q)) return false;
     }
     return true;
+}
+
+// the disk O + a U + b V, a^2 + b^2 <= 1, lies outside the medium shape.  Sphere boundary: the disk's point closest to the centre (the
+// centre's projection onto the plane, pulled back to the rim) lies outside -- exact.  Cube: the disk's circumscribed square passes the
+// rectangle / box test -- conservative: a disk whose square cuts the cube with a corner the disk does not reach is refused too.
+static bool disk_outside(const mer_scene_desc &sc, const double M[3][4]) {
+    if (sc.boundary != MER_BOUNDARY_SPHERE) return !rect_meets_shape(sc, M);
+    const double d[3] = {sc.sph_center[0] - M[0][3], sc.sph_center[1] - M[1][3], sc.sph_center[2] - M[2][3]};
+    double a = (d[0] * M[0][0] + d[1] * M[1][0] + d[2] * M[2][0]) / col_dot(M, 0, 0), b = (d[0] * M[0][1] + d[1] * M[1][1] + d[2] * M[2][1]) / col_dot(M, 1, 1);
+    const double r = std::sqrt(a * a + b * b);
+    if (r > 1) { a /= r; b /= r; }
+    double d2 = 0;
+    for (int i = 0; i < 3; i++) { const double e = M[i][0] * a + M[i][1] * b - d[i]; d2 += e * e; }
+    return !(d2 < (double) sc.sph_radius * sc.sph_radius);
+}
+// the sphere (centre = column 3 of M, radius R) is clear of the medium shape: apart from it (centre distance > R + r', or distance from the
+// centre to the box > R), or -- a flipped sphere only -- around it (centre distance + r' < R, or the farthest corner of the box closer than R)
+static bool sphere_clear(const mer_scene_desc &sc, const double M[3][4], double R, bool flipped) {
+    const double c[3] = {M[0][3], M[1][3], M[2][3]};
+    double nearest2 = 0, farthest2 = 0;
+    if (sc.boundary == MER_BOUNDARY_SPHERE) {
+        double d2 = 0; for (int i = 0; i < 3; i++) d2 += (c[i] - sc.sph_center[i]) * (c[i] - sc.sph_center[i]);
+        const double d = std::sqrt(d2);
+        return d > R + sc.sph_radius || (flipped && d + sc.sph_radius < R);
+    }
+    for (int i = 0; i < 3; i++) {
+        const double lo = sc.bmin[i], hi = sc.bmax[i], out = std::max(std::max(lo - c[i], c[i] - hi), 0.0), far = std::max(std::fabs(c[i] - lo), std::fabs(c[i] - hi));
+        nearest2 += out * out; farthest2 += far * far;
+    }
+    return nearest2 > R * R || (flipped && farthest2 < R * R);
 }
 
 // emitter `spot` (src/emitters/spot.cpp:68-95): the cone record of its point-table slot, in float as the reference derives it (degToRad in
@@ -332,15 +398,24 @@ static int add_point(mer_context *ctx, const mer_scene_desc &sc, Emitters &em, c
     em.any_spot = em.any_spot || cone;
     return 0;
 }
-// One rectangle record.  The legacy area_* fields (list = false) keep their five-probe outside test and no test of the radiance's sign.
-static int add_rect(mer_context *ctx, const mer_scene_desc &sc, Emitters &em, const float to_world[12], const float radiance[3], double weight, bool list,
+// One area-emitter record on a shape (AREA_RECT / AREA_DISK / AREA_SPHERE).  The legacy area_* fields (a rectangle, list = false) keep their
+// five-probe outside test and no test of the radiance's sign.
+static int add_rect(mer_context *ctx, const mer_scene_desc &sc, Emitters &em, int shape, const float to_world[12], const float radiance[3], double weight, bool list,
                     const std::string &at) {
     if (sc.rif_mode != MER_RIF_CONST) return fail(ctx, at + "the area emitter is built for straight rays (rif_mode = CONST)");
     if (sc.boundary_bsdf != MER_BSDF_NULL || sc.boundary == MER_BOUNDARY_SDF) return fail(ctx, at + "the area emitter needs an index-matched cube / sphere boundary");
     for (int i = 0; i < 3; i++) if (list && !(radiance[i] >= 0)) return fail(ctx, at + "emitter radiance / intensity must be non-negative");
+    for (int i = 0; i < 12; i++) if (shape != AREA_RECT && !std::isfinite(to_world[i])) return fail(ctx, at + "area emitter: 'toWorld' must be finite");
     DRect R{}; double M[3][4];
-    if (const char *err = rect_derive(to_world, R, M)) return fail(ctx, at + err);
-    if (!rect_outside(sc, M, list)) return fail(ctx, at + "the area emitter's rectangle must lie outside the medium shape");
+    R.flip = 1.0f;
+    if (const char *err = shape == AREA_SPHERE ? sphere_derive(to_world, R, M) : shape == AREA_DISK ? disk_derive(to_world, R, M) : rect_derive(to_world, R, M))
+        return fail(ctx, at + err);
+    if (shape == AREA_SPHERE) {
+        if (!sphere_clear(sc, M, R.radius, R.flip < 0))
+            return fail(ctx, at + "the area emitter's sphere must be clear of the medium shape (apart from it, or with inward normals around it)");
+    } else if (shape == AREA_DISK) {
+        if (!disk_outside(sc, M)) return fail(ctx, at + "the area emitter's disk must lie outside the medium shape");
+    } else if (!rect_outside(sc, M, list)) return fail(ctx, at + "the area emitter's rectangle must lie outside the medium shape");
     for (int i = 0; i < 3; i++) R.L[i] = R.Le[i] = radiance[i];
     em.tab.rects[em.n_rect] = R; em.wr[em.n_rect++] = weight;
     return 0;
@@ -373,8 +448,9 @@ static int emitter_list(mer_context *ctx, const mer_scene_desc &sc, Emitters &em
             if (const char *err = spot_derive(e, cone)) return fail(ctx, at + err);
             const float pos[3] = {e.to_world[3], e.to_world[7], e.to_world[11]};
             if (add_point(ctx, sc, em, pos, e.intensity, &cone, e.sampling_weight, true, at)) return 1;
-        } else if (e.type == MER_EMITTER_AREA) {
-            if (add_rect(ctx, sc, em, e.to_world, e.radiance, e.sampling_weight, true, at)) return 1;
+        } else if (e.type == MER_EMITTER_AREA || e.type == MER_EMITTER_AREA_DISK || e.type == MER_EMITTER_AREA_SPHERE) {   // one kind, one CDF, in list order
+            const int shape = e.type == MER_EMITTER_AREA_SPHERE ? AREA_SPHERE : e.type == MER_EMITTER_AREA_DISK ? AREA_DISK : AREA_RECT;
+            if (add_rect(ctx, sc, em, shape, e.to_world, e.radiance, e.sampling_weight, true, at)) return 1;
         } else if (e.type == MER_EMITTER_ENVMAP) {    // the environment: its own kind, one at most, sampled at every collision (selection probability 1)
             if (em.has_env || sc.env_radiance[0] != 0 || sc.env_radiance[1] != 0 || sc.env_radiance[2] != 0)
                 return fail(ctx, at + "The scene may only contain one environment emitter (an envmap entry excludes a second one and a non-zero env_radiance)");
@@ -592,7 +668,7 @@ static int emitters(mer_context *ctx, const mer_scene_desc &sc, Params &P, Emitt
     if (sc.point_intensity[0] != 0 || sc.point_intensity[1] != 0 || sc.point_intensity[2] != 0)
         if (add_point(ctx, sc, em, sc.point_position, sc.point_intensity, nullptr, 1.0, false, "")) return 1;
     if (sc.area_radiance[0] != 0 || sc.area_radiance[1] != 0 || sc.area_radiance[2] != 0)
-        if (add_rect(ctx, sc, em, sc.area_to_world, sc.area_radiance, 1.0, false, "")) return 1;
+        if (add_rect(ctx, sc, em, AREA_RECT, sc.area_to_world, sc.area_radiance, 1.0, false, "")) return 1;
     if (sc.n_emitters != 0 && emitter_list(ctx, sc, em)) return 1;
     if (!em.any_spot) std::memset(em.tab.spots, 0, sizeof(em.tab.spots));     // point-only scenes carry no cone table: the kernels skip the falloff
     selection_cdf(em.tab.points, em.wp, em.n_point, &DPoint::Ie);

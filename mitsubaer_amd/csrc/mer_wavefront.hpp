@@ -208,9 +208,10 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                 f3 L(0, 0, 0);
                 float plen = 0.0f;                                   // transient film: optical path length so far
                 const float itsT = intersect_shape_b<BND>(P, o, d, mint, maxt);
-                // the area emitter's rectangle in front of the medium shape (or hit instead of it): its.isEmitter() => Le, then the all-absorbing BSDF ends the path
-                int kRect = 0; const float tRect = (EXTRA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
-                if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P.rects[kRect], d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
+                // an area emitter's shape (rectangle, disk, sphere: straight rays only, so the curved kernels carry none of it) in front of the medium shape
+                // (or hit instead of it): its.isEmitter() => Le, then the all-absorbing BSDF ends the path
+                int kRect = 0; const float tRect = (EXTRA && !CURVED && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
+                if (tRect >= 0 && (itsT < 0 || tRect < itsT)) { if (!S.hide_emitters) { L = rect_le(P.rects[kRect], o + d * tRect, d); if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); } }
                 else if (itsT < 0) { if (!S.hide_emitters) L = env_along<EXTRA>(P, env, d); }
                 else if (1 >= maxDepth && maxDepth != -1) { }
                 else if (EXTRA && S.boundary_bsdf != MER_BSDF_NULL) hit = true;      // Fresnel / microfacet sampling at the surface: K_event
@@ -220,7 +221,7 @@ __global__ void __launch_bounds__(MER_BLOCK) gen_kernel(const Params P) {
                     if (!(2 <= maxDepth || maxDepth < 0)) { }
                     else if (!medium) {
                         float extra = 0.0f;
-                        if (!S.hide_emitters) L = escape_radiance<EXTRA>(P, env, o + d * itsT, d, 0.0f, extra);
+                        if (!S.hide_emitters) L = escape_radiance<EXTRA && !CURVED, EXTRA>(P, env, o + d * itsT, d, 0.0f, extra);
                         if (camera_edge_counts(P)) plen = edge_length(P, itsT);
                         if (S.decomposition != MER_DECOMPOSITION_BOUNCE) plen += extra;
                     }
@@ -569,6 +570,9 @@ static __device__ unsigned long long mer_prof[256 * 16];      // 256 replicas (b
 template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool EXTRA, int BND = 0, bool INLINE = false, bool ROUGH = false>
 __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : MER_EVENT_WAVES) event_kernel(const Params P, uint32_t pass) {
     static_assert(!ROUGH || EXTRA, "the rough boundary lives in the EXTRA kernels");
+    // area emitters (rectangle, disk, sphere) need straight rays and an index-matched boundary (make_params refuses them otherwise): the
+    // curved and the rough instances carry none of their code
+    constexpr bool AREA = EXTRA && !CURVED && !ROUGH;
     typedef Walk<CURVED, RIF, STEPPER, SIGMA, BND> WalkT;
     const uint32_t j = blockIdx.x * MER_BLOCK + threadIdx.x;
     if (j >= P.nslots_all) return;
@@ -687,9 +691,9 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             C.paths++;
             ev = EV_NONE;
             itsT = intersect_shape_b<BND>(P, o, d, mint, maxt);                       // rRec.rayIntersect(ray)
-            int kRect = 0; const float tRect = (EXTRA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
-            if (tRect >= 0 && (itsT < 0 || tRect < itsT)) {                              // an area emitter's rectangle is met first (K_gen retires these; gen_all hands them over)
-                if (!S.hide_emitters) { if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); const f3 Le = rect_le(P.rects[kRect], d); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }
+            int kRect = 0; const float tRect = (AREA && P.n_rect) ? rect_nearest(P, o, d, mint, maxt, kRect) : -1.0f;
+            if (tRect >= 0 && (itsT < 0 || tRect < itsT)) {                              // an area emitter's shape is met first (K_gen retires these; gen_all hands them over)
+                if (!S.hide_emitters) { if (camera_edge_counts(P)) plen = edge_length(P, tRect * S.rif_const); const f3 Le = rect_le(P.rects[kRect], o + d * tRect, d); L = L + mod_weight<EXTRA>(P, Le, plen); film_contribute(P, px, py, Le, plen); }
                 ev = EV_PATH_DONE;
             } else
             if (itsT < 0) {
@@ -727,7 +731,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 if (!(depth <= maxDepth || maxDepth < 0)) ev = EV_PATH_DONE;
                 else if (!medium) {
                     if (!S.hide_emitters) {
-                        float extra; const f3 Le = escape_radiance<EXTRA>(P, env, ro, d, 0.0f, extra);
+                        float extra; const f3 Le = escape_radiance<AREA, EXTRA>(P, env, ro, d, 0.0f, extra);
                         const float pl = plen + (S.decomposition != MER_DECOMPOSITION_BOUNCE ? extra : 0.0f);
                         L = L + mod_weight<EXTRA>(P, T * Le, pl); film_contribute(P, px, py, T * Le, pl);
                     }
@@ -856,8 +860,8 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     if (CURVED) value = envmap_value(E, dsave);
                     value = dpdf > 0 ? value / dpdf : f3(0, 0, 0);
                 }
-                // any rectangle shadows the environment (Scene::evalTransmittance stops at a non-null surface); tested after the walk so that the sampler draws stay the oracle's
-                if (EXTRA && P.n_rect && rect_blocks(P, ps, dd, 0.0f, MER_INF, -1)) tr = f3(0, 0, 0);
+                // any area emitter's shape shadows the environment (Scene::evalTransmittance stops at a non-null surface); tested after the walk so that the sampler draws stay the oracle's
+                if (AREA && P.n_rect && rect_blocks(P, ps, dd, 0.0f, MER_INF, -1)) tr = f3(0, 0, 0);
                 value = value * tr;
                 if (!is_zero(value)) {
                     const float phaseVal = phase_eval(S.phase, S.g, wi, dd);
@@ -881,11 +885,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                         value = tr * envmap_eval(E, dsave, emitterPdf);
                         if (CURVED) value = tr * envmap_value(E, dd);
                     }
-                    if (EXTRA && P.n_rect) {
-                        // rayIntersectAndLookForEmitter (volpath.cpp:370-428): beyond the null boundary the ray meets the nearest rectangle or the environment;
-                        // the MIS partner's pdf is that of sampling this rectangle: its selection probability x its solid-angle pdf
+                    if (AREA && P.n_rect) {
+                        // rayIntersectAndLookForEmitter (volpath.cpp:370-428): beyond the null boundary the ray meets the nearest emitter shape or the environment;
+                        // the MIS partner's pdf is that of sampling this shape from the vertex ps: its selection probability x its solid-angle pdf (a sphere's depends on ps)
                         int k; const float tR = rect_nearest(P, ps, dsave, 0.0f, MER_INF, k);
-                        if (tR >= 0) { const DRect &R = P.rects[k]; value = tr * rect_le(R, dsave); emitterPdf = R.pdf * rect_pdf_direct(R, dsave, tR); extra = (tR - (itsValid ? itsT : 0.0f)) * S.rif_const; }
+                        if (tR >= 0) { const DRect &R = P.rects[k]; value = tr * rect_le(R, ps + dsave * tR, dsave); emitterPdf = R.pdf * rect_pdf_direct(R, ps, dsave, tR); extra = (tR - (itsValid ? itsT : 0.0f)) * S.rif_const; }
                         else if (!hasEnv) value = f3(0, 0, 0);
                     }
                     if (!is_zero(value)) {
@@ -925,8 +929,9 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 L = L + mod_weight<EXTRA>(P, c, plen + edge_length(P, optLen));
                 film_contribute(P, px, py, c, plen + edge_length(P, optLen));
             }
-            // ---- luminaire sampling of ONE area emitter (scene.cpp:854-874, area.cpp:162-177, shape.cpp:102-115); its MIS partner is the look-up below
-            if (EXTRA && !CURVED && P.n_rect && ev == EV_PHASE) {
+            // ---- luminaire sampling of ONE area emitter -- rectangle, disk or sphere, one CDF -- (scene.cpp:854-874, area.cpp:158-173, shape.cpp:102-115,
+            // sphere.cpp:286-355); two sampler numbers whatever the shape; its MIS partner is the look-up below
+            if (AREA && P.n_rect && ev == EV_PHASE) {
                 C.nee++;
                 const int interactions = maxDepth - depth - 1;
                 float pk; const int k = emitter_select(P.rects, P.n_rect, rng, 4, pk);
@@ -939,7 +944,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     f3 trA(1, 1, 1);
                     if (crosses && interactions == 0) trA = f3(0, 0, 0);
                     else trA = straight_transmittance<SIGMA>(P, rng, C, ps, dvec, crosses ? tExit : dist);
-                    // the other rectangles are all-absorbing occluders (tested after the walk: the sampler draws do not depend on them)
+                    // the other shapes are all-absorbing occluders (tested after the walk: the sampler draws do not depend on them)
                     if (P.n_rect > 1 && rect_blocks(P, ps, dvec, 0.0f, dist, k)) trA = f3(0, 0, 0);
                     value = value * trA;
                     if (!is_zero(value)) {
@@ -959,7 +964,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             dsave = wo;
             if (CURVED) { itsT = 0; SET_FLAG(F_ITSVALID, true); }
             else { itsT = intersect_shape_b<BND>(P, ps, wo, 0.0f, MER_INF); SET_FLAG(F_ITSVALID, itsT >= 0); }
-            if (hasEnv || (EXTRA && P.n_rect)) {
+            if (hasEnv || (AREA && P.n_rect)) {
                 W.kind = K_LOOKUP;
                 if (CURVED && envLight) dd = wo;                                        // the walk's exit direction until it reports one (EV_EXITED)
                 trOpt = (!CURVED && itsValid) ? itsT * S.rif_const : 0.0f;
@@ -1036,7 +1041,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             } else
             if (!itsValid) {
                 if (emitted && (!S.hide_emitters || scattered)) {
-                    float extra; const f3 Le = escape_radiance<EXTRA && !CURVED, EXTRA>(P, env, ps, dsave, 0.0f, extra);
+                    float extra; const f3 Le = escape_radiance<AREA, EXTRA>(P, env, ps, dsave, 0.0f, extra);
                     const float pl = plen + (S.decomposition != MER_DECOMPOSITION_BOUNCE ? extra : 0.0f);
                     L = L + mod_weight<EXTRA>(P, T * Le, pl); film_contribute(P, px, py, T * Le, pl);
                 }
@@ -1048,7 +1053,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     if (emitted && (!S.hide_emitters || scattered)) {
                         // outside the (convex) shape now: the environment, or the area emitter's rectangle (straight rays: from the exit point ps + itsT dsave)
                         // (curved rays: the map at the direction in which the path left the shape)
-                        float extra; const f3 Le = escape_radiance<EXTRA && !CURVED, EXTRA>(P, env, ps + dsave * itsT, (CURVED && envLight) ? normalize(m.d) : dsave, 0.0f, extra);
+                        float extra; const f3 Le = escape_radiance<AREA, EXTRA>(P, env, ps + dsave * itsT, (CURVED && envLight) ? normalize(m.d) : dsave, 0.0f, extra);
                         const float pl = plen + (S.decomposition != MER_DECOMPOSITION_BOUNCE ? extra : 0.0f);
                         L = L + mod_weight<EXTRA>(P, T * Le, pl); film_contribute(P, px, py, T * Le, pl);
                     }

@@ -174,6 +174,7 @@ void Shape::addChild(const std::string &name, ObjRef child) {
     if (cls == "Medium") {
         if (name == "interior") {
             interior = std::static_pointer_cast<Medium>(child);
+            if (areaEmitter) Log_EError("sphere: a shape that carries an area emitter cannot also bound an 'interior' medium on the GPU path");
             if (interior->isheterogeneousrefractive() && hasBSDF && bsdf != MER_BSDF_HDIELECTRIC && bsdf != MER_BSDF_HROUGHDIELECTRIC)   // shape.cpp:172-176
                 Log_EError("A shape with heterogeneous refractive index medium should only have a bsdf that is also heterogeneous!");
         } else if (name == "exterior") Log_EError("Shape: an 'exterior' medium is not supported on the GPU path (the sensor must be in vacuum)");
@@ -183,7 +184,8 @@ void Shape::addChild(const std::string &name, ObjRef child) {
         auto e = std::static_pointer_cast<Emitter>(child);
         if (areaEmitter) Log_EError("Tried to attach multiple emitters to a shape!");
         if (e->kind != Emitter::EArea) Log_EError("Tried to attach a non-surface emitter to a shape");
-        if (!isRectangle) Log_EError("area emitter: only a 'rectangle' shape can carry one on the GPU path");
+        if (!areaType) Log_EError("area emitter: only a 'rectangle', 'disk' or 'sphere' shape can carry one on the GPU path");
+        if (interior) Log_EError("sphere: a shape that carries an area emitter cannot also bound an 'interior' medium on the GPU path");
         areaEmitter = e;
     }
     else ConfigurableObject::addChild(name, child);
@@ -343,7 +345,7 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
         auto o = std::make_shared<Shape>();
         float m[16]; props.getTransform("toWorld", m);
         if (type == "rectangle") {                                       // src/shapes/rectangle.cpp:99-110: the carrier of an `area` emitter; any shear-free toWorld
-            o->isRectangle = true;
+            o->isRectangle = true; o->areaType = MER_EMITTER_AREA;
             for (int i = 0; i < 12; i++) o->rectToWorld[i] = m[i];
             const double du[3] = {m[0], m[4], m[8]}, dv[3] = {m[1], m[5], m[9]};
             const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
@@ -351,14 +353,41 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             out = o;
             return out;
         }
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++)
-            if (r != c && std::fabs(m[r * 4 + c]) > 1e-6f) Log_EError("shape: only scale + translate 'toWorld' transforms are supported on the GPU path");
+        if (type == "disk") {                                            // src/shapes/disk.cpp:83-115: the carrier of an `area` emitter; flipNormals prepends scale(1, 1, -1)
+            o->areaType = MER_EMITTER_AREA_DISK;
+            for (int i = 0; i < 12; i++) o->rectToWorld[i] = m[i];
+            if (props.getBoolean("flipNormals", false)) for (int r = 0; r < 3; r++) o->rectToWorld[4 * r + 2] = -m[4 * r + 2];
+            const double du[3] = {m[0], m[4], m[8]}, dv[3] = {m[1], m[5], m[9]};
+            const double lu = std::sqrt(du[0] * du[0] + du[1] * du[1] + du[2] * du[2]), lv = std::sqrt(dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2]);
+            if (!(lu > 0 && lv > 0) || std::fabs((du[0] * dv[0] + du[1] * dv[1] + du[2] * dv[2]) / (lu * lv)) > 1e-3) Log_EError("Error: 'toWorld' transformation contains shear!");   // :108-109
+            if (std::fabs(lu / lv - 1) > 1e-3) Log_EError("Error: 'toWorld' transformation contains a non-uniform scale!");                                                      // :111-112
+            out = o;
+            return out;
+        }
+        if (type == "sphere") {
+            // as the carrier of an `area` emitter (src/shapes/sphere.cpp:108-132): any toWorld T; objectToWorld = T * scale(1 / s) * translate(center)
+            // with s = |T e_x|, so the centre is T_linear (center / s) + T_translation and the radius `radius` * s
+            const Vec3 c = props.getPoint("center", Vec3{0, 0, 0}); const float r = props.getFloat("radius", 1.0f);
+            const float s = std::sqrt(m[0] * m[0] + m[4] * m[4] + m[8] * m[8]), R = r * s;
+            if (!(R > 0)) Log_EError("Cannot create spheres of radius <= 0");                                                    // :130-131
+            const float q[3] = {c.x / s, c.y / s, c.z / s};
+            for (int i = 0; i < 12; i++) o->rectToWorld[i] = 0;
+            for (int k = 0; k < 3; k++) { o->rectToWorld[4 * k + k] = R; o->rectToWorld[4 * k + 3] = m[4 * k] * q[0] + m[4 * k + 1] * q[1] + m[4 * k + 2] * q[2] + m[4 * k + 3]; }
+            if (props.getBoolean("flipNormals", false)) o->rectToWorld[10] = -R;
+            o->areaType = MER_EMITTER_AREA_SPHERE;
+        }
+        // the medium boundary takes scale + translate only; a sphere that carries an emitter takes any toWorld (build() raises boundaryError without one)
+        for (int r = 0; r < 3 && o->boundaryError.empty(); r++) for (int c = 0; c < 3; c++)
+            if (r != c && std::fabs(m[r * 4 + c]) > 1e-6f) {
+                if (type != "sphere") Log_EError("shape: only scale + translate 'toWorld' transforms are supported on the GPU path");
+                o->boundaryError = "shape: only scale + translate 'toWorld' transforms are supported on the GPU path";
+            }
         if (type == "cube") {
             for (int i = 0; i < 3; i++) { float s = std::fabs(m[i * 4 + i]); o->bmin[i] = m[i * 4 + 3] - s; o->bmax[i] = m[i * 4 + 3] + s; }
         } else if (type == "sphere") {
             o->boundary = MER_BOUNDARY_SPHERE;
             Vec3 c = props.getPoint("center", Vec3{0, 0, 0}); const float r = props.getFloat("radius", 1.0f);
-            if (std::fabs(m[0] - m[5]) > 1e-6f || std::fabs(m[0] - m[10]) > 1e-6f) Log_EError("sphere: non-uniform scales are not supported");
+            if (o->boundaryError.empty() && (std::fabs(m[0] - m[5]) > 1e-6f || std::fabs(m[0] - m[10]) > 1e-6f)) o->boundaryError = "sphere: non-uniform scales are not supported";
             o->center[0] = c.x * m[0] + m[3]; o->center[1] = c.y * m[5] + m[7]; o->center[2] = c.z * m[10] + m[11]; o->radius = r * std::fabs(m[0]);
         } else if (type == "obj") {
             // bounding box of the vertices (scenes/volumetric/bounds.obj is the cube [-1,1]^3)
@@ -372,7 +401,7 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             }
             if (!any) Log_EError("obj: no vertices found");
             for (int i = 0; i < 3; i++) { float a = lo[i] * m[i * 4 + i] + m[i * 4 + 3], b = hi[i] * m[i * 4 + i] + m[i * 4 + 3]; o->bmin[i] = std::min(a, b); o->bmax[i] = std::max(a, b); }
-        } else Log_EError("shape \"" + type + "\" is not supported on the GPU path (cube, sphere, obj bounding box; rectangle with an area emitter)");
+        } else Log_EError("shape \"" + type + "\" is not supported on the GPU path (cube, sphere, obj bounding box; rectangle, disk or sphere with an area emitter)");
         out = o;
     } else if (tag == "sensor") {
         auto o = std::make_shared<Sensor>();
@@ -716,6 +745,11 @@ struct Loader {
         if (n.tag == "shape") for (auto &ch : children) if (std::string(ch.second->getClassName()) == "BSDF") {
             std::static_pointer_cast<Shape>(obj)->hasBSDF = true; std::static_pointer_cast<Shape>(obj)->bsdf = std::static_pointer_cast<BSDF>(ch.second)->kind;
             std::static_pointer_cast<Shape>(obj)->bsdfObj = std::static_pointer_cast<BSDF>(ch.second); }
+        if (n.tag == "shape" && !std::static_pointer_cast<Shape>(obj)->boundaryError.empty()) {          // a sphere that is no emitter carrier is a medium boundary
+            bool carrier = false;
+            for (auto &ch : children) carrier = carrier || std::string(ch.second->getClassName()) == "Emitter";
+            if (!carrier) Log_EError(std::static_pointer_cast<Shape>(obj)->boundaryError);
+        }
         for (auto &ch : children) obj->addChild(ch.first, ch.second);
         obj->configure();
         if (n.attr.count("id")) byId[subst(n.attr.at("id"))] = obj;
@@ -837,18 +871,22 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     }
     d.phase = m.phase->kind; d.g = m.phase->g;
     d.tr_estimator = m.trEstimator; d.method = m.method; d.het_stepsize = m.hetStepSize;
-    // point emitters and the area emitters of `rectangle` shapes, in scene order (rectangles first).  At most one of each kind: the single-emitter
-    // fields of the scene desc; more: the emitter list (scene.emitterList), each entry with its samplingWeight
-    int nconst = 0, npoint = 0, narea = 0, nspot = 0, nenv = 0;
+    // point emitters and the area emitters of `rectangle` / `disk` / `sphere` shapes, in scene order (shapes first).  At most one point and one
+    // rectangle, nothing else: the single-emitter fields of the scene desc; otherwise the emitter list (scene.emitterList), each entry with its
+    // samplingWeight.  A disk or sphere is always a list entry (the single-emitter fields describe a rectangle)
+    int nconst = 0, npoint = 0, narea = 0, nspot = 0, nenv = 0, nround = 0;
     std::vector<mer_emitter> &list = scene.emitterList;
     list.clear();
     for (int i = 0; i < 3; i++) { d.env_radiance[i] = 0; d.point_intensity[i] = 0; d.point_position[i] = 0; d.emission[i] = m.emission.c[i]; d.area_radiance[i] = 0; }
     for (int i = 0; i < 12; i++) d.area_to_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
     d.n_emitters = 0; d.emitters = nullptr;
     for (auto &sh : scene.shapes) {
-        if (!sh->isRectangle) continue;
-        if (!sh->areaEmitter) Log_EError("shape \"rectangle\" is supported on the GPU path as the carrier of an area emitter only");
-        mer_emitter e{}; e.type = MER_EMITTER_AREA; e.sampling_weight = sh->areaEmitter->samplingWeight;
+        if (sh.get() == shape) continue;
+        if (!sh->areaEmitter && sh->isRectangle) Log_EError("shape \"rectangle\" is supported on the GPU path as the carrier of an area emitter only");
+        if (!sh->areaEmitter && sh->areaType == MER_EMITTER_AREA_DISK) Log_EError("shape \"disk\" is supported on the GPU path as the carrier of an area emitter only");
+        if (!sh->areaEmitter) continue;
+        mer_emitter e{}; e.type = sh->areaType; e.sampling_weight = sh->areaEmitter->samplingWeight;
+        if (e.type != MER_EMITTER_AREA) ++nround;
         for (int i = 0; i < 12; i++) e.to_world[i] = sh->rectToWorld[i];
         for (int i = 0; i < 3; i++) e.radiance[i] = sh->areaEmitter->radiance.c[i];
         list.push_back(e); ++narea;
@@ -879,7 +917,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
         }
     }
     if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point, spot and area emitters are supported on the GPU path");
-    if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0) {
+    if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0 && nround == 0) {
         for (const mer_emitter &e : list) {
             if (e.type == MER_EMITTER_AREA) { for (int i = 0; i < 12; i++) d.area_to_world[i] = e.to_world[i]; for (int i = 0; i < 3; i++) d.area_radiance[i] = e.radiance[i]; }
             else for (int i = 0; i < 3; i++) { d.point_position[i] = e.position[i]; d.point_intensity[i] = e.intensity[i]; }

@@ -134,6 +134,11 @@ public:
     float bmin[3] = {-1, -1, -1}, bmax[3] = {1, 1, 1}, center[3] = {0, 0, 0}, radius = 1;
     std::shared_ptr<Medium> interior;
     bool isRectangle = false; float rectToWorld[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};   ///< `rectangle` (src/shapes/rectangle.cpp): carrier of an area emitter
+    /// the emitter-list entry type this shape yields with an `area` emitter child: MER_EMITTER_AREA (`rectangle`), MER_EMITTER_AREA_DISK
+    /// (`disk`, src/shapes/disk.cpp) or MER_EMITTER_AREA_SPHERE (`sphere`, src/shapes/sphere.cpp); 0 = the shape cannot carry one.
+    /// rectToWorld then is the entry's to_world (a sphere's: translate(centre) * scale(radius), z negated for flipNormals)
+    int areaType = 0;
+    std::string boundaryError;         ///< a `sphere` whose toWorld the medium boundary cannot take (it may still carry an emitter): raised without an emitter child
     std::shared_ptr<class Emitter> areaEmitter;
     bool hasBSDF = false;              ///< a bsdf child was given (null | hdielectric | hroughdielectric)
     int bsdf = MER_BSDF_NULL;          ///< MER_BSDF_*

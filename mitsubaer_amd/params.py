@@ -115,7 +115,8 @@ class SceneParams:
         # emitter `area` on a `rectangle` shape (src/emitters/area.cpp, src/shapes/rectangle.cpp): the image of [-1,1]^2 x {0} under area_to_world
         # (3x4 or 4x4, no shear; None = identity), radiance into the half space of its normal toWorld(0,0,1); zero radiance = none
         self.area_to_world = None; self.area_radiance = [0.0, 0.0, 0.0]
-        # several point / area emitters (include/mer.h: mer_emitter): a list of point_emitter(...) / area_emitter(...) entries.  Non-empty:
+        # several point / area emitters (include/mer.h: mer_emitter): a list of point_emitter(...) / area_emitter(...) / disk_emitter(...) /
+        # sphere_emitter(...) / spot_emitter(...) / envmap_emitter(...) entries.  Non-empty:
         # point_intensity and area_radiance must stay zero; one emitter of each kind is sampled per collision, chosen by samplingWeight
         self.emitters = []
         # film decomposition (src/librender/film.cpp:56-84): 0 none | 1 transient | 2 bounce (bins by edge count); frames = ceil((max-min)/binWidth)
@@ -142,6 +143,9 @@ EMITTER_POINT = 1
 EMITTER_AREA = 2
 EMITTER_SPOT = 3
 EMITTER_ENVMAP = 4
+EMITTER_AREA_DISK = 5
+EMITTER_AREA_SPHERE = 6
+AREA_TYPES = (EMITTER_AREA, EMITTER_AREA_DISK, EMITTER_AREA_SPHERE)      # one kind: one selection CDF in list order
 MAX_EMITTERS = 32
 
 
@@ -154,6 +158,46 @@ def point_emitter(position, intensity, sampling_weight=1.0):
 def area_emitter(to_world, radiance, sampling_weight=1.0):
     """an entry of SceneParams.emitters: emitter `area` on a `rectangle`, the image of [-1,1]^2 x {0} under to_world (3x4 or 4x4, no shear)"""
     return {"type": EMITTER_AREA, "to_world": to_world, "radiance": [float(v) for v in radiance], "sampling_weight": float(sampling_weight)}
+
+
+def disk_emitter(to_world, radiance, sampling_weight=1.0):
+    """an entry of SceneParams.emitters: emitter `area` on a `disk` (src/shapes/disk.cpp), the image of the unit disk in z = 0 under to_world
+    (3x4 or 4x4, no shear, uniform u / v scale; a negative determinant is the reference's flipNormals); normal = to_world(Normal(0,0,1))"""
+    return {"type": EMITTER_AREA_DISK, "to_world": to_world, "radiance": [float(v) for v in radiance], "sampling_weight": float(sampling_weight)}
+
+
+def sphere_emitter(center, radius, radiance, sampling_weight=1.0, flip_normals=False):
+    """an entry of SceneParams.emitters: emitter `area` on a `sphere` (src/shapes/sphere.cpp).  The entry carries the transform the C ABI reads:
+    translate(center) * scale(radius), with the z scale negated for flip_normals (a negative determinant: the sphere emits inward)"""
+    import numpy as np
+    m = np.eye(4); r = float(radius)
+    m[0, 0] = m[1, 1] = r; m[2, 2] = -r if flip_normals else r
+    m[:3, 3] = [float(v) for v in center]
+    return {"type": EMITTER_AREA_SPHERE, "to_world": m, "radiance": [float(v) for v in radiance], "sampling_weight": float(sampling_weight)}
+
+
+def area_shape_error(kind, to_world):
+    """why mer_render refuses the transform of a disk / sphere area emitter (None: accepted); the messages are the library's"""
+    import numpy as np
+    m = np.asarray(to_world if to_world is not None else np.eye(4), np.float64)
+    if m.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(m)):
+        return "area emitter: 'toWorld' must be finite"
+    A = m[:3, :3].astype(np.float32).astype(np.float64)
+    if not abs(np.linalg.det(A)) > 0:
+        return "area emitter: 'toWorld' is singular"
+    l = np.sqrt((A * A).sum(axis=0))
+    cos = lambda a, b: abs(float(np.dot(A[:, a], A[:, b])) / (l[a] * l[b]))
+    if kind == EMITTER_AREA_DISK:
+        if cos(0, 1) > 1e-3:
+            return "Error: 'toWorld' transformation contains shear!"
+        if abs(l[0] / l[1] - 1) > 1e-3:
+            return "Error: 'toWorld' transformation contains a non-uniform scale!"
+    elif kind == EMITTER_AREA_SPHERE:
+        for a in range(3):
+            b = (a + 1) % 3
+            if abs(l[a] / l[b] - 1) > 1e-3 or cos(a, b) > 1e-3:
+                return "sphere: 'toWorld' transformation contains a non-uniform scale!"
+    return None
 
 
 def spot_error(to_world, cutoff_deg, beam_deg):

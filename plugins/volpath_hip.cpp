@@ -256,10 +256,10 @@ public:
         /* ---- medium, phase function, volumes */
         fillMedium(ctx, shape->getInteriorMedium(), d, volumes);
 
-        /* ---- emitters: constant environment or environment map, point and spot emitters and area emitters on rectangles.  One point and one
-           area emitter at most, no spot and no map: the single-emitter fields of mer_scene_desc; otherwise the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
+        /* ---- emitters: constant environment or environment map, point and spot emitters and area emitters on rectangles, disks and spheres.  One point and one
+           area emitter (on a rectangle) at most, no spot and no map: the single-emitter fields of mer_scene_desc; otherwise the emitter list, each entry with its samplingWeight (src/librender/emitter.cpp:103) */
         std::vector<mer_emitter> list;
-        int npoint = 0, narea = 0, nspot = 0, nenv = 0;
+        int npoint = 0, narea = 0, nspot = 0, nenv = 0, nround = 0;
         if (const Emitter *env = scene->getEnvironmentEmitter()) {
             if (env->getClass()->getName() == "EnvironmentMap") {
                 /* `envmap` (src/emitters/envmap.cpp): its level-0 image through getBitmap() (:647-649, the MIP map's top level), `scale` from its
@@ -287,24 +287,53 @@ public:
             const Emitter *e = emitters[i].get();
             if (e->isEnvironmentEmitter()) continue;
             if (e->getClass()->getName() == "AreaLight") {
-                /* `area` emitter on a `rectangle` shape (src/emitters/area.cpp, src/shapes/rectangle.cpp): the rectangle keeps its objectToWorld private,
-                   so the transform is recovered from three corner samples (Rectangle::samplePosition, :210-216: p = toWorld(2u - 1, 2v - 1, 0)) */
+                /* `area` emitter on a `rectangle`, `disk` or `sphere` shape (src/emitters/area.cpp, src/shapes/rectangle.cpp, disk.cpp, sphere.cpp): the
+                   shapes keep their objectToWorld private, so the transform is recovered from position samples.  Rectangle::samplePosition
+                   (:210-216): p = toWorld(2u - 1, 2v - 1, 0) -- three corners.  Disk::samplePosition (disk.cpp:247-255): the concentric map sends
+                   (0.5, 0.5) to the centre, (1, 0.5) to toWorld(1, 0, 0) and (0.5, 1) to toWorld(0, 1, 0).  Sphere::samplePosition (sphere.cpp:257-268):
+                   (0, 0) and (0, 1) are the two poles centre +- radius e_z; the normal at the first pole points inward when flipNormals is set,
+                   which the C ABI reads off a negative determinant */
                 const Shape *rs = e->getShape();
-                if (!rs || rs->getClass()->getName() != "Rectangle") Log(EError, "volpath_hip: an area emitter must sit on a 'rectangle' shape");
-                PositionSamplingRecord p00(0.0f), p10(0.0f), p01(0.0f);
-                rs->samplePosition(p00, Point2(0, 0)); rs->samplePosition(p10, Point2(1, 0)); rs->samplePosition(p01, Point2(0, 1));
-                const Vector du = (p10.p - p00.p) * 0.5f, dv = (p01.p - p00.p) * 0.5f;
-                const Point c = p00.p + du + dv;
-                const Normal n = p00.n;                                                          /* the frame normal, toWorld(Normal(0,0,1)) normalized */
-                const float cols[3][4] = { { du.x, dv.x, n.x, c.x }, { du.y, dv.y, n.y, c.y }, { du.z, dv.z, n.z, c.z } };
+                const std::string shapeName = rs ? rs->getClass()->getName() : std::string();
+                if (shapeName != "Rectangle" && shapeName != "Disk" && shapeName != "Sphere")
+                    Log(EError, "volpath_hip: an area emitter must sit on a 'rectangle', 'disk' or 'sphere' shape");
+                int areaType = MER_EMITTER_AREA;
+                float cols[3][4];
+                if (shapeName == "Sphere") {
+                    PositionSamplingRecord north(0.0f), south(0.0f);
+                    rs->samplePosition(north, Point2(0, 0)); rs->samplePosition(south, Point2(0, 1));
+                    const Point c = north.p + (south.p - north.p) * 0.5f;
+                    const float radius = (float) (north.p - south.p).length() * 0.5f;
+                    const bool flipped = dot(Vector(north.n), north.p - c) < 0;
+                    const float diag[3] = { radius, radius, flipped ? -radius : radius }, ctr[3] = { (float) c.x, (float) c.y, (float) c.z };
+                    for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) cols[r][k] = r == k ? diag[r] : 0.0f; cols[r][3] = ctr[r]; }
+                    areaType = MER_EMITTER_AREA_SPHERE;
+                } else {
+                    const bool disk = shapeName == "Disk";
+                    PositionSamplingRecord p00(0.0f), p10(0.0f), p01(0.0f);
+                    Vector du, dv; Point c;
+                    if (disk) {
+                        rs->samplePosition(p00, Point2(0.5f, 0.5f)); rs->samplePosition(p10, Point2(1, 0.5f)); rs->samplePosition(p01, Point2(0.5f, 1));
+                        du = p10.p - p00.p; dv = p01.p - p00.p; c = p00.p;
+                        areaType = MER_EMITTER_AREA_DISK;
+                    } else {
+                        rs->samplePosition(p00, Point2(0, 0)); rs->samplePosition(p10, Point2(1, 0)); rs->samplePosition(p01, Point2(0, 1));
+                        du = (p10.p - p00.p) * 0.5f; dv = (p01.p - p00.p) * 0.5f; c = p00.p + du + dv;
+                    }
+                    const Normal n = p00.n;                                                      /* the frame normal, toWorld(Normal(0,0,1)) normalized */
+                    const float m3[3][4] = { { (float) du.x, (float) dv.x, (float) n.x, (float) c.x }, { (float) du.y, (float) dv.y, (float) n.y, (float) c.y },
+                                             { (float) du.z, (float) dv.z, (float) n.z, (float) c.z } };
+                    memcpy(cols, m3, sizeof(cols));
+                }
                 PositionSamplingRecord pr(0.0f); rs->samplePosition(pr, Point2(0.5f));
                 const Spectrum Le = e->evalPosition(pr) * INV_PI;                                 /* AreaLight::evalPosition = radiance * pi (area.cpp:98-100) */
                 Float r, g, b; Le.toLinearRGB(r, g, b);
                 mer_emitter m; memset(&m, 0, sizeof(m));
-                m.type = MER_EMITTER_AREA; m.sampling_weight = (float) e->getSamplingWeight();
+                m.type = areaType; m.sampling_weight = (float) e->getSamplingWeight();
                 for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) m.to_world[4 * r + k] = cols[r][k];
                 m.radiance[0] = r; m.radiance[1] = g; m.radiance[2] = b;
                 list.push_back(m); ++narea;
+                if (areaType != MER_EMITTER_AREA) ++nround;                                      /* a disk or sphere is always a list entry */
                 continue;
             }
             if (e->getClass()->getName() == "SpotEmitter") {
@@ -325,7 +354,7 @@ public:
                 list.push_back(m); ++nspot;
                 continue;
             }
-            if (e->getClass()->getName() != "PointEmitter") Log(EError, "volpath_hip: emitters must be 'constant', 'point', 'spot' or 'area' (on a rectangle)");
+            if (e->getClass()->getName() != "PointEmitter") Log(EError, "volpath_hip: emitters must be 'constant', 'point', 'spot' or 'area' (on a rectangle, disk or sphere)");
             PositionSamplingRecord pRec(0.0f);
             const Spectrum I = e->samplePosition(pRec, Point2(0.5f)) / (4 * M_PI);       /* src/emitters/point.cpp:82-90 */
             Float r, g, b; I.toLinearRGB(r, g, b);
@@ -335,7 +364,7 @@ public:
             m.position[0] = pRec.p.x; m.position[1] = pRec.p.y; m.position[2] = pRec.p.z;
             list.push_back(m); ++npoint;
         }
-        if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0) {
+        if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0 && nround == 0) {
             for (size_t i = 0; i < list.size(); ++i) {
                 const mer_emitter &m = list[i];
                 if (m.type == MER_EMITTER_AREA) {
@@ -395,7 +424,7 @@ private:
         const ref_vector<Shape> &shapes = scene->getShapes();
         for (size_t i = 0; i < shapes.size(); ++i) {
             if (!shapes[i]->getInteriorMedium()) {
-                if (!shapes[i]->isEmitter()) SLog(EError, "volpath_hip: a shape without an interior medium must be a rectangle carrying an area emitter");
+                if (!shapes[i]->isEmitter()) SLog(EError, "volpath_hip: a shape without an interior medium must be a rectangle, disk or sphere carrying an area emitter");
                 continue;
             }
             if (found && shapes[i]->getInteriorMedium() != found->getInteriorMedium())
