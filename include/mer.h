@@ -291,6 +291,32 @@ int  mer_volume_upload(mer_context *ctx, const mer_grid_desc *desc, const void *
 /* same, from a device-resident dense grid (generated on the GPU) */
 int  mer_volume_upload_dev(mer_context *ctx, const mer_grid_desc *desc, const void *data_dev,
                            int32_t layout, mer_volume *out);
+/* Signed-distance grid of a triangle mesh, built on the GPU: the `sdf` child of heterogeneousrefractive for a shape given as faces.  The
+   reference reads such a grid but has no tool that makes one (its exact inside test, winding numbers over the mesh, is commented out:
+   src/medium/heterogeneousrefractive.cpp:732-739).
+   desc: the grid -- channels = 1, dtype = MER_VOL_F32, world_to_volume all zero; node (i, j, k) lies at
+   aabb_min[a] + (float) i * ((aabb_max[a] - aabb_min[a]) / (float) (res[a] - 1)) per axis, x fastest (the VOL payload order).
+   vertices: host, n_vertices x xyz; triangles: host, n_triangles x 3 vertex indices.
+   Per node, in float32: distance = min over the triangles of the point-triangle distance (closest point by Voronoi regions, Ericson,
+   Real-Time Collision Detection 5.1.5); winding number w = (1 / 4 pi) sum_t 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|)
+   with a, b, c = the triangle's vertices minus the node (Van Oosterom-Strackee).  The node is inside iff |w| >= 0.5 -- a mesh whose
+   orientation is inverted as a whole gives the same grid, an open mesh degrades gracefully -- and the grid holds -distance inside,
+   +distance outside (the convention of mer_scene_desc.sdf).
+   Every node is tested against every triangle; the triangles are processed max_triangles_per_launch at a time (0 = default, 4096), one
+   kernel launch per chunk and per 2^24 nodes, so that no launch runs long.  Every node adds its triangles in index order: the result is
+   bit-identical for every chunk size.
+   Refused with a message (mer_last_error) before anything reaches the device: res[a] < 2; more than 2^31 nodes; a box that is empty or
+   not finite; n_triangles outside [1, 2^22]; an index outside [0, n_vertices); a vertex that is not finite; max_triangles_per_launch < 0;
+   a non-zero world_to_volume.  Triangles with a repeated index or an exactly zero cross product (b - a) x (c - a) are dropped; a mesh
+   with none left is refused.
+   layout: as for mer_volume_upload_dev, whose path the result takes (a BRICK layout stays refused for an sdf at render time).
+   winding_host: NULL, or one float per node that receives w.  *out: an ordinary volume handle (mer_volume_destroy). */
+int  mer_sdf_from_mesh(mer_context *ctx, const mer_grid_desc *desc, const float *vertices, int64_t n_vertices,
+                       const int32_t *triangles, int64_t n_triangles, int32_t max_triangles_per_launch,
+                       int32_t layout, float *winding_host, mer_volume *out);
+/* the dense x-fastest float32 payload of a 1-channel float32 volume (res[0] * res[1] * res[2] floats), whatever its device layout;
+   refused for 3-channel and uint8 volumes and for envmap handles */
+int  mer_volume_download(mer_context *ctx, mer_volume v, float *data_host);
 /* builds cubic-B-spline coefficients on the GPU (Spline<3>::build3d, include/mitsuba/core/basisspline.h:812-890) */
 int  mer_volume_build_spline(mer_context *ctx, mer_volume v);
 int  mer_volume_download_spline(mer_context *ctx, mer_volume v, float *coeff_host);

@@ -17,7 +17,7 @@ LAYOUT_DENSE, LAYOUT_CELL8, LAYOUT_BRICK27, LAYOUT_BRICK125, LAYOUT_AUTO = 0, 1,
 # every symbol include/mer.h declares (checked by tests/test_abi.py against the header text)
 SYMBOLS = [
     "mer_abi_version", "mer_context_create", "mer_context_destroy", "mer_last_error", "mer_context_set_stream",
-    "mer_device_info", "mer_context_set_option", "mer_context_get_option", "mer_debug_bounds", "mer_volume_upload", "mer_volume_upload_dev", "mer_volume_build_spline",
+    "mer_device_info", "mer_context_set_option", "mer_context_get_option", "mer_debug_bounds", "mer_volume_upload", "mer_volume_upload_dev", "mer_sdf_from_mesh", "mer_volume_download", "mer_volume_build_spline",
     "mer_volume_download_spline", "mer_volume_destroy", "mer_film_channels", "mer_film_alloc_n", "mer_film_zero_n",
     "mer_film_download_n", "mer_film_alloc", "mer_film_zero", "mer_film_download",
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
@@ -456,6 +456,30 @@ class Context:
         h = C.c_int32()
         self._check(self.lib.mer_volume_upload_dev(self.h, C.byref(d), C.c_void_p(dev_ptr), C.c_int32(layout), C.byref(h)))
         return Volume(self, h.value, d, layout)
+
+    def sdf_from_mesh(self, vertices, triangles, res, aabb_min, aabb_max, layout=LAYOUT_DENSE, max_triangles_per_launch=0, return_winding=False):
+        """mer_sdf_from_mesh: the signed-distance grid (negative inside) of a triangle mesh as a Volume.  vertices float [V][3], triangles
+        int [T][3], res = (nx, ny, nz); max_triangles_per_launch = 0: the library's default chunk.  return_winding: -> (Volume, w[z][y][x])."""
+        v = np.ascontiguousarray(np.asarray(vertices, np.float32).reshape(-1, 3))
+        t = np.ascontiguousarray(np.asarray(triangles, np.int32).reshape(-1, 3))
+        nx, ny, nz = (int(r) for r in res)
+        d = self._desc((nz, ny, nx), 1, P.VOL_F32, aabb_min, aabb_max)
+        w = np.empty((nz, ny, nx), np.float32) if return_winding else None
+        h = C.c_int32()
+        self._check(self.lib.mer_sdf_from_mesh(self.h, C.byref(d), _fp(v), C.c_int64(v.shape[0]), _fp(t), C.c_int64(t.shape[0]),
+                                               C.c_int32(max_triangles_per_launch), C.c_int32(layout), _fp(w) if w is not None else None, C.byref(h)))
+        vol = Volume(self, h.value, d, layout)
+        return (vol, w) if return_winding else vol
+
+    def volume_download(self, vol):
+        """mer_volume_download: the dense float32 payload [z][y][x] of a 1-channel float32 Volume"""
+        if vol.desc is None:
+            raise MerError("volume_download: an envmap handle has no grid payload")
+        if vol.desc.channels != 1 or vol.desc.dtype != P.VOL_F32:
+            raise MerError("volume_download: only a 1-channel float32 volume can be downloaded")
+        out = np.empty((vol.desc.res[2], vol.desc.res[1], vol.desc.res[0]), np.float32)
+        self._check(self.lib.mer_volume_download(self.h, C.c_int32(vol.handle), _fp(out)))
+        return out
 
     def synth_volume(self, kind, N, layout=LAYOUT_DENSE, aabb_min=(-1, -1, -1), aabb_max=(1, 1, 1)):
         """Synthetic field generated in HBM (0 = sigma_t density, 1 = linear RIF, 2 = radial RIF)."""

@@ -291,6 +291,61 @@ int mer_volume_upload_dev(mer_context *ctx, const mer_grid_desc *desc, const voi
     return volume_upload(ctx, desc, data_dev, true, layout, out);
 }
 
+int mer_sdf_from_mesh(mer_context *ctx, const mer_grid_desc *desc, const float *vertices, int64_t n_vertices, const int32_t *triangles, int64_t n_triangles,
+                      int32_t max_triangles_per_launch, int32_t layout, float *winding_host, mer_volume *out) {
+    MER_USE_DEVICE(ctx);
+    if (!ctx || !desc || !out) return 1;
+    // everything is refused here, before anything reaches the device
+    if (desc->channels != 1 || desc->dtype != MER_VOL_F32) return fail(ctx, "mer_sdf_from_mesh: the grid must have channels = 1 and dtype = MER_VOL_F32");
+    for (int a = 0; a < 3; a++) if (desc->res[a] < 2) return fail(ctx, "mer_sdf_from_mesh: the grid needs at least 2 nodes along every axis");
+    if ((int64_t) desc->res[0] * desc->res[1] * desc->res[2] > (int64_t) 1 << 31) return fail(ctx, "mer_sdf_from_mesh: more than 2^31 nodes");
+    for (int a = 0; a < 3; a++)
+        if (!std::isfinite(desc->aabb_min[a]) || !std::isfinite(desc->aabb_max[a]) || !(desc->aabb_min[a] < desc->aabb_max[a]))
+            return fail(ctx, "mer_sdf_from_mesh: the box is empty or not finite");
+    for (int i = 0; i < 12; i++) if (desc->world_to_volume[i] != 0.0f) return fail(ctx, "mer_sdf_from_mesh: a non-zero world_to_volume is not supported");
+    if (max_triangles_per_launch < 0) return fail(ctx, "mer_sdf_from_mesh: max_triangles_per_launch must not be negative");
+    if (n_triangles < 1 || n_triangles > ((int64_t) 1 << 22) || !triangles) return fail(ctx, "mer_sdf_from_mesh: n_triangles must be in [1, 2^22]");
+    if (n_vertices < 1 || !vertices) return fail(ctx, "mer_sdf_from_mesh: the mesh has no vertices");
+    for (int64_t i = 0; i < 3 * n_triangles; i++)
+        if (triangles[i] < 0 || triangles[i] >= n_vertices) return fail(ctx, "mer_sdf_from_mesh: triangle index out of range");
+    for (int64_t i = 0; i < 3 * n_vertices; i++) if (!std::isfinite(vertices[i])) return fail(ctx, "mer_sdf_from_mesh: a vertex is not finite");
+    // drop triangles with a repeated index or an exactly zero cross product; 12 floats per kept triangle
+    std::vector<float> tri12;
+    tri12.reserve((size_t) n_triangles * 12);
+    for (int64_t t = 0; t < n_triangles; t++) {
+        const int32_t i0 = triangles[3 * t], i1 = triangles[3 * t + 1], i2 = triangles[3 * t + 2];
+        if (i0 == i1 || i1 == i2 || i0 == i2) continue;
+        const float *a = vertices + 3 * (size_t) i0, *b = vertices + 3 * (size_t) i1, *c = vertices + 3 * (size_t) i2;
+        const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        const float nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2], nz = e1[0] * e2[1] - e1[1] * e2[0];
+        if (nx == 0.0f && ny == 0.0f && nz == 0.0f) continue;
+        for (const float *v : {a, b, c}) { tri12.push_back(v[0]); tri12.push_back(v[1]); tri12.push_back(v[2]); tri12.push_back(0.0f); }
+    }
+    const int64_t kept = (int64_t) (tri12.size() / 12);
+    if (kept == 0) return fail(ctx, "mer_sdf_from_mesh: no triangle left after dropping the degenerate ones");
+    float *sdf_dev = nullptr, *w_dev = nullptr;
+    if (sdf_build(ctx, desc, tri12.data(), kept, max_triangles_per_launch, &sdf_dev, &w_dev)) return 1;
+    const size_t nodes = (size_t) desc->res[0] * desc->res[1] * desc->res[2];
+    int rc = 0;
+    if (winding_host && hipMemcpy(winding_host, w_dev, nodes * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, "mer_sdf_from_mesh: copy of the winding numbers failed");
+    if (!rc) rc = volume_upload(ctx, desc, sdf_dev, true, layout, out);         // the path of mer_volume_upload_dev
+    (void) hipFree(sdf_dev); (void) hipFree(w_dev);
+    return rc;
+}
+
+int mer_volume_download(mer_context *ctx, mer_volume h, float *data_host) {
+    MER_USE_DEVICE(ctx);
+    if (!ctx || !data_host) return 1;
+    if (ctx->envmaps.count(h)) return fail(ctx, "mer_volume_download: an envmap handle has no grid payload");
+    auto it = ctx->volumes.find(h);
+    if (it == ctx->volumes.end()) return fail(ctx, "invalid volume handle");
+    const Volume &v = it->second;
+    if (v.desc.channels != 1 || v.desc.dtype != MER_VOL_F32) return fail(ctx, "mer_volume_download: only a 1-channel float32 volume can be downloaded");
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(ctx, hipMemcpy(data_host, v.dense, v.bytes_dense, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int mer_volume_build_spline(mer_context *ctx, mer_volume h) {
     MER_USE_DEVICE(ctx);
     auto it = ctx->volumes.find(h);

@@ -146,4 +146,11 @@ int tile_skew_for(int tiles_x, int tile_count, int tile_deal);
 int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
                   uint64_t n_film, uint64_t n_path_out);
 
+// mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
+// validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.
+struct SdfGridArgs { int32_t res[3]; float lo[3], step[3]; uint64_t n_nodes; unsigned long long *chk; };
+#define MER_SDF_DEFAULT_CHUNK 4096                         // triangles per launch when the caller passes 0
+#define MER_SDF_NODES_PER_LAUNCH ((uint64_t) 1 << 24)      // nodes per launch (256^3): with the default chunk 6.9e10 pairs per launch
+int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host, int64_t n_tri, int32_t max_tri_per_launch, float **sdf_dev, float **w_dev);
+
 }  // namespace mer

@@ -37,6 +37,25 @@ def flatten_xml(path, defines=None):
     return d, spp.value
 
 
+def obj_mesh(path, defines=None):
+    """The faces the scene's `obj` medium shape exposes (toWorld applied): (vertices float32 [V][3], triangles int32 [T][3])"""
+    nv = C.c_int64(); nt = C.c_int64()
+    if lib().merhost_obj_mesh(path.encode(), _defs(defines), C.byref(nv), C.byref(nt), None, None) != 0:
+        raise HostError(lib().merhost_last_error().decode())
+    v = np.zeros((nv.value, 3), np.float32); t = np.zeros((nt.value, 3), np.int32)
+    if lib().merhost_obj_mesh(path.encode(), _defs(defines), C.byref(nv), C.byref(nt), v.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p)) != 0:
+        raise HostError(lib().merhost_last_error().decode())
+    return v, t
+
+
+def flatten_xml_mesh_sdf(path, n=0, defines=None):
+    """Parse + validate as `mer_render --mesh-sdf[=N]` does (n = 0: no N): (capi.SceneDesc, capi.GridDesc of the grid that would be built)"""
+    d = capi.SceneDesc(); g = capi.GridDesc()
+    if lib().merhost_flatten_xml_mesh_sdf(path.encode(), _defs(defines), C.c_int32(n), C.byref(d), C.byref(g)) != 0:
+        raise HostError(lib().merhost_last_error().decode())
+    return d, g
+
+
 def render_xml(path, defines=None, device=0, spp=0, seed=0, layout=capi.LAYOUT_AUTO, devices=None, shard=capi.SHARD_SAMPLES):
     """devices: a list of GPU indices renders on all of them (mer_multi_*: shard = capi.SHARD_SAMPLES | SHARD_TILES); None = `device` alone"""
     d, _ = flatten_xml(path, defines)

@@ -390,13 +390,28 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             if (o->boundaryError.empty() && (std::fabs(m[0] - m[5]) > 1e-6f || std::fabs(m[0] - m[10]) > 1e-6f)) o->boundaryError = "sphere: non-uniform scales are not supported";
             o->center[0] = c.x * m[0] + m[3]; o->center[1] = c.y * m[5] + m[7]; o->center[2] = c.z * m[10] + m[11]; o->radius = r * std::fabs(m[0]);
         } else if (type == "obj") {
-            // bounding box of the vertices (scenes/volumetric/bounds.obj is the cube [-1,1]^3)
+            // bounding box of the vertices (scenes/volumetric/bounds.obj is the cube [-1,1]^3); the faces are kept for --mesh-sdf
             std::ifstream f(resolve(props.getString("filename")));
             if (!f) Log_EError("The file \"" + resolve(props.getString("filename")) + "\" does not exist!");
             std::string line; bool any = false; float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
+            o->isObj = true;
             while (std::getline(f, line)) {
                 if (line.size() > 2 && line[0] == 'v' && std::isspace((unsigned char) line[1])) {
-                    float v[3]; if (std::sscanf(line.c_str() + 1, "%f %f %f", v, v + 1, v + 2) == 3) { any = true; for (int i = 0; i < 3; i++) { lo[i] = std::min(lo[i], v[i]); hi[i] = std::max(hi[i], v[i]); } }
+                    float v[3]; if (std::sscanf(line.c_str() + 1, "%f %f %f", v, v + 1, v + 2) == 3) {
+                        any = true; for (int i = 0; i < 3; i++) { lo[i] = std::min(lo[i], v[i]); hi[i] = std::max(hi[i], v[i]); o->meshVertices.push_back(v[i] * m[i * 4 + i] + m[i * 4 + 3]); }
+                    }
+                } else if (o->meshError.empty() && line.size() > 2 && line[0] == 'f' && std::isspace((unsigned char) line[1])) {
+                    // i, i/j, i/j/k, i//k: the vertex index; negative = relative to the vertices read so far; a polygon is a fan around its first vertex
+                    std::vector<int32_t> idx; const char *q = line.c_str() + 1;
+                    while (*q) {
+                        while (*q && std::isspace((unsigned char) *q)) q++;
+                        if (!*q || *q == '#') break;
+                        char *e = NULL; const long i = std::strtol(q, &e, 10);
+                        if (e == q || i == 0) { o->meshError = "obj: malformed face record \"" + line + "\""; idx.clear(); break; }      // raised by --mesh-sdf only: without it the faces are not used
+                        idx.push_back((int32_t) (i > 0 ? i - 1 : (long) (o->meshVertices.size() / 3) + i));
+                        q = e; while (*q && !std::isspace((unsigned char) *q)) q++;
+                    }
+                    for (size_t k = 1; k + 1 < idx.size(); k++) { o->meshTriangles.push_back(idx[0]); o->meshTriangles.push_back(idx[k]); o->meshTriangles.push_back(idx[k + 1]); }
                 }
             }
             if (!any) Log_EError("obj: no vertices found");
@@ -788,6 +803,7 @@ static bool point_inside_shape(const mer_scene_desc &d, const Medium &m, const f
         return d2 < d.sph_radius * d.sph_radius;
     }
     if (d.boundary != MER_BOUNDARY_SDF) { bool in = true; for (int i = 0; i < 3; i++) in = in && p[i] >= d.bmin[i] && p[i] <= d.bmax[i]; return in; }
+    if (!m.sdf) Log_EError("--mesh-sdf: a point or spot emitter with a hroughdielectric boundary needs the grid before it is built; write it with `python -m mitsubaer_amd.meshsdf` and name it as the `sdf` child");
     const VolumeDataSource &v = *m.sdf;
     const float *W = v.worldToVolume; bool ident = true; for (int i = 0; i < 12; i++) ident = ident && W[i] == 0.0f;
     float q[3];
@@ -808,7 +824,7 @@ static bool point_inside_shape(const mer_scene_desc &d, const Medium &m, const f
     return val < 0;
 }
 
-void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
+void Integrator::flatten(const Scene &scene, mer_scene_desc &d, const mer_grid_desc *meshGrid) const {
     std::memset(&d, 0, sizeof(d));
     const Sensor &se = *scene.sensor; const Film &fi = *se.film;
     d.width = fi.width; d.height = fi.height;
@@ -846,6 +862,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
         if (m.sdf->isConstant() || m.sdf->channels != 1 || m.sdf->dtype != MER_VOL_F32) Log_EError("heterogeneousrefractive: the sdf must be a 1-channel float32 grid volume");
         d.boundary = MER_BOUNDARY_SDF;
     }
+    if (meshGrid) d.boundary = MER_BOUNDARY_SDF;          // the grid render() builds from the shape's faces
     const bool grid = m.density != NULL;
     d.sigma_mode = grid ? MER_SIGMA_GRID : MER_SIGMA_HOMOGENEOUS;
     for (int i = 0; i < 3; i++) { d.sigma_a[i] = m.sigmaA.c[i]; d.sigma_s[i] = m.sigmaS.c[i]; }
@@ -863,10 +880,14 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     d.stepper = m.stepper; d.stepsize = m.stepsize;
     d.aggressive_tracing = 0; d.sdf_max_error = 0.0f;
     if (m.aggressiveTracing) {
-        if (!m.sdf) Log_EError("aggressivetracing needs the medium's `sdf` volume");
+        if (!m.sdf && !meshGrid) Log_EError("aggressivetracing needs the medium's `sdf` volume");
         d.aggressive_tracing = 1;
         double e2 = 0;                                                       // maxSDFError(): one voxel diagonal (splinevolume.cpp:282)
-        for (int i = 0; i < 3; i++) { const double st = ((double) m.sdf->aabb_max[i] - m.sdf->aabb_min[i]) / (m.sdf->res[i] - 1); e2 += st * st; }
+        for (int i = 0; i < 3; i++) {
+            const double st = meshGrid ? ((double) meshGrid->aabb_max[i] - meshGrid->aabb_min[i]) / (meshGrid->res[i] - 1)
+                                       : ((double) m.sdf->aabb_max[i] - m.sdf->aabb_min[i]) / (m.sdf->res[i] - 1);
+            e2 += st * st;
+        }
         d.sdf_max_error = (float) std::sqrt(e2);
     }
     d.phase = m.phase->kind; d.g = m.phase->g;
@@ -941,6 +962,45 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d) const {
     }
 }
 
+void Integrator::meshSdfGrid(const Scene &scene, int n, mer_grid_desc &g) const {
+    const Shape *shape = NULL;
+    for (auto &s : scene.shapes) if (s->interior) { if (shape) Log_EError("Only one shape with an interior medium is supported on the GPU path"); shape = s.get(); }
+    if (!shape) Log_EError("No shape with an 'interior' medium was found");
+    const Medium &m = *shape->interior;
+    if (!m.isheterogeneousrefractive()) Log_EError("--mesh-sdf: the medium is \"" + m.kind + "\"; only heterogeneousrefractive has an `sdf` boundary");
+    if (m.sdf) Log_EError("--mesh-sdf: the medium already has an `sdf` child; drop the flag or the child");
+    if (!shape->isObj) Log_EError("--mesh-sdf: the medium shape is no `obj` shape; a cube or sphere is its own exact boundary");
+    if (!shape->meshError.empty()) Log_EError("--mesh-sdf: " + shape->meshError);
+    if (n < 0 || n == 1) Log_EError("--mesh-sdf=N: N must be at least 2");
+    // the mesh as mer_sdf_from_mesh validates it (mitsubaer_amd/meshio.py: validate)
+    const std::vector<float> &V = shape->meshVertices; const std::vector<int32_t> &T = shape->meshTriangles;
+    const int64_t nv = (int64_t) V.size() / 3, nt = (int64_t) T.size() / 3;
+    if (nt < 1 || nt > ((int64_t) 1 << 22)) Log_EError("--mesh-sdf: the obj file must have between 1 and 2^22 triangles (it has " + std::to_string(nt) + ")");
+    for (int32_t i : T) if (i < 0 || i >= nv) Log_EError("--mesh-sdf: the obj file has a face index out of range");
+    float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
+    for (size_t i = 0; i < V.size(); i++) { if (!std::isfinite(V[i])) Log_EError("--mesh-sdf: the obj file has a vertex that is not finite"); lo[i % 3] = std::min(lo[i % 3], V[i]); hi[i % 3] = std::max(hi[i % 3], V[i]); }
+    std::memset(&g, 0, sizeof(g));
+    g.channels = 1; g.dtype = MER_VOL_F32;
+    const bool gridRif = m.rif && !m.rif->isAcoustic() && !m.rif->isConstant();
+    if (n == 0) {
+        // the reference requires the sdf's box to match the rif's (heterogeneousrefractive.cpp:1177-1193): take box and resolution from it
+        if (!gridRif) Log_EError("--mesh-sdf: the medium has no gridded `rif` volume to take the grid from; give the resolution as --mesh-sdf=N");
+        for (int i = 0; i < 12; i++) if (m.rif->worldToVolume[i] != 0.0f) Log_EError("--mesh-sdf: the `rif` volume has a toWorld transform; give the resolution as --mesh-sdf=N");
+        for (int i = 0; i < 3; i++) { g.res[i] = m.rif->res[i]; g.aabb_min[i] = m.rif->aabb_min[i]; g.aabb_max[i] = m.rif->aabb_max[i]; }
+    } else {
+        // the mesh's bounding box grown by 5 % per side, n nodes on the longest axis, the same spacing on the others (the box grows to whole cells)
+        float ext[3], longest = 0;
+        for (int i = 0; i < 3; i++) { ext[i] = (hi[i] - lo[i]) * 1.1f; longest = std::max(longest, ext[i]); }
+        if (!(longest > 0)) Log_EError("--mesh-sdf: the mesh has no extent");
+        const float h = longest / (float) (n - 1);
+        for (int i = 0; i < 3; i++) {
+            const int cells = std::max(1, (int) std::ceil(ext[i] / h - 1e-4f));
+            const float mid = 0.5f * (lo[i] + hi[i]), half = 0.5f * (float) cells * h;
+            g.res[i] = cells + 1; g.aabb_min[i] = mid - half; g.aabb_max[i] = mid + half;
+        }
+    }
+}
+
 std::vector<float> Integrator::render(const Scene &scene, int device, int spp, unsigned long long seed, int layout) const {
     return render(scene, std::vector<int>(1, device), MER_SHARD_SAMPLES, spp, seed, layout);
 }
@@ -948,8 +1008,10 @@ std::vector<float> Integrator::render(const Scene &scene, int device, int spp, u
 // One or several GPUs: mer_multi owns a context per device, replicates the volumes and reduces the films (RCCL between distinct devices).
 // The reference's counterpart: `mitsuba -p <workers>` local workers merged by film->put (src/mitsuba/mitsuba.cpp:281,
 // src/librender/renderproc.cpp:142-149).
-std::vector<float> Integrator::render(const Scene &scene, const std::vector<int> &devices, int shardMode, int spp, unsigned long long seed, int layout) const {
-    mer_scene_desc d; flatten(scene, d);
+std::vector<float> Integrator::render(const Scene &scene, const std::vector<int> &devices, int shardMode, int spp, unsigned long long seed, int layout, int meshSdf, bool ordered) const {
+    mer_scene_desc d; mer_grid_desc meshGrid;
+    if (meshSdf >= 0) { meshSdfGrid(scene, meshSdf, meshGrid); flatten(scene, d, &meshGrid); }
+    else flatten(scene, d);
     if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
     if (devices.empty()) Log_EError("Integrator::render: no device given");
     mer_multi *mm = NULL;
@@ -974,6 +1036,19 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
         if (m.rif->isSpline() && mer_multi_volume_build_spline(mm, d.rif)) fail();
     }
     if (m.sdf) d.sdf = upload(*m.sdf, MER_LAYOUT_DENSE);
+    if (meshSdf >= 0) {        // built once on the first device, downloaded, and replicated like a grid read from a file (one path for one GPU and for several:
+                               // a single-GPU render pays one download and one upload of the grid for it)
+        const Shape *shape = NULL; for (auto &s : scene.shapes) if (s->interior) shape = s.get();
+        mer_context *c0 = mer_multi_context(mm, 0);
+        auto fail0 = [&](void) { std::string msg = mer_last_error(c0); mer_multi_destroy(mm); Log_EError(msg); };
+        mer_volume built = 0;
+        if (mer_sdf_from_mesh(c0, &meshGrid, shape->meshVertices.data(), (int64_t) shape->meshVertices.size() / 3, shape->meshTriangles.data(),
+                              (int64_t) shape->meshTriangles.size() / 3, 0, MER_LAYOUT_DENSE, NULL, &built)) fail0();
+        std::vector<float> grid((size_t) meshGrid.res[0] * meshGrid.res[1] * meshGrid.res[2]);
+        if (mer_volume_download(c0, built, grid.data())) { const std::string msg = mer_last_error(c0); (void) mer_volume_destroy(c0, built); mer_multi_destroy(mm); Log_EError(msg); }
+        if (mer_volume_destroy(c0, built)) fail0();
+        if (mer_multi_volume_upload(mm, &meshGrid, grid.data(), MER_LAYOUT_DENSE, &d.sdf)) fail();
+    }
     {   // the envmap's image (its list entry comes out of flatten with handle 0)
         size_t k = 0;
         for (auto &e : scene.emitters) {
@@ -985,7 +1060,16 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
     }
     if (mer_film_channels(mer_multi_context(mm, 0), &d, &channels)) { std::string msg = mer_last_error(mer_multi_context(mm, 0)); mer_multi_destroy(mm); Log_EError(msg); }
     std::vector<float> film((size_t) d.width * d.height * channels, 0.0f);
-    if (mer_multi_render(mm, &d, shardMode, 0, spp, seed, 1, film.data())) fail();
+    if (!ordered) { if (mer_multi_render(mm, &d, shardMode, 0, spp, seed, 1, film.data())) fail(); }
+    else {
+        // one render per sample index, the films added here in index order: the film's float atomics then meet, per pixel, only the splats of
+        // one sample pass, so a film whose samples land in one pixel each (box filter, radius 0.5) is the same bit for bit in every run
+        std::vector<float> one(film.size());
+        for (int k = 0; k < spp; k++) {
+            if (mer_multi_render(mm, &d, shardMode, k, 1, seed, 1, one.data())) fail();
+            for (size_t i = 0; i < film.size(); i++) film[i] += one[i];
+        }
+    }
     mer_multi_destroy(mm);
     return film;
 }
@@ -1175,6 +1259,28 @@ int merhost_flatten_xml(const char *path, const char *defines, mer_scene_desc *o
         g_flat_emitters = scene->emitterList;
         out->emitters = out->n_emitters ? g_flat_emitters.data() : nullptr;
         if (spp) *spp = scene->sensor->sampler->sampleCount;
+        return 0;
+    } catch (const std::exception &e) { g_host_error = e.what(); return 1; }
+}
+int merhost_obj_mesh(const char *path, const char *defines, int64_t *n_vertices, int64_t *n_triangles, float *vertices, int32_t *triangles) {
+    try {
+        auto scene = merhost::loadScene(path, parseDefines(defines));
+        const merhost::Shape *shape = NULL;
+        for (auto &s : scene->shapes) if (s->interior && s->isObj) shape = s.get();
+        if (!shape) throw std::runtime_error("the scene has no `obj` medium shape");
+        if (n_vertices) *n_vertices = (int64_t) shape->meshVertices.size() / 3;
+        if (n_triangles) *n_triangles = (int64_t) shape->meshTriangles.size() / 3;
+        if (vertices) std::memcpy(vertices, shape->meshVertices.data(), shape->meshVertices.size() * sizeof(float));
+        if (triangles) std::memcpy(triangles, shape->meshTriangles.data(), shape->meshTriangles.size() * sizeof(int32_t));
+        return 0;
+    } catch (const std::exception &e) { g_host_error = e.what(); return 1; }
+}
+int merhost_flatten_xml_mesh_sdf(const char *path, const char *defines, int32_t n, mer_scene_desc *out, mer_grid_desc *grid) {
+    try {
+        auto scene = merhost::loadScene(path, parseDefines(defines));
+        scene->integrator->meshSdfGrid(*scene, n, *grid);
+        scene->integrator->flatten(*scene, *out, grid);
+        out->emitters = nullptr; out->n_emitters = 0;           // the list lives in the scene, which ends here
         return 0;
     } catch (const std::exception &e) { g_host_error = e.what(); return 1; }
 }

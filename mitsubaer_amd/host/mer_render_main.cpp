@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cstdio>
@@ -9,6 +9,8 @@ int main(int argc, char **argv) {
     std::map<std::string, std::string> defines;
     std::string out = "out.npy", scenePath;
     int spp = 0, device = 0, layout = MER_LAYOUT_AUTO; unsigned long long seed = 0; bool raw = false;
+    bool ordered = false;          // --ordered: one render per sample index, films added in index order
+    int meshSdf = -1;              // --mesh-sdf[=N]: -1 off, 0 = the rif volume's grid, N = nodes on the longest axis of the mesh's box
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -24,7 +26,18 @@ int main(int argc, char **argv) {
         else if (a == "--dense") layout = MER_LAYOUT_DENSE;
         else if (a == "--cell8") layout = MER_LAYOUT_CELL8;
         else if (a == "--raw") raw = true;
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] scene.xml\n"
+        else if (a == "--ordered") ordered = true;
+        else if (a == "--mesh-sdf") meshSdf = 0;
+        else if (a.rfind("--mesh-sdf=", 0) == 0) {
+            char *e = NULL; const long n = std::strtol(a.c_str() + 11, &e, 10);
+            if (e == a.c_str() + 11 || *e || n < 2 || n > 4096) { std::fprintf(stderr, "--mesh-sdf=N expects a node count between 2 and 4096\n"); return 2; }
+            meshSdf = (int) n;
+        }
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] scene.xml\n"
+                                                         "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
+                                                         "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
+                                                         "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
+                                                         "  samples (bit-reproducible when every sample lands in one pixel: box filter of radius 0.5); slower\n"
                                                          "  --gpus N / --devices: one context per listed GPU, volumes replicated, samples (default) or 32x32 image tiles (--tiles) sharded over them,\n"
                                                          "  films reduced with RCCL (distinct devices) or peer copies (a device listed twice)\n"); return 0; }
         else scenePath = a;
@@ -34,7 +47,7 @@ int main(int argc, char **argv) {
         auto scene = merhost::loadScene(scenePath, defines);
         const int w = scene->sensor->film->width, h = scene->sensor->film->height;
         if (devices.empty()) devices.push_back(device);
-        std::vector<float> film = scene->integrator->render(*scene, devices, shardMode, spp, seed, layout);
+        std::vector<float> film = scene->integrator->render(*scene, devices, shardMode, spp, seed, layout, meshSdf, ordered);
         const int frames = scene->sensor->film->frames();
         if (raw) merhost::writeNpy(out, film.data(), h, w, frames * 3 + 2);
         else {
