@@ -89,9 +89,15 @@ typedef struct {
    boundary's radius < radius; cube: its farthest corner closer than the radius); a disk outside it (sphere boundary: the disk's point
    closest to the centre lies outside -- exact; cube: the disk's circumscribed square passes the rectangle / box test -- conservative: a
    disk near a cube's edge or corner can be refused although it does not touch).  Same scope as the rectangle: rif_mode = MER_RIF_CONST,
-   index-matched cube / sphere boundary, no point or spot emitter outside the medium shape in the same list. */
+   index-matched cube / sphere boundary, no point or spot emitter outside the medium shape in the same list.
+   MER_EMITTER_COLLIMATED: emitter `collimated` (src/emitters/collimated.cpp:56-134), a beam that is a delta in position and direction --
+   list entries only, integrator = MER_INTEGRATOR_PTRACER only (no camera path can sample it: with volpath it is refused, it could only
+   render black).  to_world = the beam's frame (row-major 3x4): the origin is its translation column, the direction the image of (0,0,1);
+   a linear part that is not a rotation within 1e-4 is refused with the reference's message ("Scale factors in the emitter-to-world
+   transformation are not allowed!", :63-65).  intensity = the beam's `power` (:61,85,123).  The other fields are ignored. */
 #define MER_MAX_EMITTERS 32
-enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3, MER_EMITTER_ENVMAP = 4, MER_EMITTER_AREA_DISK = 5, MER_EMITTER_AREA_SPHERE = 6 };
+enum { MER_EMITTER_POINT = 1, MER_EMITTER_AREA = 2, MER_EMITTER_SPOT = 3, MER_EMITTER_ENVMAP = 4, MER_EMITTER_AREA_DISK = 5, MER_EMITTER_AREA_SPHERE = 6,
+       MER_EMITTER_COLLIMATED = 7 };
 typedef struct {
     int32_t type;
     float   position[3], intensity[3];
@@ -182,6 +188,33 @@ typedef struct {
        MIS partner (volpath.cpp:120-173,370-428).  All-zero radiance = none.  The rectangle lies outside the medium shape.  Straight rays
        (rif_mode = MER_RIF_CONST), index-matched cube / sphere boundary. */
     float   area_to_world[12], area_radiance[3];
+    /* the integrator: MER_INTEGRATOR_VOLPATH (0: path tracing from the sensor, everything above) or MER_INTEGRATOR_PTRACER -- light tracing,
+       the reference's `ptracer` (src/integrators/ptracer/ptracer_proc.cpp, src/librender/particleproc.cpp:107-270) and the t = 1 strategy of its
+       `bdpt`: paths start at an emitter, every scattering vertex is connected to the sensor and splatted onto the pixel the connection
+       arrives at.  It is the estimator for sources no camera path can sample (MER_EMITTER_COLLIMATED).  One light path per (pixel, sample
+       index) of the shard, its sampler stream keyed by that pair as a camera path's is; a tile shard selects paths by pixel id, splats land
+       anywhere on the film.  Film: the layout of mer_film_channels; a contribution goes into RGB with the reconstruction filter's table
+       weights (ImageBlock::put); every (pixel, sample index) adds exactly 1 to that pixel's alpha and weight, so that after S samples
+       weight = S everywhere and RGB / weight is the reference's setBitmap(accum, W H / particles) (ptracer_proc.cpp:200-204).  Straight rays:
+       value = throughput x power x importance / dist^2 x phase x transmittance (PerspectiveCamera::sampleDirect), pixel = its uv.  Curved
+       rays: the vertex is joined to the sensor by the shooting solver of mer_connect; value = sampleDirect's straight-line value x the
+       curved connection's transmittance x the solver weight x phase at the launch direction, and the PIXEL COMES FROM THE ARRIVAL DIRECTION
+       (getSamplePosition of mer_connect's revDir; src/libbidir/vertex.cpp:1334-1348, bdpt_proc.cpp:396-399,432); a failed connection or one
+       outside the frame contributes nothing.  A decomposed film bins by the summed edge lengths (optical on curved segments) plus the
+       connection edge plus the camera edge (the part outside the medium shape; left out under calibrated_transient).  max_depth / rr_depth as
+       particleproc.cpp:163,258-267 (no eta^2 in the roulette) and ptracer_proc.cpp:171-176; the null boundary costs one depth, as in volpath.
+       The null crossing of a connection counts against max_depth with straight rays (scene.cpp:619-678, as volpath's straight kernels have
+       it); with curved rays a path is charged one null crossing at most, as volpath's curved kernels charge it (their emitter connection is
+       free): ptracer and volpath hold the same scattering orders at every max_depth.
+       Scope: the perspective sensor with a rigid cam_to_world (rotation within 1e-4); list entries of kind point, spot (toWorld without
+       scale) and collimated; a cube or sphere with the null BSDF; homogeneous or gridded sigma_t, constant or gridded albedo; rif_mode CONST,
+       TRILINEAR in the dense layout, BSPLINE3, ACOUSTIC; both steppers; steady, transient, bounce and modulated films.  NOT built, refused
+       with a message before anything reaches the device: emission events (ptracer_proc.cpp:83-107) -- a point or spot emitter is not visible
+       directly, exactly as in volpath --, a non-zero env_radiance, envmap and area entries, the legacy point_* / area_* fields, medium
+       emission, the lens and orthographic sensors, the signed-distance boundary, dielectric boundaries, the CELL8 / BRICK record layouts of
+       the index field, method = simpson, and mer_render_paths.  integrator_reserved = 0.  All zero = volpath.  Two words in front
+       of the list pointer, which stays 8-byte aligned: no padding, and the sensor and rough_* fields keep their places at the end. */
+    int32_t integrator, integrator_reserved;
     /* several emitters: n_emitters entries (at most MER_MAX_EMITTERS) of a HOST array the caller owns for the duration of the call (placed
        before the rough_* fields, which stay the last 12 bytes of the struct, pointer first: no padding); every call that takes the scene reads it (each context of a mer_multi uploads it in its own mer_render).  n_emitters = 0: the point_* and
        area_* fields above describe the (at most one) point and area emitter.  n_emitters > 0: those fields must be zero and the list holds
@@ -213,6 +246,7 @@ typedef struct {
 } mer_scene_desc;
 enum { MER_METHOD_WOODCOCK = 0, MER_METHOD_SIMPSON = 1 };
 enum { MER_SENSOR_PERSPECTIVE = 0, MER_SENSOR_ORTHOGRAPHIC = 1, MER_SENSOR_THINLENS = 2, MER_SENSOR_TELECENTRIC = 3 };
+enum { MER_INTEGRATOR_VOLPATH = 0, MER_INTEGRATOR_PTRACER = 1 };
 enum { MER_BSDF_NULL = 0, MER_BSDF_HDIELECTRIC = 1, MER_BSDF_HROUGHDIELECTRIC = 2 };
 enum { MER_MICROFACET_BECKMANN = 0, MER_MICROFACET_GGX = 1, MER_MICROFACET_PHONG = 2 };   /* MicrofacetDistribution::EType order (microfacet.h) */
 enum { MER_MODULATION_NONE = 0, MER_MODULATION_SINE, MER_MODULATION_SQUARE, MER_MODULATION_HAMILTONIAN, MER_MODULATION_MSEQ,
@@ -343,7 +377,9 @@ int  mer_film_free(mer_context *ctx, float *film_dev);
 /* ---- the hot path: replaces SamplingIntegrator::render -> renderBlock -> Li -> ImageBlock::put
         (src/librender/integrator.cpp:95-188, src/integrators/path/volpath.cpp:84-343).
         Accumulates (R,G,B,alpha,weight) splats into film_dev.  Launches on the context stream; returns when the
-        last wavefront pass has been issued and found no live path (it synchronises the stream internally). ---- */
+        last wavefront pass has been issued and found no live path (it synchronises the stream internally).
+        scene->integrator = MER_INTEGRATOR_PTRACER: the light tracer instead (CaptureParticleWorker, ptracer_proc.cpp:167-194), one
+        lane per light path in launches of a fixed number of paths; mer_shard keeps its meaning. ---- */
 int  mer_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard,
                 uint64_t seed, float *film_dev);
 int  mer_synchronize(mer_context *ctx);
@@ -422,9 +458,18 @@ int  mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float 
    MER_SENSOR_PERSPECTIVE o and d are those of mer_camera_rays bit for bit. */
 int  mer_sensor_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, const float *aperture2, int64_t n, float *o, float *d,
                      float *mint, float *maxt);
+/* PerspectiveCamera::sampleDirect (src/sensors/perspective.cpp:387-424, importance :191-245) of the scene's pinhole at n reference points
+   ref[3*i..]: out stride 8: value = importance x invDist^2, the film position in pixels [2], the unit direction from the point to the
+   sensor [3], the distance, 0.  All zero for a point outside the clip range or the frustum.  cam_to_world must be rigid (its inverse is
+   taken as the transpose).  The light tracer's own device function. */
+int  mer_sensor_direct(mer_context *ctx, const mer_scene_desc *scene, const float *ref, int64_t n, float *out);
+/* PerspectiveCamera::getSamplePosition (perspective.cpp:367-385) of n world directions dirs[3*i..] leaving the sensor (need not be unit):
+   out_uv[2*i..] = the film position in pixels, out_ok[i] = 1, or 0 (and uv = 0) behind the sensor or outside the frame.  The light
+   tracer's own device function: the pixel of a curved connection comes from its arrival direction through it. */
+int  mer_sensor_position(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_uv, int32_t *out_ok);
 /* PathLengthSampler::correlationFunction for the scene's modulation (src/librender/pathlengthsampler.cpp:68-114) */
 int  mer_correlation(mer_context *ctx, const mer_scene_desc *scene, const float *path_length, int64_t n, float *out);
-/* per-path radiance Li of sample `sample_index` for every pixel: out[(y*w+x)*3] (no filter) */
+/* per-path radiance Li of sample `sample_index` for every pixel: out[(y*w+x)*3] (no filter); integrator = volpath only */
 int  mer_render_paths(mer_context *ctx, const mer_scene_desc *scene, int32_t sample_index, uint64_t seed, float *out_rgb);
 /* sampler stream known answers */
 int  mer_rng_floats(mer_context *ctx, uint64_t seed, uint32_t pixel, uint32_t sample, int32_t n, float *out);

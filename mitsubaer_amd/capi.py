@@ -23,7 +23,7 @@ SYMBOLS = [
     "mer_film_free", "mer_render", "mer_synchronize", "mer_last_kernel_ms", "mer_last_render_stats", "mer_counters_read",
     "mer_counters_reset", "mer_lookup_trilinear", "mer_lookup_trilinear_rgb", "mer_rif_value_grad", "mer_acoustic_value_grad", "mer_er_trace",
     "mer_sample_distance", "mer_connect", "mer_emitter_direct", "mer_area_direct", "mer_area_hit", "mer_envmap_upload", "mer_envmap_eval", "mer_envmap_sample", "mer_multi_envmap_upload", "mer_eval_transmittance", "mer_phase_sample", "mer_phase_eval", "mer_rough_dielectric_eval",
-    "mer_rough_dielectric_sample", "mer_camera_rays", "mer_sensor_rays",
+    "mer_rough_dielectric_sample", "mer_camera_rays", "mer_sensor_rays", "mer_sensor_direct", "mer_sensor_position",
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
@@ -87,6 +87,7 @@ class SceneDesc(C.Structure):
         ("ac_n_o", C.c_float), ("ac_n_max", C.c_float), ("ac_k_r", C.c_float), ("ac_mode", C.c_int32),
         ("method", C.c_int32), ("het_stepsize", C.c_float),
         ("area_to_world", C.c_float * 12), ("area_radiance", C.c_float * 3),
+        ("integrator", C.c_int32), ("integrator_reserved", C.c_int32),
         ("emitters", C.POINTER(EmitterDesc)), ("n_emitters", C.c_int32),
         ("sensor", C.c_int32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("sensor_reserved", C.c_int32),
         ("rough_distribution", C.c_int32), ("rough_alpha", C.c_float), ("rough_sample_visible", C.c_int32),
@@ -252,6 +253,14 @@ def validate_emitters(p):
             if p.boundary_bsdf == P.BSDF_HROUGHDIELECTRIC and inside:
                 raise MerError(at + "hroughdielectric: the spot emitter must lie outside the medium shape")
             outside_point = outside_point or (p.boundary != P.BOUNDARY_SDF and not inside)
+        elif e["type"] == P.EMITTER_COLLIMATED:
+            if getattr(p, "integrator", P.INTEGRATOR_VOLPATH) != P.INTEGRATOR_PTRACER:
+                raise MerError(at + "a collimated emitter is a delta in position and direction: no camera path can sample it (it would render black); use integrator = ptracer")
+            err = P.collimated_error(e.get("to_world"))
+            if err:
+                raise MerError(at + err)
+            if not all(np.isfinite(v) and v >= 0 for v in e["power"]):
+                raise MerError(at + "emitter radiance / intensity must be non-negative")
         elif e["type"] in P.AREA_TYPES:
             if p.rif_mode != P.RIF_CONST:
                 raise MerError(at + "the area emitter is built for straight rays (rif_mode = CONST)")
@@ -284,6 +293,49 @@ def validate_emitters(p):
             raise MerError(at + "unknown emitter type")
     if has_rect and outside_point:
         raise MerError("emitter list: a point or spot emitter outside the medium shape cannot be combined with an area emitter")
+
+
+def _is_rotation(m, tol=1e-4):
+    R = np.asarray(m, np.float64)[:3, :3].astype(np.float32).astype(np.float64)
+    return bool(np.all(np.isfinite(R)) and np.max(np.abs(R @ R.T - np.eye(3))) <= tol and np.linalg.det(R) > 0)
+
+
+def validate_integrator(p):
+    """The refusals of the integrator field, and of a scene outside the light tracer's scope (integrator = ptracer), as mer_render
+    applies them before anything reaches the device: MerError.  No GPU needed."""
+    integ = getattr(p, "integrator", P.INTEGRATOR_VOLPATH)
+    if integ not in (P.INTEGRATOR_VOLPATH, P.INTEGRATOR_PTRACER):
+        raise MerError("integrator: unknown integrator (volpath, ptracer)")
+    if integ != P.INTEGRATOR_PTRACER:
+        return
+    at = "ptracer: "
+    if p.sensor != P.SENSOR_PERSPECTIVE:
+        raise MerError(at + "light paths are connected to the perspective sensor only (orthographic, thinlens and telecentric are not built)")
+    if not _is_rotation(p.cam_to_world):
+        raise MerError(at + "cam_to_world must be a rigid transformation (its inverse is taken as the transpose)")
+    if any(v != 0 for v in p.env_radiance):
+        raise MerError(at + "a constant environment (env_radiance) is not built for light tracing")
+    if any(v != 0 for v in p.emission):
+        raise MerError(at + "medium emission is not built for light tracing")
+    if any(v != 0 for v in p.point_intensity) or any(v != 0 for v in p.area_radiance):
+        raise MerError(at + "emitters are given as list entries (mer_scene_desc.emitters); the point_* / area_* fields must be zero")
+    ems = list(getattr(p, "emitters", None) or [])
+    if not ems:
+        raise MerError(at + "the scene has no emitter (list entries of kind point, spot or collimated)")
+    for j, e in enumerate(ems[:P.MAX_EMITTERS]):
+        ej = at + "emitter list, entry %d: " % j
+        if e["type"] == P.EMITTER_ENVMAP:
+            raise MerError(ej + "an envmap emitter is not built for light tracing")
+        if e["type"] in P.AREA_TYPES:
+            raise MerError(ej + "area emitters are not built for light tracing")
+        if e["type"] == P.EMITTER_SPOT and not _is_rotation(np.array(_rows3x4(e.get("to_world"))).reshape(3, 4)):
+            raise MerError(ej + "a spot emitter's 'toWorld' must be free of scale for light tracing (its cone is sampled about the z axis)")
+    if p.boundary == P.BOUNDARY_SDF:
+        raise MerError(at + "the signed-distance boundary is not built for light tracing (cube or sphere)")
+    if p.boundary_bsdf != P.BSDF_NULL:
+        raise MerError(at + "dielectric boundaries are not built for light tracing (the index-matched null boundary)")
+    if p.sigma_mode == P.SIGMA_GRID and p.method == P.METHOD_SIMPSON:
+        raise MerError(at + "method = simpson is not built for light tracing (woodcock)")
 
 
 def _upload_scene_envmap(ctx, p, vols):
@@ -501,6 +553,8 @@ class Context:
         s.cam_to_world[:] = [float(v) for v in np.asarray(p.cam_to_world, np.float32).reshape(-1)]
         s.rfilter, s.rfilter_param = p.rfilter, p.rfilter_param
         validate_sensor(p)
+        validate_integrator(p)
+        s.integrator = int(getattr(p, "integrator", P.INTEGRATOR_VOLPATH)); s.integrator_reserved = 0
         s.sensor = int(p.sensor); s.sensor_reserved = 0
         lens = p.sensor in (P.SENSOR_THINLENS, P.SENSOR_TELECENTRIC)
         s.aperture_radius = float(p.aperture_radius) if lens else 0.0
@@ -547,6 +601,8 @@ class Context:
                 elif e.type == P.EMITTER_SPOT:
                     e.to_world[:] = _rows3x4(d.get("to_world")); e.intensity[:] = [float(v) for v in d["intensity"]]
                     e.cutoff_angle_deg = float(d["cutoff_deg"]); e.beam_width_deg = float(d["beam_deg"])
+                elif e.type == P.EMITTER_COLLIMATED:
+                    e.to_world[:] = _rows3x4(d.get("to_world")); e.intensity[:] = [float(v) for v in d["power"]]
                 elif e.type == P.EMITTER_ENVMAP:
                     e.to_world[:] = _rows3x4(d.get("to_world")); e.env_scale = float(d.get("scale", 1.0)); e.env_reserved = 0.0
                     e.envmap = envmap.handle if envmap is not None else int(d.get("handle", 0))
@@ -791,6 +847,21 @@ class Context:
         self._check(self.lib.mer_sensor_rays(self.h, C.byref(scene), _fp(pos2), _fp(ap) if ap is not None else None, C.c_int64(n),
                                              _fp(o), _fp(d), _fp(mint), _fp(maxt)))
         return o, d, mint, maxt
+
+    def sensor_direct(self, scene, ref):
+        """mer_sensor_direct: PerspectiveCamera::sampleDirect at the points ref [n][3] -> [n][8]: value = importance / dist^2, film position
+        (2), unit direction to the sensor (3), distance, 0; all zero outside the clip range or the frustum"""
+        ref = _f32(ref); n = ref.shape[0]
+        out = np.empty((n, 8), np.float32)
+        self._check(self.lib.mer_sensor_direct(self.h, C.byref(scene), _fp(ref), C.c_int64(n), _fp(out)))
+        return out
+
+    def sensor_position(self, scene, dirs):
+        """mer_sensor_position: getSamplePosition of the world directions dirs [n][3] -> (uv [n][2] in pixels, ok [n] bool)"""
+        dirs = _f32(dirs); n = dirs.shape[0]
+        uv = np.empty((n, 2), np.float32); ok = np.empty(n, np.int32)
+        self._check(self.lib.mer_sensor_position(self.h, C.byref(scene), _fp(dirs), C.c_int64(n), _fp(uv), ok.ctypes.data_as(C.c_void_p)))
+        return uv, ok != 0
 
     def correlation(self, scene, path_length):
         t = _f32(path_length); n = t.shape[0]

@@ -557,12 +557,14 @@ int mer_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *s
     if (!ctx || !scene || !film_dev) return 1;
     int32_t ch = 5;
     if (mer_film_channels(ctx, scene, &ch)) return 1;
+    if (scene->integrator == MER_INTEGRATOR_PTRACER) return launch_ptracer(ctx, scene, shard, seed, film_dev, (uint64_t) scene->width * scene->height * (uint64_t) ch);
     return launch_render(ctx, scene, shard, seed, film_dev, nullptr, (uint64_t) scene->width * scene->height * (uint64_t) ch, 0);
 }
 
 int mer_render_paths(mer_context *ctx, const mer_scene_desc *scene, int32_t sample_index, uint64_t seed, float *out_rgb) {
     MER_USE_DEVICE(ctx);
     if (!ctx || !scene || !out_rgb) return 1;
+    if (scene->integrator == MER_INTEGRATOR_PTRACER) return fail(ctx, "mer_render_paths: per-path radiance is a camera-path quantity (integrator = volpath); a light path splats onto many pixels");
     const size_t n = (size_t) scene->width * scene->height * 3;
     DevBuf buf(ctx);
     if (buf.alloc(n * 4)) return 1;

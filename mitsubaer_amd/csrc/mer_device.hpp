@@ -741,8 +741,8 @@ struct Params {
     // sensor: the camera-to-world matrix is sc.cam_to_world.  par_dir = normalize(T e_z) (the parallel kinds' ray direction), lens_radius =
     // apertureRadius (thinlens) or apertureRadius / |T e_x| (telecentric), lens_focus = focusDistance or focusDistance / |T e_z| -- what the
     // reference's constructors / configure() precompute (make_params).  These 40 bytes and the 16 the sensor fields add to sc take the
-    // place of a 56-byte copy of the matrix: Params keeps its size
-    float aspect, cot_half_fov, par_dir[3], lens_radius, lens_focus, sensor_pad[3];
+    // place of a 56-byte copy of the matrix: Params keeps its size (two of the three words of padding went to sc.integrator / integrator_reserved)
+    float aspect, cot_half_fov, par_dir[3], lens_radius, lens_focus, sensor_pad[1];
     float inv_res_x, inv_res_y;
     const float *ftable;                // reconstruction-filter table, 33 floats in device memory: a table INSIDE this struct, indexed per lane, makes the
                                         // compiler copy the whole 2.3 KB kernel-argument struct into scratch (K_connect, the EXTRA K_event)

@@ -146,6 +146,9 @@ int tile_skew_for(int tiles_x, int tile_count, int tile_deal);
 int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
                   uint64_t n_film, uint64_t n_path_out);
 
+// mer_render_ptracer.hip: integrator = MER_INTEGRATOR_PTRACER -- one lane per light path, launched a fixed number of paths at a time
+int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, uint64_t n_film);
+
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
 // validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.
 struct SdfGridArgs { int32_t res[3]; float lo[3], step[3]; uint64_t n_nodes; unsigned long long *chk; };

@@ -348,6 +348,29 @@ static const char *spot_derive(const mer_emitter &e, DSpot &s) {
     return nullptr;
 }
 
+// is the linear part of a row-major 3x4 matrix a rotation (M M^T = 1 within tol, det > 0)?  Transform::hasScale's question (transform.cpp)
+static bool is_rotation(const float m[12], double tol) {
+    for (int i = 0; i < 12; i++) if (!std::isfinite(m[i])) return false;
+    double M[3][3];
+    linear3(m, M);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            const double d = M[r][0] * M[c][0] + M[r][1] * M[c][1] + M[r][2] * M[c][2] - (r == c ? 1.0 : 0.0);
+            if (!(std::fabs(d) <= tol)) return false;
+        }
+    return det3(M) > 0;
+}
+// emitter `collimated` (src/emitters/collimated.cpp:58-66,115-124): the record of its point-table slot -- z = the beam's direction
+// toWorld(0,0,1), both cosines -2 (falloff 1, as a point emitter's) and pad = 1, which marks the slot as a beam for the light tracer.
+static const char *collimated_derive(const mer_emitter &e, DSpot &s) {
+    for (int i = 0; i < 12; i++) if (!std::isfinite(e.to_world[i])) return "collimated emitter: 'toWorld' must be finite";
+    if (!is_rotation(e.to_world, 1e-4)) return "Scale factors in the emitter-to-world transformation are not allowed!";      // collimated.cpp:63-65
+    const double dx = e.to_world[2], dy = e.to_world[6], dz = e.to_world[10], len = std::sqrt(dx * dx + dy * dy + dz * dz);
+    s.z[0] = (float) (dx / len); s.z[1] = (float) (dy / len); s.z[2] = (float) (dz / len);
+    s.cos_cutoff = s.cos_beam = -2.0f; s.cutoff = 0; s.inv_width = 0; s.pad = 1.0f;
+    return nullptr;
+}
+
 // emitter `envmap`: its record from the uploaded map and the entry's toWorld (a rotation within 1e-5; the translation is ignored -- a direction
 // does not see it) and scale.  Returns an error message or nullptr.
 static const char *envmap_derive(mer_context *ctx, const mer_emitter &e, DEnvMap &E) {
@@ -448,6 +471,13 @@ static int emitter_list(mer_context *ctx, const mer_scene_desc &sc, Emitters &em
             if (const char *err = spot_derive(e, cone)) return fail(ctx, at + err);
             const float pos[3] = {e.to_world[3], e.to_world[7], e.to_world[11]};
             if (add_point(ctx, sc, em, pos, e.intensity, &cone, e.sampling_weight, true, at)) return 1;
+        } else if (e.type == MER_EMITTER_COLLIMATED) {   // a beam: a point-table slot whose cone record carries the direction (DSpot::pad = 1); light tracing only
+            if (sc.integrator != MER_INTEGRATOR_PTRACER)
+                return fail(ctx, at + "a collimated emitter is a delta in position and direction: no camera path can sample it (it would render black); use integrator = ptracer");
+            DSpot beam{};
+            if (const char *err = collimated_derive(e, beam)) return fail(ctx, at + err);
+            const float pos[3] = {e.to_world[3], e.to_world[7], e.to_world[11]};
+            if (add_point(ctx, sc, em, pos, e.intensity, &beam, e.sampling_weight, true, at)) return 1;
         } else if (e.type == MER_EMITTER_AREA || e.type == MER_EMITTER_AREA_DISK || e.type == MER_EMITTER_AREA_SPHERE) {   // one kind, one CDF, in list order
             const int shape = e.type == MER_EMITTER_AREA_SPHERE ? AREA_SPHERE : e.type == MER_EMITTER_AREA_DISK ? AREA_DISK : AREA_RECT;
             if (add_rect(ctx, sc, em, shape, e.to_world, e.radiance, e.sampling_weight, true, at)) return 1;
@@ -467,6 +497,36 @@ static int emitter_list(mer_context *ctx, const mer_scene_desc &sc, Emitters &em
 
 // ---- the steps of make_params, in its order -----------------------------------------------------------------------------------------
 
+// integrator = ptracer: what the light tracer (mer_ptracer.hpp) is built for; everything else is refused here, from the scene's fields alone,
+// before any step touches the device
+static int ptracer_scope(mer_context *ctx, const mer_scene_desc &sc) {
+    const std::string at = "ptracer: ";
+    if (sc.sensor != MER_SENSOR_PERSPECTIVE) return fail(ctx, at + "light paths are connected to the perspective sensor only (orthographic, thinlens and telecentric are not built)");
+    if (!is_rotation(sc.cam_to_world, 1e-4)) return fail(ctx, at + "cam_to_world must be a rigid transformation (its inverse is taken as the transpose)");
+    if (sc.env_radiance[0] != 0 || sc.env_radiance[1] != 0 || sc.env_radiance[2] != 0) return fail(ctx, at + "a constant environment (env_radiance) is not built for light tracing");
+    if (sc.emission[0] != 0 || sc.emission[1] != 0 || sc.emission[2] != 0) return fail(ctx, at + "medium emission is not built for light tracing");
+    if (sc.point_intensity[0] != 0 || sc.point_intensity[1] != 0 || sc.point_intensity[2] != 0 || sc.area_radiance[0] != 0 || sc.area_radiance[1] != 0 || sc.area_radiance[2] != 0)
+        return fail(ctx, at + "emitters are given as list entries (mer_scene_desc.emitters); the point_* / area_* fields must be zero");
+    if (sc.n_emitters <= 0 || !sc.emitters) return fail(ctx, at + "the scene has no emitter (list entries of kind point, spot or collimated)");
+    for (int j = 0; j < sc.n_emitters && j < MER_MAX_EMITTERS; ++j) {
+        const mer_emitter &e = sc.emitters[j];
+        const std::string ej = at + "emitter list, entry " + std::to_string(j) + ": ";
+        if (e.type == MER_EMITTER_ENVMAP) return fail(ctx, ej + "an envmap emitter is not built for light tracing");
+        if (e.type == MER_EMITTER_AREA || e.type == MER_EMITTER_AREA_DISK || e.type == MER_EMITTER_AREA_SPHERE) return fail(ctx, ej + "area emitters are not built for light tracing");
+        if (e.type == MER_EMITTER_SPOT && !is_rotation(e.to_world, 1e-4)) return fail(ctx, ej + "a spot emitter's 'toWorld' must be free of scale for light tracing (its cone is sampled about the z axis)");
+    }
+    if (sc.boundary == MER_BOUNDARY_SDF) return fail(ctx, at + "the signed-distance boundary is not built for light tracing (cube or sphere)");
+    if (sc.boundary_bsdf != MER_BSDF_NULL) return fail(ctx, at + "dielectric boundaries are not built for light tracing (the index-matched null boundary)");
+    if (sc.sigma_mode == MER_SIGMA_GRID && sc.method == MER_METHOD_SIMPSON) return fail(ctx, at + "method = simpson is not built for light tracing (woodcock)");
+    if (sc.stepper != MER_STEP_VERLET && sc.stepper != MER_STEP_RK4 && sc.rif_mode != MER_RIF_CONST) return fail(ctx, at + "unknown stepper (verlet, rk4)");
+    if (sc.rif_mode == MER_RIF_TRILINEAR) {
+        auto it = ctx->volumes.find(sc.rif);
+        if (it != ctx->volumes.end() && it->second.cell8)
+            return fail(ctx, at + "the index field must be uploaded in the dense layout (the CELL8 / BRICK record layouts are not built for light tracing)");
+    }
+    return 0;
+}
+
 static int integrator(mer_context *ctx, const mer_scene_desc &sc, Params &P) {
     if (sc.width <= 0 || sc.height <= 0) return fail(ctx, "film: width/height must be positive");
     if (sc.rr_depth <= 0) return fail(ctx, "'rrDepth' must be set to a value greater than zero!");                 // integrator.cpp:217
@@ -474,6 +534,9 @@ static int integrator(mer_context *ctx, const mer_scene_desc &sc, Params &P) {
         return fail(ctx, "'maxDepth' must be set to -1 (infinite) or a value greater than zero!");                  // integrator.cpp:220
     if (sc.phase == MER_PHASE_HG && (sc.g >= 1 || sc.g <= -1))
         return fail(ctx, "The asymmetry parameter must lie in the interval (-1, 1)!");                              // hg.cpp:52-53
+    if (sc.integrator != MER_INTEGRATOR_VOLPATH && sc.integrator != MER_INTEGRATOR_PTRACER) return fail(ctx, "integrator: unknown integrator (volpath, ptracer)");
+    if (sc.integrator_reserved != 0) return fail(ctx, "integrator: integrator_reserved must be 0");
+    if (sc.integrator == MER_INTEGRATOR_PTRACER) return ptracer_scope(ctx, sc);
     return 0;
 }
 
@@ -612,7 +675,8 @@ static int sampling_strategy(mer_context *ctx, const mer_scene_desc &sc, Params 
 static int sensor(mer_context *ctx, const mer_scene_desc &sc, Params &P) {
     P.aspect = (float) sc.width / (float) sc.height;
     P.cot_half_fov = 1.0f / std::tan((sc.fov_x_deg / 2.0f) * (MER_PI / 180.0f));
-    for (int i = 0; i < 3; i++) P.par_dir[i] = P.sensor_pad[i] = 0.0f;
+    for (int i = 0; i < 3; i++) P.par_dir[i] = 0.0f;
+    P.sensor_pad[0] = 0.0f;
     P.lens_radius = P.lens_focus = 0.0f;
     if (sc.sensor < MER_SENSOR_PERSPECTIVE || sc.sensor > MER_SENSOR_TELECENTRIC) return fail(ctx, "sensor: unknown sensor kind (perspective, orthographic, thinlens, telecentric)");
     if (sc.sensor_reserved != 0) return fail(ctx, "sensor: sensor_reserved must be 0");

@@ -224,10 +224,16 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
     auto resolve = [&](const std::string &fn) { return (fn.empty() || fn[0] == '/' || baseDir.empty()) ? fn : baseDir + "/" + fn; };
     ObjRef out;
     if (tag == "integrator") {
-        if (type != "volpath") Log_EError("integrator \"" + type + "\": only 'volpath' runs on the GPU path");
+        if (type != "volpath" && type != "ptracer") Log_EError("integrator \"" + type + "\": only 'volpath' runs on the GPU path");
         auto o = std::make_shared<Integrator>();
         o->rrDepth = props.getInteger("rrDepth", 5); o->maxDepth = props.getInteger("maxDepth", -1);        // integrator.cpp:190-225
+        if (type == "ptracer") {                                         // src/integrators/ptracer/ptracer.cpp:86-105
+            o->kind = MER_INTEGRATOR_PTRACER;
+            (void) props.getInteger("granularity", 200000);              // work-unit size of the reference's scheduler: accepted and ignored
+            if (props.getBoolean("bruteForce", false)) Log_EError("integrator \"ptracer\": bruteForce = true (waiting for paths to hit the sensor) is not built on the GPU path");
+        } else {
         o->strictNormals = props.getBoolean("strictNormals", false); o->hideEmitters = props.getBoolean("hideEmitters", false);
+        }
         if (o->rrDepth <= 0) Log_EError("'rrDepth' must be set to a value greater than zero!");
         if (o->maxDepth <= 0 && o->maxDepth != -1) Log_EError("'maxDepth' must be set to -1 (infinite) or a value greater than zero!");
         out = o;
@@ -554,6 +560,22 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
             if (!(std::fabs(det) > 0)) Log_EError("spot emitter: 'toWorld' is singular");
             for (int i = 0; i < 3; i++) if (!(o->radiance.c[i] >= 0)) Log_EError("spot emitter: intensity must be non-negative");
             o->position = Vec3{M[3], M[7], M[11]};
+        } else if (type == "collimated") {                               // src/emitters/collimated.cpp:58-66
+            o->kind = Emitter::ECollimated;
+            props.getTransform("toWorld", o->toWorld);
+            o->radiance = props.getSpectrum("power", Spectrum{{1, 1, 1}});
+            const float *M = o->toWorld;
+            for (int i = 0; i < 12; i++) if (!std::isfinite(M[i])) Log_EError("collimated emitter: 'toWorld' must be finite");
+            for (int r = 0; r < 3; r++)                                   // Transform::hasScale (transform.cpp): M M^T = 1; within 1e-4, as mer_render checks it
+                for (int c = 0; c < 3; c++) {
+                    const double d = (double) M[4 * r] * M[4 * c] + (double) M[4 * r + 1] * M[4 * c + 1] + (double) M[4 * r + 2] * M[4 * c + 2] - (r == c ? 1.0 : 0.0);
+                    if (!(std::fabs(d) <= 1e-4)) Log_EError("Scale factors in the emitter-to-world transformation are not allowed!");
+                }
+            const double det = (double) M[0] * ((double) M[5] * M[10] - (double) M[6] * M[9]) - (double) M[1] * ((double) M[4] * M[10] - (double) M[6] * M[8]) +
+                               (double) M[2] * ((double) M[4] * M[9] - (double) M[5] * M[8]);
+            if (!(det > 0)) Log_EError("Scale factors in the emitter-to-world transformation are not allowed!");
+            for (int i = 0; i < 3; i++) if (!(o->radiance.c[i] >= 0) || !std::isfinite(o->radiance.c[i])) Log_EError("collimated emitter: power must be finite and non-negative");
+            o->position = Vec3{M[3], M[7], M[11]};
         } else if (type == "envmap") {                                   // src/emitters/envmap.cpp:103-187
             o->kind = Emitter::EEnvmap;
             const std::string fn = resolve(props.getString("filename"));
@@ -574,7 +596,7 @@ ObjRef createObject(const std::string &tag, const Properties &props, const std::
                                (double) M[2] * ((double) M[4] * M[9] - (double) M[5] * M[8]);
             if (!(det > 0)) Log_EError("envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)");
             o->image = readEnvmapImage(fn, o->imageW, o->imageH);
-        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, envmap, point, spot, area)");
+        } else Log_EError("emitter \"" + type + "\" is not supported on the GPU path (constant, envmap, point, spot, area, collimated)");
         o->samplingWeight = props.getFloat("samplingWeight", 1.0f);     // src/librender/emitter.cpp:103
         if (!(o->samplingWeight > 0) || !std::isfinite(o->samplingWeight)) Log_EError("emitter \"" + type + "\": samplingWeight must be positive");
         out = o;
@@ -844,6 +866,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d, const mer_grid_d
     for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) d.cam_to_world[r * 4 + c] = se.toWorld[r * 4 + c];
     d.rfilter = fi.rfilter->kind; d.rfilter_param = fi.rfilter->param;
     d.max_depth = maxDepth; d.rr_depth = rrDepth; d.hide_emitters = hideEmitters;
+    d.integrator = kind; d.integrator_reserved = 0;
     const Shape *shape = NULL;
     for (auto &s : scene.shapes) if (s->interior) { if (shape) Log_EError("Only one shape with an interior medium is supported on the GPU path"); shape = s.get(); }
     if (!shape) Log_EError("No shape with an 'interior' medium was found");
@@ -895,7 +918,7 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d, const mer_grid_d
     // point emitters and the area emitters of `rectangle` / `disk` / `sphere` shapes, in scene order (shapes first).  At most one point and one
     // rectangle, nothing else: the single-emitter fields of the scene desc; otherwise the emitter list (scene.emitterList), each entry with its
     // samplingWeight.  A disk or sphere is always a list entry (the single-emitter fields describe a rectangle)
-    int nconst = 0, npoint = 0, narea = 0, nspot = 0, nenv = 0, nround = 0;
+    int nconst = 0, npoint = 0, narea = 0, nspot = 0, nenv = 0, nround = 0, nbeam = 0;
     std::vector<mer_emitter> &list = scene.emitterList;
     list.clear();
     for (int i = 0; i < 3; i++) { d.env_radiance[i] = 0; d.point_intensity[i] = 0; d.point_position[i] = 0; d.emission[i] = m.emission.c[i]; d.area_radiance[i] = 0; }
@@ -925,6 +948,13 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d, const mer_grid_d
             for (int i = 0; i < 3; i++) { q.intensity[i] = e->radiance.c[i]; q.position[i] = e->toWorld[4 * i + 3]; }
             q.cutoff_angle_deg = e->cutoffAngle; q.beam_width_deg = e->beamWidth;
             list.push_back(q); ++nspot;
+        } else if (e->kind == Emitter::ECollimated) {                    // always a list entry; light tracing only
+            if (kind != MER_INTEGRATOR_PTRACER)
+                Log_EError("emitter \"collimated\" is a delta in position and direction: no camera path of 'volpath' can sample it (it would render black); use the 'ptracer' integrator");
+            mer_emitter q{}; q.type = MER_EMITTER_COLLIMATED; q.sampling_weight = e->samplingWeight;
+            for (int i = 0; i < 12; i++) q.to_world[i] = e->toWorld[i];
+            for (int i = 0; i < 3; i++) { q.intensity[i] = e->radiance.c[i]; q.position[i] = e->toWorld[4 * i + 3]; }
+            list.push_back(q); ++nbeam;
         } else if (e->kind == Emitter::EEnvmap) {                        // always a list entry; render() uploads the image and sets the handle
             if (nconst + nenv > 0) Log_EError("The scene may only contain one environment emitter");       // src/librender/scene.cpp:512
             mer_emitter q{}; q.type = MER_EMITTER_ENVMAP; q.sampling_weight = e->samplingWeight;
@@ -938,7 +968,17 @@ void Integrator::flatten(const Scene &scene, mer_scene_desc &d, const mer_grid_d
         }
     }
     if ((int) list.size() > MER_MAX_EMITTERS) Log_EError("At most " + std::to_string(MER_MAX_EMITTERS) + " point, spot and area emitters are supported on the GPU path");
-    if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0 && nround == 0) {
+    if (kind == MER_INTEGRATOR_PTRACER) {      // the light tracer's scope (mer_render refuses the same): a perspective sensor, list entries of kind point, spot, collimated
+        if (d.sensor != MER_SENSOR_PERSPECTIVE) Log_EError("integrator \"ptracer\": light paths are connected to the perspective sensor only");
+        if (nconst || nenv) Log_EError("integrator \"ptracer\": constant and envmap emitters are not built for light tracing");
+        if (narea) Log_EError("integrator \"ptracer\": area emitters are not built for light tracing");
+        if (list.empty()) Log_EError("integrator \"ptracer\": the scene has no emitter (point, spot or collimated)");
+        if (d.boundary == MER_BOUNDARY_SDF || d.boundary_bsdf != MER_BSDF_NULL) Log_EError("integrator \"ptracer\": the medium shape must be a cube or sphere with the null BSDF");
+        if (d.emission[0] != 0 || d.emission[1] != 0 || d.emission[2] != 0) Log_EError("integrator \"ptracer\": medium emission is not built for light tracing");
+        if (d.sigma_mode == MER_SIGMA_GRID && d.method == MER_METHOD_SIMPSON) Log_EError("integrator \"ptracer\": method = simpson is not built for light tracing");
+        d.n_emitters = (int32_t) list.size(); d.emitters = list.data();
+    } else
+    if (npoint <= 1 && narea <= 1 && nspot == 0 && nenv == 0 && nround == 0 && nbeam == 0) {
         for (const mer_emitter &e : list) {
             if (e.type == MER_EMITTER_AREA) { for (int i = 0; i < 12; i++) d.area_to_world[i] = e.to_world[i]; for (int i = 0; i < 3; i++) d.area_radiance[i] = e.radiance[i]; }
             else for (int i = 0; i < 3; i++) { d.point_position[i] = e.position[i]; d.point_intensity[i] = e.intensity[i]; }
@@ -1032,7 +1072,7 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
     if (m.density) d.density = upload(*m.density, MER_LAYOUT_DENSE);
     if (m.albedo && !m.albedo->isConstant()) d.albedo_grid = upload(*m.albedo, MER_LAYOUT_DENSE);
     if (m.rif && !m.rif->isAcoustic()) {
-        d.rif = upload(*m.rif, m.rif->isSpline() ? MER_LAYOUT_DENSE : layout);
+        d.rif = upload(*m.rif, (m.rif->isSpline() || kind == MER_INTEGRATOR_PTRACER) ? MER_LAYOUT_DENSE : layout);     // the light tracer reads the dense layout
         if (m.rif->isSpline() && mer_multi_volume_build_spline(mm, d.rif)) fail();
     }
     if (m.sdf) d.sdf = upload(*m.sdf, MER_LAYOUT_DENSE);

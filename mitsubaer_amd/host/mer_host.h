@@ -9,8 +9,8 @@
 //   Medium                homogeneous | heterogeneous | heterogeneousrefractive   include/mitsuba/render/medium.h:113-234
 //   Shape                 cube | sphere | obj (bounding box), `interior` medium, null BSDF   src/librender/shape.cpp:48-70,166-190
 //   Sensor / Film / ReconstructionFilter / Sampler      perspective | orthographic | thinlens | telecentric, hdrfilm, gaussian | box, independent | ldsampler
-//   Emitter               constant | point | area (on a rectangle shape)
-//   Integrator            volpath -> render() flattens the scene to mer_scene_desc and calls mer_render
+//   Emitter               constant | point | area (on a rectangle shape) | collimated (ptracer)
+//   Integrator            volpath | ptracer -> render() flattens the scene to mer_scene_desc and calls mer_render
 //   SceneHandler          scene-XML subset with $param substitution    src/librender/scenehandler.cpp, src/mitsuba/mitsuba.cpp:58,168-173
 //
 // Errors: like Log(EError) in the reference (src/libcore/logger.cpp:100-147) every failure throws std::runtime_error.
@@ -194,10 +194,10 @@ public:
 class Emitter : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "Emitter"; }
-    enum Kind { EConstant, EPoint, EArea, ESpot, EEnvmap } kind = EConstant;
-    Spectrum radiance{};                        // constant / area: radiance ; point / spot: intensity
+    enum Kind { EConstant, EPoint, EArea, ESpot, EEnvmap, ECollimated } kind = EConstant;
+    Spectrum radiance{};                        // constant / area: radiance ; point / spot: intensity ; collimated: power
     Vec3 position{0, 0, 0};                     // point (src/emitters/point.cpp:60-68)
-    float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // spot: its frame (src/emitters/spot.cpp:124-131)
+    float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // spot: its frame (src/emitters/spot.cpp:124-131); collimated: the beam's (collimated.cpp:115-124)
     float cutoffAngle = 20, beamWidth = 15;     // spot: degrees (spot.cpp:68-73)
     float samplingWeight = 1.0f;                // `samplingWeight` (src/librender/emitter.cpp:103): selection weight among the emitters of its kind
     std::vector<float> image; int imageW = 0, imageH = 0;      // envmap: the lat-long image as loaded, float [h][w][3] (src/emitters/envmap.cpp:116-160)
@@ -205,11 +205,12 @@ public:
 };
 
 class Scene;
-/// `volpath` executed on the GPU: Integrator::render() (include/mitsuba/render/integrator.h:74) owns its parallelism
+/// `volpath`, or `ptracer` (kind = MER_INTEGRATOR_PTRACER: light tracing, src/integrators/ptracer), executed on the GPU: Integrator::render() (include/mitsuba/render/integrator.h:74) owns its parallelism
 class Integrator : public ConfigurableObject {
 public:
     const char *getClassName() const override { return "Integrator"; }
     int maxDepth = -1, rrDepth = 5; bool hideEmitters = false, strictNormals = false;
+    int kind = MER_INTEGRATOR_VOLPATH;          ///< MER_INTEGRATOR_*
     /// flatten (validates like the reference's configure()) -- no GPU needed.  Several point or area emitters: desc.emitters points into
     /// scene.emitterList, which must outlive desc
     /// meshGrid: the grid of a signed-distance volume that render() will build from the `obj` medium shape (meshSdfGrid): the boundary then is

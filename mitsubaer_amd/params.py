@@ -25,6 +25,7 @@ METHOD_WOODCOCK, METHOD_SIMPSON = 0, 1
 BSDF_NULL, BSDF_HDIELECTRIC, BSDF_HROUGHDIELECTRIC = 0, 1, 2
 MICROFACET_BECKMANN, MICROFACET_GGX, MICROFACET_PHONG = 0, 1, 2
 SENSOR_PERSPECTIVE, SENSOR_ORTHOGRAPHIC, SENSOR_THINLENS, SENSOR_TELECENTRIC = 0, 1, 2, 3      # src/sensors/: the projective family
+INTEGRATOR_VOLPATH, INTEGRATOR_PTRACER = 0, 1          # path tracing from the sensor | light tracing (`ptracer`: paths start at an emitter)
 MODULATION_NONE, MODULATION_SINE, MODULATION_SQUARE, MODULATION_HAMILTONIAN, MODULATION_MSEQ, MODULATION_DEPTHSELECTIVE = 0, 1, 2, 3, 4, 5
 
 
@@ -78,6 +79,9 @@ class SceneParams:
         self.rfilter = FILTER_GAUSSIAN; self.rfilter_param = 0.5
         # integrator volpath (src/librender/integrator.cpp:190-225)
         self.max_depth = -1; self.rr_depth = 5; self.hide_emitters = False
+        # INTEGRATOR_PTRACER: light tracing (src/integrators/ptracer): every scattering vertex of a path started at an emitter is connected
+        # to the perspective sensor; emitters are list entries of kind point, spot or collimated (include/mer.h: mer_scene_desc.integrator)
+        self.integrator = INTEGRATOR_VOLPATH
         # shape: cube [-1,1]^3 (scenes/volumetric/bounds.obj), null BSDF
         self.boundary = BOUNDARY_AABB
         self.boundary_bsdf = BSDF_NULL                            # BSDF_HDIELECTRIC: smooth dielectric, eta = RIF at the hit point
@@ -145,6 +149,7 @@ EMITTER_SPOT = 3
 EMITTER_ENVMAP = 4
 EMITTER_AREA_DISK = 5
 EMITTER_AREA_SPHERE = 6
+EMITTER_COLLIMATED = 7
 AREA_TYPES = (EMITTER_AREA, EMITTER_AREA_DISK, EMITTER_AREA_SPHERE)      # one kind: one selection CDF in list order
 MAX_EMITTERS = 32
 
@@ -273,6 +278,28 @@ def envmap_emitter(image, to_world=None, scale=1.0, sampling_weight=1.0):
     if err:
         raise ValueError(err)
     return {"type": EMITTER_ENVMAP, "image": a, "to_world": to_world, "scale": float(scale), "sampling_weight": float(sampling_weight)}
+
+
+def collimated_error(to_world):
+    """why mer_render refuses a collimated emitter with this frame (None: accepted); the scale message is the reference's"""
+    import numpy as np
+    m = np.asarray(to_world if to_world is not None else np.eye(4), np.float64)
+    if m.shape not in ((3, 4), (4, 4)) or not np.all(np.isfinite(m)):
+        return "collimated emitter: 'toWorld' must be finite"
+    R = m[:3, :3].astype(np.float32).astype(np.float64)
+    if np.max(np.abs(R @ R.T - np.eye(3))) > 1e-4 or not np.linalg.det(R) > 0:
+        return "Scale factors in the emitter-to-world transformation are not allowed!"
+    return None
+
+
+def collimated_emitter(to_world, power, sampling_weight=1.0):
+    """an entry of SceneParams.emitters: emitter `collimated` (src/emitters/collimated.cpp), a beam that is a delta in position and
+    direction: it starts at to_world's origin and runs along to_world's z axis (a 3x4 / 4x4 frame without scale: look_at gives one) and
+    carries `power`.  Only light tracing (integrator = INTEGRATOR_PTRACER) can render it.  ValueError for what mer_render refuses."""
+    err = collimated_error(to_world)
+    if err:
+        raise ValueError(err)
+    return {"type": EMITTER_COLLIMATED, "to_world": to_world, "power": [float(v) for v in power], "sampling_weight": float(sampling_weight)}
 
 
 def spot_position(e):

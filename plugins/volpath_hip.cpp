@@ -165,6 +165,7 @@ public:
         else Log(EError, "volpath_hip: the sensor must be 'perspective', 'orthographic', 'thinlens' or 'telecentric' (got %s)", sensorClass.c_str());
         const ProjectiveCamera *cam = static_cast<const ProjectiveCamera *>(sensor);
         d.sensor_reserved = 0; d.aperture_radius = 0; d.focus_distance = 0;
+        d.integrator = MER_INTEGRATOR_VOLPATH; d.integrator_reserved = 0;      // this plugin is the volpath integrator (light tracing: the `ptracer` of the host front end)
         if (d.sensor == MER_SENSOR_THINLENS || d.sensor == MER_SENSOR_TELECENTRIC) {
             d.aperture_radius = (float) sensor->getProperties().getFloat("apertureRadius", 0.0f);
             if (d.sensor == MER_SENSOR_THINLENS && d.aperture_radius == 0) d.aperture_radius = (float) Epsilon;
