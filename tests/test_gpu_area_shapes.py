@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from mitsubaer_amd import params as P, capi
 from tests import area_shapes64 as A, scenes, volpath64_shapes as vs
+from tests.combined_scenes import mixed_params as _mixed_params
 
 pytestmark = pytest.mark.gpu
 
@@ -238,17 +239,6 @@ def test_dome_equals_the_constant_environment(ctx):
     se = np.sqrt(a.var() / a.size + b.var() / b.size)
     print("dome %.6f, environment %.6f, 4 sigma of the difference %.6f" % (a.mean(), b.mean(), 4 * se))
     assert a.mean() > 0.5 and abs(a.mean() - b.mean()) < 4 * se, (a.mean(), b.mean(), se)
-
-
-def _mixed_params(**kw):
-    c, r, l, ws = vs.MIXED_SPHERE
-    ems = [P.sphere_emitter(c, r, [l] * 3, ws), P.disk_emitter(vs.MIXED_DISK[0], [vs.MIXED_DISK[1]] * 3, vs.MIXED_DISK[2]),
-           P.area_emitter(vs.MIXED_RECT[0], [vs.MIXED_RECT[1]] * 3, vs.MIXED_RECT[2])]
-    m = vs.MIXED
-    base = dict(w=m["width"], h=m["height"], sigma_s=[m["sigma_s"]] * 3, sigma_a=[m["sigma_a"]] * 3, phase=P.PHASE_HG, g=m["g"], env_radiance=[m["env"]] * 3,
-                fov_x_deg=m["fov_x_deg"], cam_to_world=P.look_at(*vs.MIXED_CAM), rfilter=P.FILTER_BOX, rfilter_param=0.5, max_depth=-1, emitters=ems)
-    base.update(kw)
-    return scenes.homogeneous_scene(**base)
 
 
 def test_render_matches_the_float64_volpath(ctx):
