@@ -261,6 +261,11 @@ typedef struct {
     int32_t tile_rank, tile_count;
 } mer_shard;
 
+/* a fluence grid (mer_fluence_create): res[a] cells on axis a over the box bmin ... bmax; cell (i, j, k) holds the points whose
+   floor((p - bmin) / (bmax - bmin) * res) is (i, j, k) per axis: the cells are half-open, a point on bmax lies outside */
+typedef int32_t mer_fluence;                                  /* handle, > 0 */
+typedef struct { int32_t res[3]; float bmin[3], bmax[3]; } mer_fluence_desc;
+
 enum {
     MER_C_PATHS = 0, MER_C_STEPS, MER_C_RIF_EVALS, MER_C_TENTATIVE, MER_C_REAL,
     MER_C_SEGMENTS, MER_C_NEE, MER_C_LOOP_ITERS, MER_C_ACTIVE_LANES,
@@ -390,6 +395,41 @@ int  mer_last_kernel_ms(mer_context *ctx, float *ms);
 int  mer_last_render_stats(mer_context *ctx, int32_t *passes, float *march_ms, float *event_ms);
 int  mer_counters_read(mer_context *ctx, uint64_t out[MER_C_COUNT]);    /* StatsCounter analogue */
 int  mer_counters_reset(mer_context *ctx);
+
+/* ---- the fluence inside the medium as a voxel grid, recorded from light paths: replaces the `fluencemeter` sensor driven by `ptracer`
+        (src/sensors/fluencemeter.cpp:40-41, "the average radiance passing through a specified position"), one grid of probes instead of one
+        probe per render.
+        The estimator.  A light path is exactly the one mer_render walks for the same scene, shard and seed under integrator = ptracer: the
+        same work id and (pixel, sample) sampler key, emitter selection and emitted ray, entry into the shape (one depth paid for the null
+        boundary), free flights, phase-function samples and roulette, and the same bounds on the scatterings and march units of a path.
+        There is no sensor connection: the sensor fields only enumerate the paths, width x height x samples of them, and the film fields
+        (decomposition, modulation, filter) are ignored.  max_depth means what it means in the light tracer's loop: with an emitter outside
+        the shape, max_depth = 2 keeps the first collisions only (the ballistic fluence).
+        Every real collision the loop reaches is a collision-estimator sample of the fluence.  With T the path's throughput BEFORE it is
+        multiplied by the albedo, the deposit is  w = T * power * (transmittance / pdfSuccess)  per channel -- 1 / sigma_t for delta
+        tracking in a gridded sigma_t, tau_c / pdf for the homogeneous strategies -- into the cell that holds the collision point.  No
+        refRatioSq is applied: particles carry power, and the light tracer applies none either.  A point outside the box deposits nothing;
+        its w is added to the `dropped` total.
+        The grid holds raw float64 sums, double[nz][ny][nx][3], added with float64 atomics.  fluence = sums / (paths * cell volume), per
+        unit of whatever the emitter's intensity / power is in; sigma_a * fluence is the absorbed power density.  Raw sums of disjoint
+        shards add (several GPUs: one grid per context, added by the caller).
+        totals[8], kept beside the grid: [0] paths started; [1..3] escaped weight, T * power when the path leaves the shape or the emitted
+        ray misses it; [4..6] dropped deposit weight; [7] paths ended by a budget, a failed start gate (B-spline field) or no forward
+        progress.  sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power in expectation when every free flight is drawn from the
+        medium (medium_sampling_weight = 1, or a gridded sigma_t) and max_depth = -1; with a smaller medium_sampling_weight the escaped
+        weight carries no 1 / pdfFailure and overstates the power that leaves.
+        Scope: exactly the light tracer's -- the scene must pass mer_render's checks for integrator = MER_INTEGRATOR_PTRACER unchanged (point,
+        spot and collimated list entries; cube or sphere with the null boundary; homogeneous or gridded sigma_t; constant or gridded albedo;
+        rif_mode CONST, dense TRILINEAR, BSPLINE3 or ACOUSTIC; both steppers), and any other integrator is refused, before any launch.
+        mer_fluence_create: res 1 ... 1024 per axis, at most 2^27 cells, bmin < bmax per axis, all finite; the grid starts zeroed.
+        mer_render_fluence ACCUMULATES into the grid (mer_fluence_clear zeroes it and the totals), launches on the context stream in the light
+        tracer's chunks and returns synchronised; mer_counters_read afterwards reports the walk as it does after mer_render.
+        mer_fluence_read: sums may be NULL (totals only).  mer_context_destroy frees the grids still alive. ---- */
+int  mer_fluence_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out);
+int  mer_fluence_clear(mer_context *ctx, mer_fluence f);
+int  mer_fluence_destroy(mer_context *ctx, mer_fluence f);
+int  mer_render_fluence(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_fluence f);
+int  mer_fluence_read(mer_context *ctx, mer_fluence f, double *sums /* [nz][ny][nx][3] or NULL */, double totals[8]);
 
 /* ---- leaf entry points for parity tests (host pointers, batched SoA) ------------------------------ */
 /* GridDataSource::lookupFloat (gridvolume.cpp:337-388); out_idx[4*i..] = x1,y1,z1,linear index or -1 */

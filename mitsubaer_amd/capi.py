@@ -27,6 +27,7 @@ SYMBOLS = [
     "mer_correlation", "mer_render_paths", "mer_rng_floats", "mer_synth_field_dev", "mer_device_free",
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
+    "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -358,6 +359,38 @@ class MerError(RuntimeError):
     """Mirrors the reference's Log(EError) -> std::runtime_error (src/libcore/logger.cpp:100-147)."""
 
 
+class FluenceDesc(C.Structure):
+    """mer_fluence_desc: res cells per axis (x, y, z) over the box bmin ... bmax"""
+    _fields_ = [("res", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3)]
+
+
+FLUENCE_TOTALS = ("paths", "escaped", "dropped", "ended")        # mer_fluence_read's totals: [0], [1..3], [4..6], [7]
+
+
+def fluence_desc(res, bmin, bmax):
+    d = FluenceDesc()
+    d.res[:] = [int(v) for v in res]
+    d.bmin[:] = [float(v) for v in bmin]
+    d.bmax[:] = [float(v) for v in bmax]
+    return d
+
+
+def validate_fluence(desc):
+    """The refusals of mer_fluence_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_fluence_create: "
+    cells = 1
+    for a in range(3):
+        if desc.res[a] < 1 or desc.res[a] > 1024:
+            raise MerError(at + "res must lie in 1 ... 1024 on every axis")
+        if not (np.isfinite(desc.bmin[a]) and np.isfinite(desc.bmax[a])):
+            raise MerError(at + "bmin / bmax must be finite")
+        if not desc.bmin[a] < desc.bmax[a]:
+            raise MerError(at + "bmin must be below bmax on every axis")
+        cells *= desc.res[a]
+    if cells > 1 << 27:
+        raise MerError(at + "more than 2^27 cells")
+
+
 def lib(path=None):
     """The C-ABI library (ctypes).  path = None: libmer.so; Context(check=True) loads libmer_check.so beside it."""
     path = path or LIB_PATH
@@ -429,6 +462,7 @@ class Context:
             if rc != 0:
                 raise MerError(self.lib.mer_last_error(None).decode())
         self.device_id = device_id
+        self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -688,6 +722,65 @@ class Context:
             return self.film_download(f, scene.width, scene.height, ch)
         finally:
             self.film_free(f)
+
+    # ---- the fluence grid recorded from light paths (mer_render_fluence) ------------------------
+    def fluence_create(self, res, bmin, bmax):
+        """-> handle of a zeroed grid of res = (nx, ny, nz) cells over the box bmin ... bmax"""
+        d = fluence_desc(res, bmin, bmax)
+        validate_fluence(d)
+        h = C.c_int32()
+        self._check(self.lib.mer_fluence_create(self.h, C.byref(d), C.byref(h)))
+        self._fluence_res[h.value] = tuple(d.res)
+        return h.value
+
+    def fluence_clear(self, handle):
+        self._check(self.lib.mer_fluence_clear(self.h, C.c_int32(handle)))
+
+    def fluence_destroy(self, handle):
+        self._check(self.lib.mer_fluence_destroy(self.h, C.c_int32(handle)))
+        self._fluence_res.pop(handle, None)
+
+    def render_fluence(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
+        """accumulates the light paths of the shard into the grid; returns synchronised"""
+        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
+        self._check(self.lib.mer_render_fluence(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+
+    def fluence_read(self, handle, sums=True):
+        """-> (raw sums float64 [nz][ny][nx][3], or None with sums = False; totals float64 [8])"""
+        totals = np.zeros(8, np.float64)
+        out = None
+        if sums:
+            res = self._fluence_res.get(handle)
+            if res is None:
+                raise MerError("mer_fluence_read: unknown fluence handle")
+            out = np.zeros((res[2], res[1], res[0], 3), np.float64)
+        self._check(self.lib.mer_fluence_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
+        return out, totals
+
+    def fluence(self, scene, res, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
+        """One fluence map of the scene (integrator = ptracer): (phi float64 [nz][ny][nx][3], info).  phi = sums / (paths x cell volume), per
+        unit of the emitters' intensity / power; the box defaults to the bounding box of the medium shape.  info: the totals by name
+        (paths, escaped [3], dropped [3], ended), the raw sums, the box and the cell volume."""
+        if bmin is None or bmax is None:
+            if scene.boundary == P.BOUNDARY_SPHERE:
+                c, r = np.array(scene.sph_center[:], np.float64), float(scene.sph_radius)
+                lo, hi = c - r, c + r
+            else:
+                lo, hi = np.array(scene.bmin[:], np.float64), np.array(scene.bmax[:], np.float64)
+            bmin = lo if bmin is None else bmin
+            bmax = hi if bmax is None else bmax
+        h = self.fluence_create(res, bmin, bmax)
+        try:
+            self.render_fluence(scene, h, spp_begin, spp_count, seed)
+            sums, t = self.fluence_read(h)
+        finally:
+            self.fluence_destroy(h)
+        d = fluence_desc(res, bmin, bmax)
+        volume = float(np.prod([(np.float64(d.bmax[a]) - np.float64(d.bmin[a])) / d.res[a] for a in range(3)]))
+        info = {"paths": t[0], "escaped": t[1:4].copy(), "dropped": t[4:7].copy(), "ended": t[7], "sums": sums,
+                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64), "cell_volume": volume}
+        phi = sums / (t[0] * volume) if t[0] > 0 else np.zeros_like(sums)
+        return phi, info
 
     def synchronize(self):
         self._check(self.lib.mer_synchronize(self.h))

@@ -33,6 +33,13 @@ struct EnvMap {
     size_t off_cols = 0, off_rows = 0, off_weights = 0;
 };
 
+// a fluence grid (mer_fluence_create): one device buffer -- the sums double[nz][ny][nx][3], then the 8 totals.  Its handle shares the volumes' numbering.
+struct Fluence {
+    mer_fluence_desc desc;
+    double *dev = nullptr;
+    uint64_t n_cells = 0;
+};
+
 #define MER_MAX_PIPES 4
 struct Pipe {
     hipStream_t stream = nullptr, own_stream = nullptr;      // pipeline 0 runs on the context stream
@@ -79,6 +86,7 @@ struct mer_context {
     std::string error;
     std::map<int, mer::Volume> volumes;
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
+    std::map<int, mer::Fluence> fluences;        // mer_fluence_create (handles from next_handle)
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
@@ -148,6 +156,8 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
 
 // mer_render_ptracer.hip: integrator = MER_INTEGRATOR_PTRACER -- one lane per light path, launched a fixed number of paths at a time
 int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, uint64_t n_film);
+
+// mer_render_fluence.hip: the fluence grid recorded from the same light paths (mer_render_fluence and the mer_fluence_* entry points)
 
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
 // validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.

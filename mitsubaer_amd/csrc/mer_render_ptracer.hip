@@ -64,6 +64,23 @@ int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shar
     return 0;
 }
 
+// the kernels of the two leaf entry points (here, not in mer_ptracer.hpp: a second translation unit includes that header)
+__global__ void sensor_direct_kernel(const Params P, const float *ref, int64_t n, float *out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float u, v, dist; f3 d;
+    const float val = sensor_direct(P, f3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), u, v, d, dist);
+    float *o = out + 8 * i;
+    o[0] = val; o[1] = u; o[2] = v; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = dist; o[7] = 0.0f;
+}
+__global__ void sensor_position_kernel(const Params P, const float *dirs, int64_t n, float *uv, int32_t *ok) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float u, v;
+    const bool good = sensor_position(P, f3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]), u, v);
+    uv[2 * i] = u; uv[2 * i + 1] = v; ok[i] = good ? 1 : 0;
+}
+
 // the pinhole's sampleDirect / getSamplePosition for the leaf entry points: the scene's sensor fields only
 static int sensor_params(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
     if (!scene) return fail(ctx, std::string(who) + ": no scene");

@@ -1041,23 +1041,7 @@ void Integrator::meshSdfGrid(const Scene &scene, int n, mer_grid_desc &g) const 
     }
 }
 
-std::vector<float> Integrator::render(const Scene &scene, int device, int spp, unsigned long long seed, int layout) const {
-    return render(scene, std::vector<int>(1, device), MER_SHARD_SAMPLES, spp, seed, layout);
-}
-
-// One or several GPUs: mer_multi owns a context per device, replicates the volumes and reduces the films (RCCL between distinct devices).
-// The reference's counterpart: `mitsuba -p <workers>` local workers merged by film->put (src/mitsuba/mitsuba.cpp:281,
-// src/librender/renderproc.cpp:142-149).
-std::vector<float> Integrator::render(const Scene &scene, const std::vector<int> &devices, int shardMode, int spp, unsigned long long seed, int layout, int meshSdf, bool ordered) const {
-    mer_scene_desc d; mer_grid_desc meshGrid;
-    if (meshSdf >= 0) { meshSdfGrid(scene, meshSdf, meshGrid); flatten(scene, d, &meshGrid); }
-    else flatten(scene, d);
-    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
-    if (devices.empty()) Log_EError("Integrator::render: no device given");
-    mer_multi *mm = NULL;
-    std::vector<int32_t> ids(devices.begin(), devices.end());
-    if (mer_multi_create(ids.data(), (int32_t) ids.size(), &mm)) Log_EError(mer_multi_last_error(NULL));
-    int32_t channels = 5;
+void Integrator::uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const {
     auto fail = [&](void) { std::string msg = mer_multi_last_error(mm); mer_multi_destroy(mm); Log_EError(msg); };
     const Medium &m = *([&]() -> const Shape * { for (auto &s : scene.shapes) if (s->interior) return s.get(); return (const Shape *) NULL; }())->interior;
     auto upload = [&](const VolumeDataSource &v, int lay) -> mer_volume {
@@ -1076,6 +1060,27 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
         if (m.rif->isSpline() && mer_multi_volume_build_spline(mm, d.rif)) fail();
     }
     if (m.sdf) d.sdf = upload(*m.sdf, MER_LAYOUT_DENSE);
+}
+
+std::vector<float> Integrator::render(const Scene &scene, int device, int spp, unsigned long long seed, int layout) const {
+    return render(scene, std::vector<int>(1, device), MER_SHARD_SAMPLES, spp, seed, layout);
+}
+
+// One or several GPUs: mer_multi owns a context per device, replicates the volumes and reduces the films (RCCL between distinct devices).
+// The reference's counterpart: `mitsuba -p <workers>` local workers merged by film->put (src/mitsuba/mitsuba.cpp:281,
+// src/librender/renderproc.cpp:142-149).
+std::vector<float> Integrator::render(const Scene &scene, const std::vector<int> &devices, int shardMode, int spp, unsigned long long seed, int layout, int meshSdf, bool ordered) const {
+    mer_scene_desc d; mer_grid_desc meshGrid;
+    if (meshSdf >= 0) { meshSdfGrid(scene, meshSdf, meshGrid); flatten(scene, d, &meshGrid); }
+    else flatten(scene, d);
+    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    if (devices.empty()) Log_EError("Integrator::render: no device given");
+    mer_multi *mm = NULL;
+    std::vector<int32_t> ids(devices.begin(), devices.end());
+    if (mer_multi_create(ids.data(), (int32_t) ids.size(), &mm)) Log_EError(mer_multi_last_error(NULL));
+    int32_t channels = 5;
+    auto fail = [&](void) { std::string msg = mer_multi_last_error(mm); mer_multi_destroy(mm); Log_EError(msg); };
+    uploadMedia(scene, mm, d, layout);
     if (meshSdf >= 0) {        // built once on the first device, downloaded, and replicated like a grid read from a file (one path for one GPU and for several:
                                // a single-GPU render pays one download and one upload of the grid for it)
         const Shape *shape = NULL; for (auto &s : scene.shapes) if (s->interior) shape = s.get();
@@ -1114,6 +1119,57 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
     return film;
 }
 
+// The fluence grid of a `ptracer` scene: one context (a mer_multi of one device, for the uploads it shares with render()), one grid over the
+// medium shape's bounding box, width x height x spp light paths.
+Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const {
+    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    mer_scene_desc d;
+    flatten(scene, d);
+    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    Fluence out;
+    mer_fluence_desc fd;
+    for (int a = 0; a < 3; a++) {
+        fd.res[a] = out.res[a] = res[a];
+        fd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
+        fd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
+    }
+    mer_multi *mm = NULL;
+    const int32_t id = device;
+    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
+    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
+    mer_context *ctx = mer_multi_context(mm, 0);
+    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
+    mer_fluence f = 0;
+    if (mer_fluence_create(ctx, &fd, &f)) fail();
+    const mer_shard whole = {0, spp, 1, 0, 1};
+    if (mer_render_fluence(ctx, &d, &whole, seed, f)) fail();
+    out.sums.resize((size_t) res[0] * res[1] * res[2] * 3);
+    if (mer_fluence_read(ctx, f, out.sums.data(), out.totals)) fail();
+    mer_multi_destroy(mm);                     // frees the grid with its context
+    return out;
+}
+std::vector<float> Integrator::Fluence::phi() const {
+    double volume = 1.0;
+    for (int a = 0; a < 3; a++) volume *= ((double) bmax[a] - (double) bmin[a]) / res[a];
+    const double inv = totals[0] > 0 ? 1.0 / (totals[0] * volume) : 0.0;
+    std::vector<float> v(sums.size());
+    for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
+    return v;
+}
+bool parseFluenceRes(const std::string &value, int res[3]) {
+    size_t p = 0;
+    for (int a = 0; a < 3; a++) {
+        size_t e = a < 2 ? value.find(',', p) : value.size();
+        if (e == std::string::npos || e == p) return false;
+        const std::string tok = value.substr(p, e - p);
+        if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
+        res[a] = std::atoi(tok.c_str());
+        if (res[a] < 1 || res[a] > 1024) return false;
+        p = e + 1;
+    }
+    return (long long) res[0] * res[1] * res[2] <= (1LL << 27);
+}
+
 std::vector<float> develop(const std::vector<float> &film, int w, int h, int frames) {
     const int ch = frames * 3 + 2;
     std::vector<float> rgb((size_t) frames * w * h * 3);
@@ -1135,6 +1191,14 @@ void writeNpy(const std::string &path, const float *data, int h, int w, int c) {
     const unsigned short len = (unsigned short) hdr.size();
     f.write("\x93NUMPY\x01\x00", 8); f.write((const char *) &len, 2); f.write(hdr.data(), (std::streamsize) hdr.size());
     f.write((const char *) data, (std::streamsize) ((size_t) h * w * c * 4));
+}
+void writeVol(const std::string &path, const float *data, int nx, int ny, int nz, int channels, const float aabbMin[3], const float aabbMax[3]) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) Log_EError("Unable to write \"" + path + "\"");
+    const int32_t head[5] = {1 /* float32 */, nx, ny, nz, channels};
+    f.write("VOL\x03", 4); f.write((const char *) head, 20);
+    f.write((const char *) aabbMin, 12); f.write((const char *) aabbMax, 12);
+    f.write((const char *) data, (std::streamsize) ((size_t) nx * ny * nz * channels * 4));
 }
 void writePfm(const std::string &path, const float *rgb, int h, int w) {
     std::ofstream f(path, std::ios::binary);

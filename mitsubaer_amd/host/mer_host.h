@@ -228,6 +228,20 @@ public:
     /// device, download it and replicate it like any other volume.  ordered: one render per sample index, the films added on the host in index
     /// order (`mer_render --ordered`): the sum no longer depends on the order of the film's float atomics across samples
     std::vector<float> render(const Scene &scene, const std::vector<int> &devices, int shardMode, int spp, unsigned long long seed, int layout, int meshSdf = -1, bool ordered = false) const;
+    /// the fluence inside the medium as a grid of res[0] x res[1] x res[2] cells over the medium shape's bounding box, recorded from the light paths
+    /// of a `ptracer` scene (mer_render_fluence: the reference's `fluencemeter` + `ptracer`, a grid of probes): width x height x spp paths on
+    /// one device.  Any other integrator is refused
+    struct Fluence {
+        int res[3]; float bmin[3], bmax[3];
+        std::vector<double> sums;               ///< raw sums [nz][ny][nx][3]
+        double totals[8];                       ///< paths, escaped x 3, dropped x 3, ended (mer_fluence_read)
+        /// sums / (paths x cell volume), float32 [nz][ny][nx][3]
+        std::vector<float> phi() const;
+    };
+    Fluence renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const;
+private:
+    /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
+    void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;
 };
 
 class Scene : public ConfigurableObject {
@@ -252,6 +266,10 @@ std::shared_ptr<Scene> loadSceneFromString(const std::string &xml, const std::ma
 std::vector<float> develop(const std::vector<float> &film, int w, int h, int frames = 1);
 void writeNpy(const std::string &path, const float *data, int h, int w, int c);
 void writePfm(const std::string &path, const float *rgb, int h, int w);
+/// VOL version 3 (src/volume/gridvolume.cpp:108-198), float32: data [nz][ny][nx][channels], the box the first and last nodes lie on
+void writeVol(const std::string &path, const float *data, int nx, int ny, int nz, int channels, const float aabbMin[3], const float aabbMax[3]);
+/// `mer_render --fluence=NX,NY,NZ`: three counts between 1 and 1024, at most 2^27 cells; false for anything else
+bool parseFluenceRes(const std::string &value, int res[3]);
 /// OpenEXR 2 scan-line file, uncompressed, three float32 channels B, G, R (what HDRFilm::develop writes through OpenEXR,
 /// src/films/hdrfilm.cpp:527; no OpenEXR library is needed for this subset)
 void writeExr(const std::string &path, const float *rgb, int h, int w);

@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cstdio>
@@ -11,6 +11,7 @@ int main(int argc, char **argv) {
     int spp = 0, device = 0, layout = MER_LAYOUT_AUTO; unsigned long long seed = 0; bool raw = false;
     bool ordered = false;          // --ordered: one render per sample index, films added in index order
     int meshSdf = -1;              // --mesh-sdf[=N]: -1 off, 0 = the rif volume's grid, N = nodes on the longest axis of the mesh's box
+    int fluenceRes[3] = {0, 0, 0}; bool fluence = false, multi = false;   // --fluence=NX,NY,NZ: the fluence grid of a ptracer scene instead of its film
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -20,8 +21,8 @@ int main(int argc, char **argv) {
         else if (a == "-s" && i + 1 < argc) spp = std::atoi(argv[++i]);
         else if (a == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], NULL, 10);
         else if (a == "--device" && i + 1 < argc) device = std::atoi(argv[++i]);
-        else if (a == "--gpus" && i + 1 < argc) { const int n = std::atoi(argv[++i]); if (n < 1) { std::fprintf(stderr, "--gpus expects a positive count\n"); return 2; } devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
-        else if (a == "--devices" && i + 1 < argc) { devices.clear(); const std::string l = argv[++i]; size_t p = 0; while (p <= l.size()) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); if (e > p) devices.push_back(std::atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
+        else if (a == "--gpus" && i + 1 < argc) { multi = true; const int n = std::atoi(argv[++i]); if (n < 1) { std::fprintf(stderr, "--gpus expects a positive count\n"); return 2; } devices.clear(); for (int k = 0; k < n; k++) devices.push_back(k); }
+        else if (a == "--devices" && i + 1 < argc) { multi = true; devices.clear(); const std::string l = argv[++i]; size_t p = 0; while (p <= l.size()) { size_t e = l.find(',', p); if (e == std::string::npos) e = l.size(); if (e > p) devices.push_back(std::atoi(l.substr(p, e - p).c_str())); p = e + 1; } }
         else if (a == "--tiles") shardMode = MER_SHARD_TILES;
         else if (a == "--dense") layout = MER_LAYOUT_DENSE;
         else if (a == "--cell8") layout = MER_LAYOUT_CELL8;
@@ -33,18 +34,39 @@ int main(int argc, char **argv) {
             if (e == a.c_str() + 11 || *e || n < 2 || n > 4096) { std::fprintf(stderr, "--mesh-sdf=N expects a node count between 2 and 4096\n"); return 2; }
             meshSdf = (int) n;
         }
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] scene.xml\n"
+        else if (a.rfind("--fluence=", 0) == 0) {
+            if (!merhost::parseFluenceRes(a.substr(10), fluenceRes)) { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+            fluence = true;
+        }
+        else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
                                                          "  samples (bit-reproducible when every sample lands in one pixel: box filter of radius 0.5); slower\n"
                                                          "  --gpus N / --devices: one context per listed GPU, volumes replicated, samples (default) or 32x32 image tiles (--tiles) sharded over them,\n"
-                                                         "  films reduced with RCCL (distinct devices) or peer copies (a device listed twice)\n"); return 0; }
+                                                         "  films reduced with RCCL (distinct devices) or peer copies (a device listed twice)\n"
+                                                         "  --fluence=NX,NY,NZ: a `ptracer` scene: instead of the film, the fluence inside the medium on a grid of NX x NY x NZ cells over the medium\n"
+                                                         "  shape's bounding box, from width x height x spp light paths on one GPU; -o names a 3-channel float32 VOL (version 3) whose box is that of\n"
+                                                         "  the cell centres, so that a gridvolume reading it interpolates between them; the totals are printed\n"); return 0; }
         else scenePath = a;
     }
+    if (fluence && multi) { std::fprintf(stderr, "--fluence runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
     if (scenePath.empty()) { std::fprintf(stderr, "mer_render: no scene file given\n"); return 2; }
     try {
         auto scene = merhost::loadScene(scenePath, defines);
+        if (fluence) {
+            if (out == "out.npy") out = "fluence.vol";
+            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, spp, seed);
+            const std::vector<float> phi = f.phi();
+            float lo[3], hi[3];                      // the box of the cell centres
+            for (int k = 0; k < 3; k++) { const float half = 0.5f * (f.bmax[k] - f.bmin[k]) / (float) f.res[k]; lo[k] = f.bmin[k] + half; hi[k] = f.bmax[k] - half; }
+            merhost::writeVol(out, phi.data(), f.res[0], f.res[1], f.res[2], 3, lo, hi);
+            std::printf("paths %.0f  escaped %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f\n", f.totals[0], f.totals[1], f.totals[2], f.totals[3],
+                        f.totals[4], f.totals[5], f.totals[6], f.totals[7]);
+            std::printf("wrote %s (%dx%dx%d cells)\n", out.c_str(), f.res[0], f.res[1], f.res[2]);
+            return 0;
+        }
         const int w = scene->sensor->film->width, h = scene->sensor->film->height;
         if (devices.empty()) devices.push_back(device);
         std::vector<float> film = scene->integrator->render(*scene, devices, shardMode, spp, seed, layout, meshSdf, ordered);
