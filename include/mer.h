@@ -265,6 +265,9 @@ typedef struct {
    floor((p - bmin) / (bmax - bmin) * res) is (i, j, k) per axis: the cells are half-open, a point on bmax lies outside */
 typedef int32_t mer_fluence;                                  /* handle, > 0 */
 typedef struct { int32_t res[3]; float bmin[3], bmax[3]; } mer_fluence_desc;
+/* a time-resolved fluence grid (mer_fluence_time_create): the same box, and `frames` bins of width t_bin from t_min on in optical path
+   length; frame f holds the deposits with floorf((l - t_min) / t_bin) == f (half-open).  reserved must be 0. */
+typedef struct { int32_t res[3]; float bmin[3], bmax[3]; int32_t frames; float t_min, t_bin; int32_t reserved; } mer_fluence_time_desc;
 
 enum {
     MER_C_PATHS = 0, MER_C_STEPS, MER_C_RIF_EVALS, MER_C_TENTATIVE, MER_C_REAL,
@@ -430,6 +433,26 @@ int  mer_fluence_clear(mer_context *ctx, mer_fluence f);
 int  mer_fluence_destroy(mer_context *ctx, mer_fluence f);
 int  mer_render_fluence(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_fluence f);
 int  mer_fluence_read(mer_context *ctx, mer_fluence f, double *sums /* [nz][ny][nx][3] or NULL */, double totals[8]);
+
+/* ---- time-resolved fluence: the deposits of mer_render_fluence binned by the optical path length at which they happen.  A time-resolved
+        grid is a second kind of mer_fluence handle: mer_fluence_clear, mer_fluence_destroy, mer_render_fluence and mer_context_destroy take
+        either kind, and mer_render_fluence picks the kernel by the handle's kind (a steady-state handle renders exactly as before).
+        The estimator.  The walk is the steady-state one, draw for draw: for one scene, shard and seed both kinds of handle meet the same
+        collisions with the same w.  The path length l of a deposit is what the light tracer's path length holds at that collision under a
+        TRANSIENT film: the exterior leg from an emitter outside the shape (index 1), plus per free flight the optical length
+        integral n ds of a curved ray or t * rif_const of a straight one, accumulated in float32.  The window is the handle's own: the
+        film fields (decomposition, min_bound, bin_width, calibrated_transient, modulation) stay ignored.
+        frame = floorf((l - t_min) / t_bin).  w goes to sums[frame][cell] when the point lies in the box and 0 <= frame < frames.
+        The grid holds raw float64 sums, double[frames][nz][ny][nx][3].  time-resolved fluence = sums / (paths * cell volume * t_bin),
+        per unit of optical path length; divide the path length by c to get time.  Summed over a window that holds every deposit, sums
+        equals the steady-state grid's.  Raw sums of disjoint shards add.
+        totals[12]: [0..7] as mer_fluence_read has them -- [4..6] is the dropped weight of points outside the box, at any time;
+        [8..10] the weight of deposits inside the box but outside the time window; [11] is 0.
+        mer_fluence_time_create: the box checks of mer_fluence_create; frames 1 ... 4096 (the film's cap); t_min finite; t_bin finite and
+        greater than 0; reserved == 0; cells * frames at most 2^27.  *out = 0 on failure.
+        mer_fluence_read refuses a time-resolved handle and mer_fluence_time_read a steady-state one.  sums may be NULL (totals only). ---- */
+int  mer_fluence_time_create(mer_context *ctx, const mer_fluence_time_desc *desc, mer_fluence *out);
+int  mer_fluence_time_read(mer_context *ctx, mer_fluence f, double *sums /* [frames][nz][ny][nx][3] or NULL */, double totals[12]);
 
 /* ---- leaf entry points for parity tests (host pointers, batched SoA) ------------------------------ */
 /* GridDataSource::lookupFloat (gridvolume.cpp:337-388); out_idx[4*i..] = x1,y1,z1,linear index or -1 */

@@ -28,6 +28,7 @@ SYMBOLS = [
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
     "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
+    "mer_fluence_time_create", "mer_fluence_time_read",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -391,6 +392,40 @@ def validate_fluence(desc):
         raise MerError(at + "more than 2^27 cells")
 
 
+class FluenceTimeDesc(C.Structure):
+    """mer_fluence_time_desc: the box of a FluenceDesc and `frames` bins of width t_bin from t_min on in optical path length"""
+    _fields_ = [("res", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3),
+                ("frames", C.c_int32), ("t_min", C.c_float), ("t_bin", C.c_float), ("reserved", C.c_int32)]
+
+
+def fluence_time_desc(res, bmin, bmax, frames, t_min, t_bin):
+    d = FluenceTimeDesc()
+    d.res[:] = [int(v) for v in res]
+    d.bmin[:] = [float(v) for v in bmin]
+    d.bmax[:] = [float(v) for v in bmax]
+    d.frames, d.t_min, d.t_bin, d.reserved = int(frames), float(t_min), float(t_bin), 0
+    return d
+
+
+def validate_fluence_time(desc):
+    """The refusals of mer_fluence_time_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_fluence_time_create: "
+    try:
+        validate_fluence(desc)                         # the box checks, unchanged
+    except MerError as e:
+        raise MerError(at + str(e)[len("mer_fluence_create: "):]) from None
+    if desc.frames < 1 or desc.frames > 4096:
+        raise MerError(at + "frames must lie in 1 ... 4096")
+    if not np.isfinite(desc.t_min):
+        raise MerError(at + "t_min must be finite")
+    if not (np.isfinite(desc.t_bin) and desc.t_bin > 0):
+        raise MerError(at + "t_bin must be finite and greater than 0")
+    if desc.reserved != 0:
+        raise MerError(at + "reserved must be 0")
+    if desc.res[0] * desc.res[1] * desc.res[2] * desc.frames > 1 << 27:
+        raise MerError(at + "more than 2^27 cells x frames")
+
+
 def lib(path=None):
     """The C-ABI library (ctypes).  path = None: libmer.so; Context(check=True) loads libmer_check.so beside it."""
     path = path or LIB_PATH
@@ -462,7 +497,7 @@ class Context:
             if rc != 0:
                 raise MerError(self.lib.mer_last_error(None).decode())
         self.device_id = device_id
-        self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids
+        self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids; a time-resolved one: (nx, ny, nz, frames)
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -733,6 +768,16 @@ class Context:
         self._fluence_res[h.value] = tuple(d.res)
         return h.value
 
+    def fluence_time_create(self, res, bmin, bmax, frames, t_min, t_bin):
+        """-> handle of a zeroed time-resolved grid: the box of fluence_create, `frames` bins of width t_bin from t_min on in optical path
+        length.  fluence_clear, fluence_destroy and render_fluence take it like any other fluence handle."""
+        d = fluence_time_desc(res, bmin, bmax, frames, t_min, t_bin)
+        validate_fluence_time(d)
+        h = C.c_int32()
+        self._check(self.lib.mer_fluence_time_create(self.h, C.byref(d), C.byref(h)))
+        self._fluence_res[h.value] = tuple(d.res) + (d.frames,)
+        return h.value
+
     def fluence_clear(self, handle):
         self._check(self.lib.mer_fluence_clear(self.h, C.c_int32(handle)))
 
@@ -753,14 +798,28 @@ class Context:
             res = self._fluence_res.get(handle)
             if res is None:
                 raise MerError("mer_fluence_read: unknown fluence handle")
+            if len(res) == 4:
+                raise MerError("mer_fluence_read: time-resolved grid: use mer_fluence_time_read")
             out = np.zeros((res[2], res[1], res[0], 3), np.float64)
         self._check(self.lib.mer_fluence_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
         return out, totals
 
-    def fluence(self, scene, res, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
-        """One fluence map of the scene (integrator = ptracer): (phi float64 [nz][ny][nx][3], info).  phi = sums / (paths x cell volume), per
-        unit of the emitters' intensity / power; the box defaults to the bounding box of the medium shape.  info: the totals by name
-        (paths, escaped [3], dropped [3], ended), the raw sums, the box and the cell volume."""
+    def fluence_time_read(self, handle, sums=True):
+        """-> (raw sums float64 [frames][nz][ny][nx][3], or None with sums = False; totals float64 [12])"""
+        totals = np.zeros(12, np.float64)
+        out = None
+        if sums:
+            res = self._fluence_res.get(handle)
+            if res is None:
+                raise MerError("mer_fluence_time_read: unknown fluence handle")
+            if len(res) != 4:
+                raise MerError("mer_fluence_time_read: steady-state grid: use mer_fluence_read")
+            out = np.zeros((res[3], res[2], res[1], res[0], 3), np.float64)
+        self._check(self.lib.mer_fluence_time_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
+        return out, totals
+
+    def _fluence_box(self, scene, bmin, bmax):
+        """the box of a fluence map: the caller's, or the bounding box of the medium shape"""
         if bmin is None or bmax is None:
             if scene.boundary == P.BOUNDARY_SPHERE:
                 c, r = np.array(scene.sph_center[:], np.float64), float(scene.sph_radius)
@@ -769,6 +828,33 @@ class Context:
                 lo, hi = np.array(scene.bmin[:], np.float64), np.array(scene.bmax[:], np.float64)
             bmin = lo if bmin is None else bmin
             bmax = hi if bmax is None else bmax
+        return bmin, bmax
+
+    def fluence_time(self, scene, res, frames, t_min, t_bin, spp_count, seed=0, bmin=None, bmax=None):
+        """One time-resolved fluence map of the scene (integrator = ptracer): (phi float64 [frames][nz][ny][nx][3], info).
+        phi = sums / (paths x cell volume x t_bin), per unit of optical path length (divide the path length by c to get time) and of the
+        emitters' intensity / power; the box defaults to the bounding box of the medium shape.  info: as Context.fluence has it, plus
+        out_of_window [3] (the weight of deposits inside the box but outside the window), frames, t_min and t_bin."""
+        bmin, bmax = self._fluence_box(scene, bmin, bmax)
+        h = self.fluence_time_create(res, bmin, bmax, frames, t_min, t_bin)
+        try:
+            self.render_fluence(scene, h, 0, spp_count, seed)
+            sums, t = self.fluence_time_read(h)
+        finally:
+            self.fluence_destroy(h)
+        d = fluence_time_desc(res, bmin, bmax, frames, t_min, t_bin)
+        volume = float(np.prod([(np.float64(d.bmax[a]) - np.float64(d.bmin[a])) / d.res[a] for a in range(3)]))
+        info = {"paths": t[0], "escaped": t[1:4].copy(), "dropped": t[4:7].copy(), "ended": t[7], "out_of_window": t[8:11].copy(), "sums": sums,
+                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64), "cell_volume": volume,
+                "frames": d.frames, "t_min": float(d.t_min), "t_bin": float(d.t_bin)}
+        phi = sums / (t[0] * volume * np.float64(d.t_bin)) if t[0] > 0 else np.zeros_like(sums)
+        return phi, info
+
+    def fluence(self, scene, res, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
+        """One fluence map of the scene (integrator = ptracer): (phi float64 [nz][ny][nx][3], info).  phi = sums / (paths x cell volume), per
+        unit of the emitters' intensity / power; the box defaults to the bounding box of the medium shape.  info: the totals by name
+        (paths, escaped [3], dropped [3], ended), the raw sums, the box and the cell volume."""
+        bmin, bmax = self._fluence_box(scene, bmin, bmax)
         h = self.fluence_create(res, bmin, bmax)
         try:
             self.render_fluence(scene, h, spp_begin, spp_count, seed)

@@ -10,18 +10,27 @@
 // One lane runs one path, as in K_ptracer, but the event loop is WAVE-UNIFORM: it runs while any lane of the wave has a live path, and a lane
 // whose path has ended idles through the body.  All 64 lanes therefore meet at the single deposit site at the end of the body, outside the
 // lane-dependent free-flight loop, where fluence_deposit merges the deposits of equal cells over the wave before it touches memory.
+//
+// TIMED (a handle of mer_fluence_time_create): the same walk, draw for draw, that also carries the light tracer's optical path length `plen`
+// (float32: the exterior leg at index 1, then m.opticalLength or m.t * rif_const per free flight) and bins every deposit by it:
+// frame = floorf((plen - t_min) / t_bin), key = frame * n_cells + cell.  The window is the handle's own; the film fields stay ignored.
 #pragma once
 #include "mer_ptracer.hpp"          // emit_ray and the bounds PT_* of a light path; the Connector it brings along is not instantiated here
 
 namespace mer {
 
-// the grid of one mer_fluence handle on the device: sums = double[nz][ny][nx][3], totals = double[8] (mer.h)
+// the grid of one mer_fluence handle on the device: sums = double[nz][ny][nx][3], totals = double[8] (mer.h); a time-resolved handle:
+// sums = double[frames][nz][ny][nx][3], n_keys() = frames * n_cells of them (at most 2^27), totals = double[12].  The steady-state
+// kernels read none of the fields after bmax.
 struct FluenceGrid {
     double *sums, *totals;
     unsigned long long *chk;
     uint64_t n_cells;
     int32_t res[3];
     float bmin[3], bmax[3];
+    int32_t frames;
+    float t_min, t_bin;
+    __host__ __device__ uint64_t n_keys() const { return (uint64_t) frames * n_cells; }
 };
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
@@ -45,6 +54,10 @@ __device__ __forceinline__ bool fluence_cell(const FluenceGrid &G, f3 p, uint32_
 // lane's cell are found with a ballot, their three channels are summed over the wave in float64, that first lane issues the three atomics,
 // and the group leaves the pending mask: at most 64 trips, one per distinct cell.  A group of one skips the sums.
 // Measured against one lane, three atomics (the fluence grid): 1.75 x the paths/s of the laser example on a 32^3 grid, 5.1 x on 8^3, a tie on 128^3.
+// TIMED: `cell` is the key frame * n_cells + cell and the extent is the time-resolved grid's.  With frames the keys of a wave spread further, so
+// the A/B was repeated (the time-resolved grid; 32^3, 1 / 16 / 100 frames): a tie on the acoustic field, where the walk dominates, and on
+// the homogeneous medium a tie when the window holds a tenth of the deposits, 1.7 - 1.8 x when it holds nearly all.  The merge stays here too.
+template <bool TIMED>
 __device__ __forceinline__ void fluence_deposit(const FluenceGrid &G, bool dep, uint32_t cell, f3 w) {
     const int lane = threadIdx.x & 63;
     unsigned long long todo = __ballot(dep);
@@ -56,7 +69,7 @@ __device__ __forceinline__ void fluence_deposit(const FluenceGrid &G, bool dep, 
         double a = same ? (double) w.x : 0.0, b = same ? (double) w.y : 0.0, c = same ? (double) w.z : 0.0;
         if (m & (m - 1ULL)) { a = wave_sum_f64(a); b = wave_sum_f64(b); c = wave_sum_f64(c); }
         if (lane == leader) {
-            double *dst = G.sums + MER_CHK(G.chk, CHK_FLUENCE, (uint64_t) lc * 3u, G.n_cells * 3u - 2u);
+            double *dst = G.sums + MER_CHK(G.chk, CHK_FLUENCE, (uint64_t) lc * 3u, (TIMED ? G.n_keys() : G.n_cells) * 3u - 2u);
             atomicAdd(dst, a); atomicAdd(dst + 1, b); atomicAdd(dst + 2, c);
         }
         todo &= ~m;
@@ -64,7 +77,7 @@ __device__ __forceinline__ void fluence_deposit(const FluenceGrid &G, bool dep, 
 }
 
 // K_fluence: light path j = work id `first + j` of the shard, as K_ptracer has it
-template <bool CURVED, int RIF, int STEPPER, int SIGMA>
+template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool TIMED>
 __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const FluenceGrid G, uint64_t first, uint32_t count) {
     const mer_scene_desc &S = P.sc;
     const uint32_t j = blockIdx.x * PT_BLOCK + threadIdx.x;
@@ -80,6 +93,8 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
     f3 escaped(0, 0, 0);                                     // a path escapes once
     double dropped[3] = {0.0, 0.0, 0.0};
     uint32_t ended = 0;
+    float plen = 0.0f;                                       // TIMED: the optical path length, accumulated in float32 as K_ptracer does under a TRANSIENT film
+    double late[3] = {0.0, 0.0, 0.0};                        // TIMED: the weight of deposits inside the box but outside the time window
     // Russian roulette at the end of every loop trip of process() (particleproc.cpp:258-267): q = min(max throughput, 0.95), no eta^2
     auto roulette = [&]() -> bool {
         if (depth++ >= S.rr_depth) {
@@ -100,7 +115,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
             alive = 0;
             if (depth <= maxDepth || maxDepth < 0) {
                 const float tIn = intersect_shape(S, ps, dcur, 0.0f, MER_INF);
-                if (tIn >= 0) { ps = ps + dcur * tIn; entering = true; alive = roulette(); }
+                if (tIn >= 0) { if (TIMED) plen += tIn; ps = ps + dcur * tIn; entering = true; alive = roulette(); }      // the exterior leg: index 1
                 else escaped = power;                        // the emitted ray misses the shape
             }
         }
@@ -139,6 +154,14 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                             w = T * power * (m.transmittance / m.pdfSuccess);
                             dep = fluence_cell(G, m.p, cell);
                             if (!dep) { dropped[0] += (double) w.x; dropped[1] += (double) w.y; dropped[2] += (double) w.z; }
+                            if (TIMED) {
+                                plen += CURVED ? m.opticalLength : m.t * S.rif_const;
+                                if (dep) {
+                                    const float b = floorf((plen - G.t_min) / G.t_bin);                  // film_contribute's bin
+                                    if (b >= 0.0f && b < (float) G.frames) cell += (uint32_t) b * (uint32_t) G.n_cells;      // the key, below 2^27
+                                    else { dep = false; late[0] += (double) w.x; late[1] += (double) w.y; late[2] += (double) w.z; }
+                                }
+                            }
                             T = T * (m.sigmaS * m.transmittance / m.pdfSuccess);
                             const f3 wi = CURVED ? normalize(-m.d) : -W.v;
                             ps = m.p;
@@ -155,7 +178,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                 }
             }
         }
-        fluence_deposit(G, dep, cell, w);
+        fluence_deposit<TIMED>(G, dep, cell, w);
     }
     if (alive) ended++;                                      // PT_MAX_EVENTS
 
@@ -164,7 +187,15 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                            wave_sum_f64(dropped[0]), wave_sum_f64(dropped[1]), wave_sum_f64(dropped[2]), (double) wave_sum(ended)};
     const uint32_t sums[8] = {wave_sum(C.paths), wave_sum(C.steps), wave_sum(C.rif_evals), wave_sum(C.tentative), wave_sum(C.real), wave_sum(C.segments),
                               wave_sum(C.nee), wave_sum(C.marched)};
+    // out of the window: per lane and flushed once per wave like the other totals -- as one more key of the grid it would be a single
+    // address that most deposits of a scene whose window starts late hit (measured: 4 x the time of the whole render on the laser example)
+    double out_of_window[3] = {0.0, 0.0, 0.0};
+    if (TIMED) { out_of_window[0] = wave_sum_f64(late[0]); out_of_window[1] = wave_sum_f64(late[1]); out_of_window[2] = wave_sum_f64(late[2]); }
     if ((threadIdx.x & 63) == 0) {
+        if (TIMED) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) if (out_of_window[q] != 0.0) atomicAdd(G.totals + 8 + q, out_of_window[q]);
+        }
 #pragma unroll
         for (int q = 0; q < 8; q++) if (tot[q] != 0.0) atomicAdd(G.totals + q, tot[q]);
         unsigned long long *dst = P.counters + (size_t) (blockIdx.x % MER_COUNTER_REPLICAS) * MER_C_COUNT;

@@ -34,10 +34,17 @@ struct EnvMap {
 };
 
 // a fluence grid (mer_fluence_create): one device buffer -- the sums double[nz][ny][nx][3], then the 8 totals.  Its handle shares the volumes' numbering.
+// A time-resolved grid (mer_fluence_time_create, frames > 0) is the second kind of the same handle: the sums double[frames][nz][ny][nx][3], then 12 totals.
 struct Fluence {
     mer_fluence_desc desc;
     double *dev = nullptr;
     uint64_t n_cells = 0;
+    int32_t frames = 0;                          // 0: a steady-state grid
+    float t_min = 0, t_bin = 0;
+    bool timed() const { return frames > 0; }
+    uint64_t n_keys() const { return n_cells * (uint64_t) (frames > 0 ? frames : 1); }
+    double *totals() const { return dev + n_keys() * 3; }
+    size_t bytes() const { return (n_keys() * 3 + (frames > 0 ? 12 : 8)) * sizeof(double); }
 };
 
 #define MER_MAX_PIPES 4

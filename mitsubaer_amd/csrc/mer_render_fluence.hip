@@ -1,6 +1,7 @@
 // mer_render_fluence.hip -- the fluence grid recorded from light paths: instantiations of K_fluence (mer_fluence.hpp), its host loop (the
 // light tracer's: launches of PT_PATHS_PER_LAUNCH / PT_PATHS_PER_LAUNCH_CURVED paths on the context stream, returned synchronised) and the
-// mer_fluence_* entry points.  A grid is one device allocation: double[nz][ny][nx][3] sums, then the 8 totals.
+// mer_fluence_* entry points.  A grid is one device allocation: double[nz][ny][nx][3] sums, then the 8 totals; a time-resolved grid
+// (mer_fluence_time_create) is double[frames][nz][ny][nx][3] sums, then 12 totals, and renders with the TIMED instantiations.
 #include "mer_internal.hpp"
 #include "mer_fluence.hpp"
 
@@ -8,28 +9,27 @@ namespace mer {
 
 typedef void (*FluenceKernel)(const Params, const FluenceGrid, uint64_t, uint32_t);
 
-// the 14 instantiations pick_ptracer (mer_render_ptracer.hip) selects from
-template <bool CURVED, int RIF, int STEPPER> static FluenceKernel pick_sigma(int sigma) {
-    return sigma == MER_SIGMA_GRID ? fluence_kernel<CURVED, RIF, STEPPER, MER_SIGMA_GRID> : fluence_kernel<CURVED, RIF, STEPPER, MER_SIGMA_HOMOGENEOUS>;
+// the 14 instantiations pick_ptracer (mer_render_ptracer.hip) selects from, once per kind of handle
+template <bool CURVED, int RIF, int STEPPER, bool TIMED> static FluenceKernel pick_sigma(int sigma) {
+    return sigma == MER_SIGMA_GRID ? fluence_kernel<CURVED, RIF, STEPPER, MER_SIGMA_GRID, TIMED> : fluence_kernel<CURVED, RIF, STEPPER, MER_SIGMA_HOMOGENEOUS, TIMED>;
 }
-template <int RIF> static FluenceKernel pick_curved(int stepper, int sigma) {
-    if (stepper == MER_STEP_VERLET) return pick_sigma<true, RIF, MER_STEP_VERLET>(sigma);
-    if (stepper == MER_STEP_RK4) return pick_sigma<true, RIF, MER_STEP_RK4>(sigma);
+template <int RIF, bool TIMED> static FluenceKernel pick_curved(int stepper, int sigma) {
+    if (stepper == MER_STEP_VERLET) return pick_sigma<true, RIF, MER_STEP_VERLET, TIMED>(sigma);
+    if (stepper == MER_STEP_RK4) return pick_sigma<true, RIF, MER_STEP_RK4, TIMED>(sigma);
     return nullptr;
 }
-static FluenceKernel pick_fluence(const mer_scene_desc *sc) {
+template <bool TIMED> static FluenceKernel pick_fluence(const mer_scene_desc *sc) {
     const int sigma = sc->sigma_mode == MER_SIGMA_GRID ? MER_SIGMA_GRID : MER_SIGMA_HOMOGENEOUS;
     switch (sc->rif_mode) {
-    case MER_RIF_CONST: return pick_sigma<false, MER_RIF_TRILINEAR, MER_STEP_VERLET>(sigma);
-    case MER_RIF_TRILINEAR: return pick_curved<MER_RIF_TRILINEAR>(sc->stepper, sigma);
-    case MER_RIF_BSPLINE3: return pick_curved<MER_RIF_BSPLINE3>(sc->stepper, sigma);
-    case MER_RIF_ACOUSTIC: return pick_curved<RIFK_ACOUSTIC>(sc->stepper, sigma);
+    case MER_RIF_CONST: return pick_sigma<false, MER_RIF_TRILINEAR, MER_STEP_VERLET, TIMED>(sigma);
+    case MER_RIF_TRILINEAR: return pick_curved<MER_RIF_TRILINEAR, TIMED>(sc->stepper, sigma);
+    case MER_RIF_BSPLINE3: return pick_curved<MER_RIF_BSPLINE3, TIMED>(sc->stepper, sigma);
+    case MER_RIF_ACOUSTIC: return pick_curved<RIFK_ACOUSTIC, TIMED>(sc->stepper, sigma);
     }
     return nullptr;
 }
 
-static int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d) {
-    const std::string at = "mer_fluence_create: ";
+static int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d, const std::string &at = "mer_fluence_create: ") {
     uint64_t cells = 1;
     for (int a = 0; a < 3; a++) {
         if (d->res[a] < 1 || d->res[a] > 1024) return fail(ctx, at + "res must lie in 1 ... 1024 on every axis");
@@ -38,6 +38,34 @@ static int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d) {
         cells *= (uint64_t) d->res[a];
     }
     if (cells > ((uint64_t) 1 << 27)) return fail(ctx, at + "more than 2^27 cells");
+    return 0;
+}
+
+// the box checks of mer_fluence_create, then the window's
+static int check_fluence_time_desc(mer_context *ctx, const mer_fluence_time_desc *d) {
+    const std::string at = "mer_fluence_time_create: ";
+    mer_fluence_desc box;
+    for (int a = 0; a < 3; a++) { box.res[a] = d->res[a]; box.bmin[a] = d->bmin[a]; box.bmax[a] = d->bmax[a]; }
+    if (check_fluence_desc(ctx, &box, at)) return 1;
+    if (d->frames < 1 || d->frames > 4096) return fail(ctx, at + "frames must lie in 1 ... 4096");
+    if (!std::isfinite(d->t_min)) return fail(ctx, at + "t_min must be finite");
+    if (!std::isfinite(d->t_bin) || !(d->t_bin > 0)) return fail(ctx, at + "t_bin must be finite and greater than 0");
+    if (d->reserved != 0) return fail(ctx, at + "reserved must be 0");
+    const uint64_t cells = (uint64_t) d->res[0] * (uint64_t) d->res[1] * (uint64_t) d->res[2];
+    if (cells * (uint64_t) d->frames > ((uint64_t) 1 << 27)) return fail(ctx, at + "more than 2^27 cells x frames");
+    return 0;
+}
+
+// the zeroed device buffer of a checked grid and its handle
+static int alloc_fluence(mer_context *ctx, Fluence &F, const char *who, mer_fluence *out) {
+    HIP_CHECK(ctx, hipMalloc((void **) &F.dev, F.bytes()));
+    if (hipMemsetAsync(F.dev, 0, F.bytes(), ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        (void) hipFree(F.dev);
+        return fail(ctx, std::string(who) + ": clearing the grid failed");
+    }
+    const int h = ctx->next_handle++;
+    ctx->fluences[h] = F;
+    *out = h;
     return 0;
 }
 
@@ -56,7 +84,7 @@ static int launch_fluence(mer_context *ctx, const mer_scene_desc *scene, const m
         shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
         return fail(ctx, "invalid shard");
     if (P.n_point <= 0) return fail(ctx, "ptracer: the scene has no emitter (list entries of kind point, spot or collimated)");
-    const FluenceKernel kernel = pick_fluence(scene);
+    const FluenceKernel kernel = F.timed() ? pick_fluence<true>(scene) : pick_fluence<false>(scene);
     if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
     // the work ids of the shard, as launch_ptracer lays them out (decode_work)
     P.seed = seed;
@@ -69,7 +97,8 @@ static int launch_fluence(mer_context *ctx, const mer_scene_desc *scene, const m
     P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) shard->spp_count;
     P.film = nullptr; P.path_out = nullptr; P.n_film = 0; P.n_path_out = 0;          // no film: the sensor fields only enumerate the paths
     FluenceGrid G;
-    G.sums = F.dev; G.totals = F.dev + F.n_cells * 3; G.chk = ctx->chk; G.n_cells = F.n_cells;
+    G.sums = F.dev; G.totals = F.totals(); G.chk = ctx->chk; G.n_cells = F.n_cells;
+    G.frames = F.frames; G.t_min = F.t_min; G.t_bin = F.t_bin;
     for (int a = 0; a < 3; a++) { G.res[a] = F.desc.res[a]; G.bmin[a] = F.desc.bmin[a]; G.bmax[a] = F.desc.bmax[a]; }
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (P.total_work == 0) return 0;
@@ -102,16 +131,20 @@ int mer_fluence_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluen
     Fluence F;
     F.desc = *desc;
     F.n_cells = (uint64_t) desc->res[0] * (uint64_t) desc->res[1] * (uint64_t) desc->res[2];
-    const size_t bytes = (F.n_cells * 3 + 8) * sizeof(double);
-    HIP_CHECK(ctx, hipMalloc((void **) &F.dev, bytes));
-    if (hipMemsetAsync(F.dev, 0, bytes, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        (void) hipFree(F.dev);
-        return fail(ctx, "mer_fluence_create: clearing the grid failed");
-    }
-    const int h = ctx->next_handle++;
-    ctx->fluences[h] = F;
-    *out = h;
-    return 0;
+    return alloc_fluence(ctx, F, "mer_fluence_create", out);
+}
+
+int mer_fluence_time_create(mer_context *ctx, const mer_fluence_time_desc *desc, mer_fluence *out) {
+    if (!ctx) return 1;
+    (void) hipSetDevice(ctx->device);
+    if (!desc || !out) return fail(ctx, "mer_fluence_time_create: invalid arguments");
+    *out = 0;
+    if (check_fluence_time_desc(ctx, desc)) return 1;
+    Fluence F;
+    for (int a = 0; a < 3; a++) { F.desc.res[a] = desc->res[a]; F.desc.bmin[a] = desc->bmin[a]; F.desc.bmax[a] = desc->bmax[a]; }
+    F.n_cells = (uint64_t) desc->res[0] * (uint64_t) desc->res[1] * (uint64_t) desc->res[2];
+    F.frames = desc->frames; F.t_min = desc->t_min; F.t_bin = desc->t_bin;
+    return alloc_fluence(ctx, F, "mer_fluence_time_create", out);
 }
 
 int mer_fluence_clear(mer_context *ctx, mer_fluence h) {
@@ -119,7 +152,7 @@ int mer_fluence_clear(mer_context *ctx, mer_fluence h) {
     (void) hipSetDevice(ctx->device);
     const Fluence *F = find_fluence(ctx, h, "mer_fluence_clear");
     if (!F) return 1;
-    HIP_CHECK(ctx, hipMemsetAsync(F->dev, 0, (F->n_cells * 3 + 8) * sizeof(double), ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(F->dev, 0, F->bytes(), ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -149,10 +182,24 @@ int mer_fluence_read(mer_context *ctx, mer_fluence h, double *sums, double total
     (void) hipSetDevice(ctx->device);
     const Fluence *F = find_fluence(ctx, h, "mer_fluence_read");
     if (!F) return 1;
+    if (F->timed()) return fail(ctx, "mer_fluence_read: time-resolved grid: use mer_fluence_time_read");
     if (!totals) return fail(ctx, "mer_fluence_read: invalid arguments");
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     if (sums) HIP_CHECK(ctx, hipMemcpy(sums, F->dev, F->n_cells * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(totals, F->dev + F->n_cells * 3, 8 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(totals, F->totals(), 8 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int mer_fluence_time_read(mer_context *ctx, mer_fluence h, double *sums, double totals[12]) {
+    if (!ctx) return 1;
+    (void) hipSetDevice(ctx->device);
+    const Fluence *F = find_fluence(ctx, h, "mer_fluence_time_read");
+    if (!F) return 1;
+    if (!F->timed()) return fail(ctx, "mer_fluence_time_read: steady-state grid: use mer_fluence_read");
+    if (!totals) return fail(ctx, "mer_fluence_time_read: invalid arguments");
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    if (sums) HIP_CHECK(ctx, hipMemcpy(sums, F->dev, F->n_keys() * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(totals, F->totals(), 12 * sizeof(double), hipMemcpyDeviceToHost));       // [11] is never written: 0
     return 0;
 }
 

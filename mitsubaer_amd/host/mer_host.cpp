@@ -1122,17 +1122,23 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
 // The fluence grid of a `ptracer` scene: one context (a mer_multi of one device, for the uploads it shares with render()), one grid over the
 // medium shape's bounding box, width x height x spp light paths.
 Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const {
+    return renderFluence(scene, device, res, 0, 0.0f, 0.0f, spp, seed);
+}
+// frames = 0: the steady-state grid; frames > 0: the time-resolved one
+Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed) const {
     if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
     mer_scene_desc d;
     flatten(scene, d);
     if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
     Fluence out;
     mer_fluence_desc fd;
+    mer_fluence_time_desc td;
     for (int a = 0; a < 3; a++) {
-        fd.res[a] = out.res[a] = res[a];
-        fd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
-        fd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
+        td.res[a] = fd.res[a] = out.res[a] = res[a];
+        td.bmin[a] = fd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
+        td.bmax[a] = fd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
     }
+    td.frames = out.frames = frames; td.t_min = out.tMin = tMin; td.t_bin = out.tBin = tBin; td.reserved = 0;
     mer_multi *mm = NULL;
     const int32_t id = device;
     if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
@@ -1140,17 +1146,19 @@ Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, co
     mer_context *ctx = mer_multi_context(mm, 0);
     auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
     mer_fluence f = 0;
-    if (mer_fluence_create(ctx, &fd, &f)) fail();
+    if (frames > 0 ? mer_fluence_time_create(ctx, &td, &f) : mer_fluence_create(ctx, &fd, &f)) fail();
     const mer_shard whole = {0, spp, 1, 0, 1};
     if (mer_render_fluence(ctx, &d, &whole, seed, f)) fail();
-    out.sums.resize((size_t) res[0] * res[1] * res[2] * 3);
-    if (mer_fluence_read(ctx, f, out.sums.data(), out.totals)) fail();
+    out.sums.resize((size_t) (frames > 0 ? frames : 1) * res[0] * res[1] * res[2] * 3);
+    for (int q = 8; q < 12; q++) out.totals[q] = 0.0;
+    if (frames > 0 ? mer_fluence_time_read(ctx, f, out.sums.data(), out.totals) : mer_fluence_read(ctx, f, out.sums.data(), out.totals)) fail();
     mer_multi_destroy(mm);                     // frees the grid with its context
     return out;
 }
 std::vector<float> Integrator::Fluence::phi() const {
     double volume = 1.0;
     for (int a = 0; a < 3; a++) volume *= ((double) bmax[a] - (double) bmin[a]) / res[a];
+    if (frames > 0) volume *= (double) tBin;
     const double inv = totals[0] > 0 ? 1.0 / (totals[0] * volume) : 0.0;
     std::vector<float> v(sums.size());
     for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
@@ -1191,6 +1199,19 @@ void writeNpy(const std::string &path, const float *data, int h, int w, int c) {
     const unsigned short len = (unsigned short) hdr.size();
     f.write("\x93NUMPY\x01\x00", 8); f.write((const char *) &len, 2); f.write(hdr.data(), (std::streamsize) hdr.size());
     f.write((const char *) data, (std::streamsize) ((size_t) h * w * c * 4));
+}
+void writeNpy(const std::string &path, const float *data, const std::vector<int> &shape) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) Log_EError("Unable to write \"" + path + "\"");
+    std::string hdr = "{'descr': '<f4', 'fortran_order': False, 'shape': (";
+    size_t count = 1;
+    for (int n : shape) { hdr += std::to_string(n) + ", "; count *= (size_t) n; }
+    hdr += "), }";
+    while ((10 + hdr.size() + 1) % 64 != 0) hdr += ' ';
+    hdr += '\n';
+    const unsigned short len = (unsigned short) hdr.size();
+    f.write("\x93NUMPY\x01\x00", 8); f.write((const char *) &len, 2); f.write(hdr.data(), (std::streamsize) hdr.size());
+    f.write((const char *) data, (std::streamsize) (count * 4));
 }
 void writeVol(const std::string &path, const float *data, int nx, int ny, int nz, int channels, const float aabbMin[3], const float aabbMax[3]) {
     std::ofstream f(path, std::ios::binary);

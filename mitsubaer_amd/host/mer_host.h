@@ -233,12 +233,16 @@ public:
     /// one device.  Any other integrator is refused
     struct Fluence {
         int res[3]; float bmin[3], bmax[3];
-        std::vector<double> sums;               ///< raw sums [nz][ny][nx][3]
-        double totals[8];                       ///< paths, escaped x 3, dropped x 3, ended (mer_fluence_read)
-        /// sums / (paths x cell volume), float32 [nz][ny][nx][3]
+        int frames = 0; float tMin = 0.0f, tBin = 0.0f;   ///< the time-resolved form: frames > 0 bins of width tBin from tMin on in optical path length
+        std::vector<double> sums;               ///< raw sums [nz][ny][nx][3]; time-resolved: [frames][nz][ny][nx][3]
+        double totals[12];                      ///< paths, escaped x 3, dropped x 3, ended (mer_fluence_read); time-resolved: then out-of-window x 3 and 0 (mer_fluence_time_read)
+        /// sums / (paths x cell volume), float32 [nz][ny][nx][3]; time-resolved: sums / (paths x cell volume x tBin), [frames][nz][ny][nx][3]
         std::vector<float> phi() const;
     };
     Fluence renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const;
+    /// the time-resolved form (mer_fluence_time_create): every deposit also binned by the optical path length at which it happens.  The window is
+    /// the caller's; the scene's film is not read
+    Fluence renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed) const;
 private:
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
     void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;
@@ -265,6 +269,8 @@ std::shared_ptr<Scene> loadSceneFromString(const std::string &xml, const std::ma
 /// film [h][w][frames*3+2] -> developed RGB [frames][h][w][3] (HDRFilm::develop: divide by the weight channel)
 std::vector<float> develop(const std::vector<float> &film, int w, int h, int frames = 1);
 void writeNpy(const std::string &path, const float *data, int h, int w, int c);
+/// float32 of any shape (`mer_render --fluence --time-resolved`: [frames][nz][ny][nx][3])
+void writeNpy(const std::string &path, const float *data, const std::vector<int> &shape);
 void writePfm(const std::string &path, const float *rgb, int h, int w);
 /// VOL version 3 (src/volume/gridvolume.cpp:108-198), float32: data [nz][ny][nx][channels], the box the first and last nodes lie on
 void writeVol(const std::string &path, const float *data, int nx, int ny, int nz, int channels, const float aabbMin[3], const float aabbMax[3]);

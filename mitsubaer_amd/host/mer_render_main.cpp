@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cstdio>
@@ -12,6 +12,7 @@ int main(int argc, char **argv) {
     bool ordered = false;          // --ordered: one render per sample index, films added in index order
     int meshSdf = -1;              // --mesh-sdf[=N]: -1 off, 0 = the rif volume's grid, N = nodes on the longest axis of the mesh's box
     int fluenceRes[3] = {0, 0, 0}; bool fluence = false, multi = false;   // --fluence=NX,NY,NZ: the fluence grid of a ptracer scene instead of its film
+    bool timeResolved = false;     // --time-resolved: that grid per frame of the film's transient window
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -38,8 +39,9 @@ int main(int argc, char **argv) {
             if (!merhost::parseFluenceRes(a.substr(10), fluenceRes)) { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
             fluence = true;
         }
+        else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -48,13 +50,33 @@ int main(int argc, char **argv) {
                                                          "  films reduced with RCCL (distinct devices) or peer copies (a device listed twice)\n"
                                                          "  --fluence=NX,NY,NZ: a `ptracer` scene: instead of the film, the fluence inside the medium on a grid of NX x NY x NZ cells over the medium\n"
                                                          "  shape's bounding box, from width x height x spp light paths on one GPU; -o names a 3-channel float32 VOL (version 3) whose box is that of\n"
-                                                         "  the cell centres, so that a gridvolume reading it interpolates between them; the totals are printed\n"); return 0; }
+                                                         "  the cell centres, so that a gridvolume reading it interpolates between them; the totals are printed\n"
+                                                         "  --time-resolved (with --fluence=): the scene's film must have decomposition = transient; every deposit is also binned by its optical path\n"
+                                                         "  length into the film's window (minBound, binWidth, ceil((maxBound - minBound) / binWidth) frames); -o names a float32 .npy\n"
+                                                         "  [frames][nz][ny][nx][3] = sums / (paths x cell volume x binWidth); the totals also print the weight outside the window\n"); return 0; }
         else scenePath = a;
     }
     if (fluence && multi) { std::fprintf(stderr, "--fluence runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
+    if (timeResolved && !fluence) { std::fprintf(stderr, "--time-resolved needs --fluence=NX,NY,NZ\n"); return 2; }
+    if (timeResolved) {
+        if (out == "out.npy") out = "fluence_t.npy";
+        if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--time-resolved writes a .npy file ([frames][nz][ny][nx][3]): a VOL holds 1 or 3 channels\n"); return 2; }
+    }
     if (scenePath.empty()) { std::fprintf(stderr, "mer_render: no scene file given\n"); return 2; }
     try {
         auto scene = merhost::loadScene(scenePath, defines);
+        if (fluence && timeResolved) {
+            const merhost::Film &film = *scene->sensor->film;
+            if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
+            const int frames = (int) std::ceil((film.maxBound - film.minBound) / film.binWidth);
+            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, frames, film.minBound, film.binWidth, spp, seed);
+            const std::vector<float> phi = f.phi();
+            merhost::writeNpy(out, phi.data(), std::vector<int>{f.frames, f.res[2], f.res[1], f.res[0], 3});
+            std::printf("paths %.0f  escaped %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f  out of window %.9g %.9g %.9g\n", f.totals[0], f.totals[1], f.totals[2],
+                        f.totals[3], f.totals[4], f.totals[5], f.totals[6], f.totals[7], f.totals[8], f.totals[9], f.totals[10]);
+            std::printf("wrote %s (%d frames of %dx%dx%d cells)\n", out.c_str(), f.frames, f.res[0], f.res[1], f.res[2]);
+            return 0;
+        }
         if (fluence) {
             if (out == "out.npy") out = "fluence.vol";
             const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, spp, seed);
