@@ -182,6 +182,7 @@ void mer_context_destroy(mer_context *ctx) {
         for (SegQueue *q : {&pp.eq, &pp.mq[0], &pp.mq[1], &pp.sq[0], &pp.sq[1], &pp.cq[0], &pp.cq[1]}) { if (q->items) (void) hipFree(q->items); if (q->counts) (void) hipFree(q->counts); if (q->keys) (void) hipFree(q->keys); }
         if (pp.msort) (void) hipFree(pp.msort);
         if (pp.cstate) (void) hipFree(pp.cstate);
+        if (pp.side_state) (void) hipFree(pp.side_state);
         if (pp.hitq) (void) hipFree(pp.hitq);
         if (pp.hitq_ctr) (void) hipFree(pp.hitq_ctr);
         if (pp.host_live) (void) hipHostFree(pp.host_live);

@@ -41,7 +41,8 @@ __device__ __forceinline__ bool is_zero(f3 a) { return a.x == 0.0f && a.y == 0.0
 // redirected to element 0, so that an out-of-range index is REPORTED (mer_debug_bounds) instead of faulting or, worse, silently
 // reading mapped memory.  The product build compiles the checks away.
 enum { CHK_SLOT = 1, CHK_QUEUE_SEG, CHK_QUEUE_ITEM, CHK_HITQ, CHK_FILM, CHK_PATHOUT, CHK_GRID_DENSE, CHK_GRID_RECORD, CHK_GRID_COEFF,
-       CHK_GRID_RGB, CHK_LIVE_ROW, CHK_ENVMAP, CHK_FLUENCE /* the sums of a fluence grid (mer_fluence.hpp) */ };
+       CHK_GRID_RGB, CHK_LIVE_ROW, CHK_ENVMAP, CHK_FLUENCE /* the sums of a fluence grid (mer_fluence.hpp) */,
+       CHK_SIDE_STATE /* the busy bytes of the side-walk slots (mer_wavefront.hpp) */ };
 #ifdef MER_BOUNDS_CHECK
 __device__ __forceinline__ uint64_t mer_chk(unsigned long long *chk, int kind, uint64_t idx, uint64_t limit) {
     if (idx < limit) return idx;
@@ -787,6 +788,9 @@ struct Params {
     // the point and area emitters (EXTRA kernels): device tables built by make_params from the legacy point_* / area_* fields or from the
     // scene's emitter list -- the records live in device memory, not in these kernel arguments
     int32_t n_point, n_rect; const DPoint *points; const DRect *rects;
+    // spawned side walks: one busy byte per side-walk slot, 8 per path slot (2 x MER_SIDE_PER_KIND used), so that K_event reads a path's six with one
+    // 8-byte load beside the record (mer_wavefront.hpp: side_state_load); NULL unless `spawn`
+    uint8_t *side_state;
 };
 #define MER_LIVE_SLOTS 4096
 #define MER_COUNTER_REPLICAS 64        // counters are flushed into one of this many copies (summed on the host)

@@ -56,6 +56,7 @@ struct Pipe {
     unsigned long long *hitq = nullptr, *hitq_ctr = nullptr; unsigned long long hitq_cap = 0;
     hipEvent_t readback[2] = {nullptr, nullptr}, finished = nullptr;     // two batches in flight per pipeline
     std::vector<hipEvent_t> pass_events;          // 3 per pass: before K_event, between, after K_march
+    uint8_t *side_state = nullptr; uint32_t side_state_slots = 0;   // busy bytes of the side-walk slots, 8 per path slot (allocated with the first render that spawns)
     uint32_t *msort = nullptr; uint32_t msort_cap = 0;            // spatial sort of the march list: sorted ids, gathered ids, keys (cap each), histogram, cursors, count
 };
 

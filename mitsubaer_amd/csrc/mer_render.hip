@@ -247,6 +247,13 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
             pp.cstate_slots = pp.nslots;
         }
         R.P.cstate = pp.cstate;
+        if (spawn && pp.side_state_slots < R.nslots) {           // busy bytes of the side-walk slots: 8 per path slot
+            if (pp.side_state) (void) hipFree(pp.side_state);
+            pp.side_state = nullptr; pp.side_state_slots = 0;
+            HIP_CHECK(ctx, hipMalloc((void **) &pp.side_state, (size_t) std::max(want, R.nslots) * 8u));
+            pp.side_state_slots = std::max(want, R.nslots);
+        }
+        R.P.side_state = spawn ? pp.side_state : nullptr;
         R.P.msort = 0; R.P.mq[0].keys = nullptr; R.P.mq[1].keys = nullptr;
         if (msort_bits) {              // spatial sort of the march list: a cell per list entry (written with the entry), the sorted list, histogram, cursors, count
             if (pp.msort_cap < pp.nslots) {
@@ -275,6 +282,7 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
         HIP_CHECK(ctx, hipMemsetAsync(pp.slots, 0, (size_t) R.nslots * MER_SLOT_WORDS * sizeof(uint32_t), pp.stream));
         // side-walk records: only their state word must read "idle" (the region may hold stale records of a render with another slot count)
         if (spawn) hipLaunchKernelGGL(clear_side_flags_kernel, dim3(nblocks((int64_t) R.nslots * (slot_mult - 1u))), dim3(256), 0, pp.stream, pp.slots, R.nslots, R.nslots * slot_mult);
+        if (spawn) HIP_CHECK(ctx, hipMemsetAsync(pp.side_state, 0, (size_t) R.nslots * 8u, pp.stream));      // ... and K_event's copy of that state (the busy bytes)
         HIP_CHECK(ctx, hipMemsetAsync(pp.live, 0, MER_LIVE_SLOTS * sizeof(uint32_t), pp.stream));
         for (SegQueue *sq : {&pp.eq, &pp.mq[0], &pp.mq[1], &pp.sq[0], &pp.sq[1], &pp.cq[0], &pp.cq[1]})
             HIP_CHECK(ctx, hipMemsetAsync(sq->counts, 0, (size_t) MER_LIVE_SLOTS * MER_NSEG * sizeof(uint32_t), pp.stream));

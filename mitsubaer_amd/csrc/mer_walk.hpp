@@ -230,6 +230,14 @@ struct Walk {
         }
     }
 
+    // A walk whose begin() is left to K_march (MER_FLAG_INIT: mer_wavefront.hpp): the record carries origin, UN-SCALED direction and kind; begin() there sets the
+    // rest.  No RIF fetch, no sampler draw.
+    __device__ __forceinline__ void defer_begin(int k, f3 o, f3 d, float rayMaxt) {
+        kind = k; p = o; v = d; t = rayMaxt;
+        trsum = 0.0f; walk = 0; Tr = 1.0f; dist = 0.0f; opt = 0.0f; backstep = 0; agg = 0; dleft = 0.0f;
+        rem = 0.0f; steps_left = 0; seg_inf = 0; hprev = 0.0f;
+    }
+
     // One unit of marching work.  Curved: one er_step + insideShape test (trace(): :676-689).
     // Straight: one tentative-collision jump (heterogeneous.cpp:633-636).
     // COUNT = false: the caller keeps one trip counter and adds steps / rif_evals / marched itself (K_march's hot loop)

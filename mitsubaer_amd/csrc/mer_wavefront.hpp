@@ -102,13 +102,13 @@ __device__ __forceinline__ void store_cold(const Params &P, uint32_t i, const ui
 // writes the record of a side walk: hot words = (origin, direction, kind, forked sampler state) with the INIT flag -- K_march sets up its first
 // segment (Walk::begin) --, cold words = what K_event needs when the walk has ended (film position, prefactor, the ray for a second Woodcock walk)
 __device__ __forceinline__ void spawn_side_walk(const Params &P, uint32_t c, int kind, f3 o, f3 d, float rayT, f3 pref, float px, float py, uint64_t rng_state,
-                                                uint32_t pixel, uint32_t sample) {
+                                                uint32_t pixel, uint32_t sample, uint32_t state_at) {
     uint32_t *rec = P.slots + (size_t) MER_CHK(P.chk, CHK_SLOT, c, P.nslots_all) * MER_SLOT_WORDS;
     uint4 *r = (uint4 *) rec;
     r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), __float_as_uint(d.x));
     r[1] = make_uint4(__float_as_uint(d.y), __float_as_uint(d.z), 0u, 0u);
     r[2] = make_uint4(0u, 0u, __float_as_uint(1.0f), __float_as_uint(rayT));
-    r[3] = make_uint4(0u, 0u, pack_flags(ST_MARCH, EV_NONE, kind, 0, 0, 0, 0) | MER_FLAG_INIT | MER_FLAG_CHILD, (uint32_t) rng_state);
+    r[3] = make_uint4(state_at /* H_TMAX: the slot's busy byte (side_state_clear) */, 0u, pack_flags(ST_MARCH, EV_NONE, kind, 0, 0, 0, 0) | MER_FLAG_INIT | MER_FLAG_CHILD, (uint32_t) rng_state);
     r[4] = make_uint4((uint32_t) (rng_state >> 32), pixel, sample, 0u);
     uint32_t cw[MER_COLD_WORDS];
 #pragma unroll
@@ -128,25 +128,35 @@ __device__ __forceinline__ void spawn_side_walk(const Params &P, uint32_t c, int
 #define MER_SIDE_PER_KIND 3                                   // side-walk slots per path and kind (luminaire sample / look-up): 2 left 11 - 15 % of the walks in the path's lane, 3 leave ~2 %
 #endif
 enum { F_NEE_ROT = 16 /* bits 4-5 */, F_CHILD = 64, F_LK_ROT = 128 /* bits 7-8 */ };      // path flags (CO_PFLAGS) beside K_event's own: where the search for a free side-walk slot of each kind starts; the record is a side walk
-// first free side-walk slot of (path i, kind k), searched from rotation r: its record id, or 0
-// the state words of path i's 2 x MER_SIDE_PER_KIND side-walk slots, read in ONE round trip at the collision (the look-up's search, half a visit later, finds its
-// three already in registers: a slot can only have become free in between, never busy -- the path itself is the only one that fills them)
-__device__ __forceinline__ void side_flags_load(const Params &P, uint32_t i, uint32_t (&fl)[2 * MER_SIDE_PER_KIND]) {
-    const uint32_t base = P.nslots + i * 2u * MER_SIDE_PER_KIND;
-#pragma unroll
-    for (uint32_t t = 0; t < 2u * MER_SIDE_PER_KIND; t++)
-        fl[t] = P.slots[(size_t) MER_CHK(P.chk, CHK_SLOT, base + t, P.nslots_all) * MER_SLOT_WORDS + H_FLAGS];
+// Busy bytes: whether a side-walk slot is in use is ALSO kept as one byte per slot in P.side_state, 8 bytes per path slot (byte k * MER_SIDE_PER_KIND + q = slot q
+// of kind k; two bytes of padding).  The child record's own state word (H_FLAGS) keeps its meaning for K_march; for K_event's search of a free slot the BYTES
+// are authoritative.  They sit at an address that depends on the path's slot id alone, so K_event reads the eight in its prologue beside the record (one
+// round trip for both) instead of gathering six state words from six different 256-byte records once the collision is known (a dependent round trip of its
+// own).  K_event sets a byte when it spawns; whoever frees the slot -- K_march at the end of the walk, K_event under the two-walk Woodcock estimator -- clears
+// it with a plain byte store (side_state_clear).  A pipeline's K_event and K_march never run at the same time, a path's bytes are set by its own lane only,
+// and byte stores leave their neighbours alone: no atomics.  A slot can only become free between the prologue and the search, never busy.
+static_assert(2 * MER_SIDE_PER_KIND <= 8, "side_state holds 8 bytes per path slot");
+__device__ __forceinline__ uint2 side_state_load(const Params &P, uint32_t i) {
+    return *(const uint2 *) (P.side_state + (size_t) MER_CHK(P.chk, CHK_SIDE_STATE, i, P.nslots) * 8u);
 }
-__device__ __forceinline__ uint32_t free_side_slot(const Params &P, uint32_t i, uint32_t k, uint32_t r, uint32_t &r_next, const uint32_t (&fl)[2 * MER_SIDE_PER_KIND]) {
+__device__ __forceinline__ void side_state_set(const Params &P, uint32_t at) {
+    P.side_state[MER_CHK(P.chk, CHK_SIDE_STATE, at, (uint64_t) P.nslots * 8u)] = 1;
+}
+// `at` = index of the slot's byte (path slot x 8 + kind x MER_SIDE_PER_KIND + q).  The side walk's own record carries it in its H_TMAX word, which curved rays do
+// not use and load_hot / store_hot hand through: the kernel that ends the walk needs neither a division nor the path's slot id, and K_march no register for it.
+__device__ __forceinline__ uint32_t side_state_index(uint32_t i, uint32_t k, uint32_t q) { return i * 8u + k * MER_SIDE_PER_KIND + q; }
+__device__ __forceinline__ void side_state_clear(const Params &P, uint32_t at) {
+    P.side_state[MER_CHK(P.chk, CHK_SIDE_STATE, at, (uint64_t) P.nslots * 8u)] = 0;
+}
+// first free side-walk slot of (path i, kind k), searched from rotation r in the path's busy bytes `ss`: its record id, or 0
+__device__ __forceinline__ uint32_t free_side_slot(const Params &P, uint32_t i, uint32_t k, uint32_t r, uint32_t &r_next, uint2 ss, uint32_t &q_found) {
     const uint32_t base = P.nslots + (i * 2u + k) * MER_SIDE_PER_KIND;
-    uint32_t found = 0u; r_next = r;
+    const uint64_t bytes = ((uint64_t) ss.y << 32) | (uint64_t) ss.x;
+    uint32_t found = 0u; r_next = r; q_found = 0u;
 #pragma unroll
     for (uint32_t t = MER_SIDE_PER_KIND; t-- > 0u; ) {         // last to first, so that the first free slot in rotation order wins
         const uint32_t q = (r + t) % MER_SIDE_PER_KIND;
-        uint32_t f = k ? fl[MER_SIDE_PER_KIND] : fl[0];
-#pragma unroll
-        for (uint32_t u = 1; u < MER_SIDE_PER_KIND; u++) f = q == u ? (k ? fl[MER_SIDE_PER_KIND + u] : fl[u]) : f;
-        if ((f & 3u) == 0u) { found = base + q; r_next = (q + 1u) % MER_SIDE_PER_KIND; }
+        if (((bytes >> (8u * (k * MER_SIDE_PER_KIND + q))) & 0xffu) == 0u) { found = base + q; q_found = q; r_next = (q + 1u) % MER_SIDE_PER_KIND; }
     }
     return found;
 }
@@ -473,8 +483,16 @@ __global__ void __launch_bounds__(MER_BLOCK, MER_MARCH_WAVES) march_kernel(const
         W.cc.reset(); W.n0 = 1.0f; W.tmin = 0.0f; W.trsum = 0.0f; W.sdens = 0.0f;
         int ev = EV_NONE; sigma = 0.0f;
         // a side walk spawned by K_event arrives as (origin, direction, kind, forked sampler): its first segment is set up here, in the lean kernel
-        if (CURVED && (fl & MER_FLAG_INIT)) ev = W.begin(P, rng, C, W.kind, W.p, W.v, W.t);
-        const int K = ev == EV_NONE ? P.ksteps : 0;          // (a side walk whose start failed -- outside the spline's limits -- goes straight to K_event)
+        // ... and so does a PATH's free flight (K_event parks it the same way after Russian roulette and at regeneration): the RIF gather of begin() is
+        // hidden by this kernel's 5 waves per SIMD, in K_event it was a dependent round trip at 2.  The end of the free flight needs refStart again
+        // (finish_free_flight): it rides in the record's H_TMAX word, which curved rays do not use and W.tmax already holds a register for (a store to the
+        // cold words here cost the bench kernel 2 VGPRs and 36 bytes of scratch); a homogeneous sigma_t's sampling density goes to its cold word.  A side
+        // walk's end needs neither, and its H_TMAX is taken (side_state_clear).
+        if (CURVED && (fl & MER_FLAG_INIT)) {
+            ev = W.begin(P, rng, C, W.kind, W.p, W.v, W.t);
+            if (!(fl & MER_FLAG_CHILD)) { W.tmax = W.n0; if (SIGMA != MER_SIGMA_GRID) SLOT(CO_SDENS) = __float_as_uint(W.sdens); }
+        }
+        const int K = ev == EV_NONE ? P.ksteps : 0;          // (a walk whose start failed -- outside the spline's limits -- goes straight to K_event)
         if (CURVED) {
             // A lane reaches a tentative collision about once in 65 steps, so at nearly every trip ONE lane of the wave would drag all
             // 64 through the collision code (sigma_t fetch, ratio / Woodcock test, next exponential segment: ~125 VALU against ~320 for
@@ -507,7 +525,7 @@ __global__ void __launch_bounds__(MER_BLOCK, MER_MARCH_WAVES) march_kernel(const
             const uint4 q = *(const uint4 *) (P.slots + (size_t) MER_CHK(P.chk, CHK_SLOT, i, P.nslots_all) * MER_SLOT_WORDS + CO_PXF);      // film position, prefactor x y
             const f3 c = f3(__uint_as_float(q.z), __uint_as_float(q.w), SLOTF(CO_LZ)) * tr;
             if (!is_zero(c)) film_splat(P, __uint_as_float(q.x), __uint_as_float(q.y), c, 0.0f, 0, 1);
-            SLOT(H_FLAGS) = 0u;
+            SLOT(H_FLAGS) = 0u; side_state_clear(P, __float_as_uint(W.tmax));
             child_ended = true; ev = EV_NONE;
         } else
         store_hot(P, i, ST_MARCH, ev, W, rng, pixel, sample, sigma, fl & MER_FLAG_CHILD);
@@ -586,9 +604,13 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
     PROF_DECL
     bool marching = false, starved_out = false, connecting = false; uint32_t i = 0; int mq_class = 0, cq_class = 0;
     bool child_done = false; uint32_t side_inline = 0;
-    uint32_t sfl[2 * MER_SIDE_PER_KIND] = {}; bool sfl_ok = false;      // state words of the path's side-walk slots (side_flags_load)
+    uint2 sst = make_uint2(0u, 0u);                                          // busy bytes of the path's side-walk slots (side_state_load)
+    bool path_init = false;                                                  // the path's next free flight is begun by K_march (MER_FLAG_INIT)
     uint32_t child0 = 0, child1 = 0; int c0class = 0, c1class = 0;           // side walks this lane has just spawned (0 = none): they join the march list below
     constexpr bool SPAWNABLE = CURVED && !EXTRA;                             // the plain curved kernels (the bench kernels) spawn side walks when P.spawn says so
+    // ... and then hand the START of a path's free flight (Walk::begin: a RIF gather and the first segment's draw) to K_march as well: origin, un-scaled
+    // direction and the path's sampler go into the record with MER_FLAG_INIT.  No draw lies between here and the parked record, so the stream is unchanged.
+    const bool handover = SPAWNABLE && P.spawn != 0;
     if (j < count) {
     i = pass == 0 ? j : (j < nq ? queue_item(P.eq, pass, j) : queue_item(P.sq[pass & 1u], pass, j - nq));
     int st, ev;                                // from the record's state word (below: it arrives with the rest of the record, in one round trip)
@@ -624,6 +646,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
     {   // The whole record is read before its state word is looked at: a lane whose slot holds no path (new, starved) reads a stale or zeroed record and
         // throws it away -- one round trip for the wave instead of two (state word, then the record of the lanes that have one).
         uint32_t fl;
+        if (SPAWNABLE && P.spawn && i < P.nslots) sst = side_state_load(P, i);      // (the address needs the list item only: same round trip as the record)
         load_hot(P, i, fl, W, rng, pixel, sample, sigma);
         st = fl & 3u; ev = (fl >> 2) & 15u;
         uint32_t cw[MER_COLD_WORDS];
@@ -637,6 +660,7 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
         W.sdens = CWF(CO_SDENS); W.tmin = CWF(CO_TMIN);
         plen = CWF(CO_PLEN); trOpt = CWF(CO_TROPT); if (EXTRA) etaPath = CWF(CO_ETA);
         prng = (uint64_t) CW(CO_WNEXT_LO) | ((uint64_t) CW(CO_WNEXT_HI) << 32);
+        if (handover && W.kind == K_FREE) W.n0 = W.tmax;      // a path's free flight was begun by K_march: refStart comes back in H_TMAX
     }
     if (st == ST_MARCH) {
         px_i = (int) (pixel % (uint32_t) S.width); py_i = (int) (pixel / (uint32_t) S.width);
@@ -737,7 +761,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                     }
                     ev = EV_PATH_DONE;
                 }
-                else { C.segments++; ps = ro; dsave = d; ev = W.begin(P, rng, C, K_FREE, ro, d, itsT); }
+                else {
+                    C.segments++; ps = ro; dsave = d;
+                    if (handover) { W.defer_begin(K_FREE, ro, d, itsT); path_init = true; ev = EV_NONE; }
+                    else ev = W.begin(P, rng, C, K_FREE, ro, d, itsT);
+                }
             }
             st = ST_MARCH;
         }
@@ -819,12 +847,12 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                         if (!CURVED) trOpt = tExit * S.rif_const;
                         bool spawned = false;
                         if (SPAWNABLE && P.spawn) {
-                            uint32_t rn; side_flags_load(P, i, sfl); sfl_ok = true; const uint32_t c = free_side_slot(P, i, 0u, ((uint32_t) flags >> 4) & 3u, rn, sfl);
+                            uint32_t rn, sq; const uint32_t c = free_side_slot(P, i, 0u, ((uint32_t) flags >> 4) & 3u, rn, sst, sq);
                             if (c != 0u) {                                            // a side-walk slot is free: the walk goes there, the path goes on
                                 const float phaseVal = phase_eval(S.phase, S.g, wi, dd);
                                 const f3 pref = T * (env / MER_INV_FOURPI) * phaseVal * mi_weight(MER_INV_FOURPI, phaseVal);
                                 if (!is_zero(pref)) {
-                                    spawn_side_walk(P, c, K_NEE, ps, dd, tExit, pref, px, py, rng.fork(1).state, pixel, sample);
+                                    spawn_side_walk(P, c, K_NEE, ps, dd, tExit, pref, px, py, rng.fork(1).state, pixel, sample, side_state_index(i, 0u, sq)); side_state_set(P, side_state_index(i, 0u, sq));
                                     W.p = ps; W.v = dd;                                // (W is idle between the collision and the next free flight: borrowed for the class estimate)
                                     child0 = c; c0class = march_class<CURVED, BND>(P, W);
                                     flags = (int) (((uint32_t) flags & ~(3u << 4)) | (rn << 4));
@@ -972,12 +1000,12 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
                 else {
                     bool spawned = false;
                     if (SPAWNABLE && P.spawn) {
-                        uint32_t rn; if (!sfl_ok) side_flags_load(P, i, sfl); const uint32_t c = free_side_slot(P, i, 1u, ((uint32_t) flags >> 7) & 3u, rn, sfl);
+                        uint32_t rn, sq; const uint32_t c = free_side_slot(P, i, 1u, ((uint32_t) flags >> 7) & 3u, rn, sst, sq);
                         if (c != 0u) {
                             const bool blocked = (maxDepth - depth - 1 == 0);                    // curved rays: the look-up always crosses the boundary once
                             const f3 pref = blocked ? f3(0, 0, 0) : T * env * mi_weight(phasePdf, MER_INV_FOURPI);
                             if (!is_zero(pref)) {
-                                spawn_side_walk(P, c, K_LOOKUP, ps, wo, itsT, pref, px, py, rng.fork(2).state, pixel, sample);
+                                spawn_side_walk(P, c, K_LOOKUP, ps, wo, itsT, pref, px, py, rng.fork(2).state, pixel, sample, side_state_index(i, 1u, sq)); side_state_set(P, side_state_index(i, 1u, sq));
                                 W.p = ps; W.v = wo;
                                 child1 = c; c1class = march_class<CURVED, BND>(P, W);
                                 flags = (int) (((uint32_t) flags & ~(3u << 7)) | (rn << 7));
@@ -1006,7 +1034,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
             if (alive) {
                 SET_FLAG(F_SCATTERED, true);
                 if (!(depth <= maxDepth || maxDepth < 0)) ev = EV_PATH_DONE;
-                else { C.segments++; ev = W.begin(P, rng, C, K_FREE, ps, dsave, itsT); }
+                else {
+                    C.segments++;
+                    if (handover) { W.defer_begin(K_FREE, ps, dsave, itsT); path_init = true; ev = EV_NONE; }
+                    else ev = W.begin(P, rng, C, K_FREE, ps, dsave, itsT);
+                }
             }
         } else if (ev == EV_FAIL) {
             // ---- no medium interaction: volpath.cpp:183-201,289-301
@@ -1074,11 +1106,11 @@ __global__ void __launch_bounds__(MER_BLOCK, INLINE ? MER_INLINE_EVENT_WAVES : M
 
     PROF(7);
     // ---- park the lane
-    if (child_done) SLOT(H_FLAGS) = 0u;                                           // side-walk slot idle again
+    if (child_done) { SLOT(H_FLAGS) = 0u; side_state_clear(P, __float_as_uint(W.tmax)); }               // side-walk slot idle again
     else if (st == ST_DONE) { SLOT(H_FLAGS) = ST_DONE; atomicAdd(P.live, 1u); }      // live[0] counts finished slots
     else if (starved) { SLOT(H_FLAGS) = ST_NEW; starved_out = true; }
     else {
-        store_hot(P, i, ST_MARCH, connecting ? EV_PHASE2 : EV_NONE, W, rng, pixel, sample, 0.0f, (SPAWNABLE && (flags & F_CHILD)) ? MER_FLAG_CHILD : 0u);
+        store_hot(P, i, ST_MARCH, connecting ? EV_PHASE2 : EV_NONE, W, rng, pixel, sample, 0.0f, ((SPAWNABLE && (flags & F_CHILD)) ? MER_FLAG_CHILD : 0u) | (path_init ? MER_FLAG_INIT : 0u));
         uint32_t cw[MER_COLD_WORDS];
         CW(CO_PXF) = __float_as_uint(px); CW(CO_PYF) = __float_as_uint(py);
         CW(CO_LX) = __float_as_uint(L.x); CW(CO_LY) = __float_as_uint(L.y); CW(CO_LZ) = __float_as_uint(L.z);
