@@ -427,7 +427,10 @@ int  mer_counters_reset(mer_context *ctx);
         mer_fluence_create: res 1 ... 1024 per axis, at most 2^27 cells, bmin < bmax per axis, all finite; the grid starts zeroed.
         mer_render_fluence ACCUMULATES into the grid (mer_fluence_clear zeroes it and the totals), launches on the context stream in the light
         tracer's chunks and returns synchronised; mer_counters_read afterwards reports the walk as it does after mer_render.
-        mer_fluence_read: sums may be NULL (totals only).  mer_context_destroy frees the grids still alive. ---- */
+        mer_fluence_read: sums may be NULL (totals only).  mer_context_destroy frees the grids still alive.
+        A handle of mer_fluence_track_create (below) makes mer_render_fluence deposit along every free flight instead -- the track-length
+        estimator, which also fills cells without extinction; it needs analog distance sampling and loses, on curved rays, the piece of
+        path before the boundary that is shorter than one stepsize. ---- */
 int  mer_fluence_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out);
 int  mer_fluence_clear(mer_context *ctx, mer_fluence f);
 int  mer_fluence_destroy(mer_context *ctx, mer_fluence f);
@@ -453,6 +456,37 @@ int  mer_fluence_read(mer_context *ctx, mer_fluence f, double *sums /* [nz][ny][
         mer_fluence_read refuses a time-resolved handle and mer_fluence_time_read a steady-state one.  sums may be NULL (totals only). ---- */
 int  mer_fluence_time_create(mer_context *ctx, const mer_fluence_time_desc *desc, mer_fluence *out);
 int  mer_fluence_time_read(mer_context *ctx, mer_fluence f, double *sums /* [frames][nz][ny][nx][3] or NULL */, double totals[12]);
+
+/* ---- track-length fluence: a third kind of mer_fluence handle, a steady-state grid with the layout and totals of mer_fluence_create
+        (double[nz][ny][nx][3] raw sums, then 8 totals), filled by the track-length estimator the users of photon-migration codes know.
+        mer_fluence_clear, mer_fluence_destroy, mer_fluence_read, mer_render_fluence and mer_context_destroy take it; mer_fluence_time_read
+        refuses it as it refuses every steady-state grid.  mer_render_fluence picks the kernel by the handle's kind; the other two kinds
+        render exactly as before.
+        The estimator.  The walk is the collision grid's, draw for draw (the deposit draws no sampler number): for one scene, shard and
+        seed the counters, totals[0] (paths), totals[1..3] (escaped) and totals[7] (ended) equal those of a mer_fluence_create handle.
+        Instead of one deposit at the collision, every free flight deposits along the piece of path it flew inside the shape -- from the
+        flight's start to the real collision or to the exit, the whole in-shape chord including any part outside the density grid's box --
+        cut at the faces of the grid's (half-open) cells.  Cell c, crossed between the flight parameters a and b (arc length from the
+        flight's start), receives per channel
+            w_c = T_c * power_c * integral_a^b tau_c(s) / S(s) ds
+        with T the throughput at the flight's start, tau_c the channel's transmittance and S(s) the probability that the sampled distance
+        exceeds s.  This is unbiased for any distance sampling; it is BUILT for the analog cases, where S is one exponential exp(-rho s):
+        a gridded sigma_t (delta tracking: rho = sigma(x), w = T * power * (b - a)), or a homogeneous sigma_t with medium_sampling_weight
+        == 1 and strategy single or manual (rho = the sampling density) or balance with three equal sigma_t (rho = sigma_t).  With
+        Delta_c = sigma_t,c - rho and l = b - a:  w_c = T_c power_c exp(-Delta_c a) (-expm1(-Delta_c l)) / Delta_c, and exactly
+        T_c power_c l when Delta_c == 0.  Where sigma_t is 0 -- a clear cuvette, a void of a density grid, a clear gradient-index medium --
+        the collision grid stays 0 and this one holds power x length.  No refRatioSq, as in the collision grid; max_depth keeps its meaning.
+        The analog requirement.  mer_render_fluence refuses, before any launch and only for a track-length handle, a homogeneous medium
+        with strategy balance and channel-dependent sigma_t, strategy maximum, or medium_sampling_weight != 1 after the default is
+        resolved: their S is no single exponential.
+        Curved rays.  Every eikonal step that passed the inside test deposits along its chord, split at the cell faces, at the arc length
+        the walk has accumulated.  The step that left the shape and the step back after it deposit nothing: the last piece of path
+        before the boundary, shorter than one stepsize, is lost, as it is for the walk itself.
+        totals[8]: [0] paths; [1..3] escaped weight; [4..6] weight x length of the pieces outside the box; [7] ended.
+        sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power holds in expectation under the conditions stated for
+        mer_fluence_create, not per path.  fluence = sums / (paths * cell volume), as for the collision grid.
+        mer_fluence_track_create: the descriptor and the checks of mer_fluence_create, under its own message prefix. ---- */
+int  mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out);
 
 /* ---- leaf entry points for parity tests (host pointers, batched SoA) ------------------------------ */
 /* GridDataSource::lookupFloat (gridvolume.cpp:337-388); out_idx[4*i..] = x1,y1,z1,linear index or -1 */

@@ -28,7 +28,7 @@ SYMBOLS = [
     "mer_multi_create", "mer_multi_destroy", "mer_multi_last_error", "mer_multi_size", "mer_multi_context", "mer_multi_set_option",
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
     "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
-    "mer_fluence_time_create", "mer_fluence_time_read",
+    "mer_fluence_time_create", "mer_fluence_time_read", "mer_fluence_track_create",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -768,6 +768,19 @@ class Context:
         self._fluence_res[h.value] = tuple(d.res)
         return h.value
 
+    def fluence_track_create(self, res, bmin, bmax):
+        """-> handle of a zeroed track-length grid (mer_fluence_track_create): the layout of fluence_create, filled by the track-length
+        estimator.  fluence_clear, fluence_destroy, render_fluence and fluence_read take it like a fluence_create handle."""
+        d = fluence_desc(res, bmin, bmax)
+        try:
+            validate_fluence(d)                            # the same checks, under the entry point's own prefix
+        except MerError as e:
+            raise MerError("mer_fluence_track_create: " + str(e)[len("mer_fluence_create: "):]) from None
+        h = C.c_int32()
+        self._check(self.lib.mer_fluence_track_create(self.h, C.byref(d), C.byref(h)))
+        self._fluence_res[h.value] = tuple(d.res)
+        return h.value
+
     def fluence_time_create(self, res, bmin, bmax, frames, t_min, t_bin):
         """-> handle of a zeroed time-resolved grid: the box of fluence_create, `frames` bins of width t_bin from t_min on in optical path
         length.  fluence_clear, fluence_destroy and render_fluence take it like any other fluence handle."""
@@ -850,12 +863,16 @@ class Context:
         phi = sums / (t[0] * volume * np.float64(d.t_bin)) if t[0] > 0 else np.zeros_like(sums)
         return phi, info
 
-    def fluence(self, scene, res, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
+    def fluence(self, scene, res, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0, estimator="collision"):
         """One fluence map of the scene (integrator = ptracer): (phi float64 [nz][ny][nx][3], info).  phi = sums / (paths x cell volume), per
         unit of the emitters' intensity / power; the box defaults to the bounding box of the medium shape.  info: the totals by name
-        (paths, escaped [3], dropped [3], ended), the raw sums, the box and the cell volume."""
+        (paths, escaped [3], dropped [3], ended), the raw sums, the box, the cell volume and the estimator.
+        estimator: "collision" (one deposit per real collision) or "track" (every free flight deposits along its path, voids included;
+        needs analog distance sampling: mer.h, mer_fluence_track_create)."""
+        if estimator not in ("collision", "track"):
+            raise MerError("fluence: estimator must be \"collision\" or \"track\"")
         bmin, bmax = self._fluence_box(scene, bmin, bmax)
-        h = self.fluence_create(res, bmin, bmax)
+        h = self.fluence_track_create(res, bmin, bmax) if estimator == "track" else self.fluence_create(res, bmin, bmax)
         try:
             self.render_fluence(scene, h, spp_begin, spp_count, seed)
             sums, t = self.fluence_read(h)
@@ -864,7 +881,7 @@ class Context:
         d = fluence_desc(res, bmin, bmax)
         volume = float(np.prod([(np.float64(d.bmax[a]) - np.float64(d.bmin[a])) / d.res[a] for a in range(3)]))
         info = {"paths": t[0], "escaped": t[1:4].copy(), "dropped": t[4:7].copy(), "ended": t[7], "sums": sums,
-                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64), "cell_volume": volume}
+                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64), "cell_volume": volume, "estimator": estimator}
         phi = sums / (t[0] * volume) if t[0] > 0 else np.zeros_like(sums)
         return phi, info
 

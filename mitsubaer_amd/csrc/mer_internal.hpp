@@ -35,13 +35,16 @@ struct EnvMap {
 
 // a fluence grid (mer_fluence_create): one device buffer -- the sums double[nz][ny][nx][3], then the 8 totals.  Its handle shares the volumes' numbering.
 // A time-resolved grid (mer_fluence_time_create, frames > 0) is the second kind of the same handle: the sums double[frames][nz][ny][nx][3], then 12 totals.
+// A track-length grid (mer_fluence_track_create, kind = 1) is the third: the steady-state layout, filled by K_fluence_track (mer_fluence_track.hpp).
 struct Fluence {
     mer_fluence_desc desc;
     double *dev = nullptr;
     uint64_t n_cells = 0;
     int32_t frames = 0;                          // 0: a steady-state grid
     float t_min = 0, t_bin = 0;
+    int32_t kind = 0;                            // 0: deposits at the collisions; 1: a track-length grid (mer_fluence_track_create), steady-state only
     bool timed() const { return frames > 0; }
+    bool track() const { return kind == 1; }
     uint64_t n_keys() const { return n_cells * (uint64_t) (frames > 0 ? frames : 1); }
     double *totals() const { return dev + n_keys() * 3; }
     size_t bytes() const { return (n_keys() * 3 + (frames > 0 ? 12 : 8)) * sizeof(double); }

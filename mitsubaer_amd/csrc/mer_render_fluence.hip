@@ -1,7 +1,8 @@
 // mer_render_fluence.hip -- the fluence grid recorded from light paths: instantiations of K_fluence (mer_fluence.hpp), its host loop (the
 // light tracer's: launches of PT_PATHS_PER_LAUNCH / PT_PATHS_PER_LAUNCH_CURVED paths on the context stream, returned synchronised) and the
 // mer_fluence_* entry points.  A grid is one device allocation: double[nz][ny][nx][3] sums, then the 8 totals; a time-resolved grid
-// (mer_fluence_time_create) is double[frames][nz][ny][nx][3] sums, then 12 totals, and renders with the TIMED instantiations.
+// (mer_fluence_time_create) is double[frames][nz][ny][nx][3] sums, then 12 totals, and renders with the TIMED instantiations.  A track-length
+// grid (mer_fluence_track_create) has the steady-state layout and renders with K_fluence_track (mer_render_fluence_track.hip).
 #include "mer_internal.hpp"
 #include "mer_fluence.hpp"
 
@@ -28,6 +29,9 @@ template <bool TIMED> static FluenceKernel pick_fluence(const mer_scene_desc *sc
     }
     return nullptr;
 }
+
+// mer_render_fluence_track.hip: the same 14 combinations of K_fluence_track, for a handle of mer_fluence_track_create
+FluenceKernel pick_fluence_track(const mer_scene_desc *sc);
 
 static int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d, const std::string &at = "mer_fluence_create: ") {
     uint64_t cells = 1;
@@ -84,7 +88,15 @@ static int launch_fluence(mer_context *ctx, const mer_scene_desc *scene, const m
         shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
         return fail(ctx, "invalid shard");
     if (P.n_point <= 0) return fail(ctx, "ptracer: the scene has no emitter (list entries of kind point, spot or collimated)");
-    const FluenceKernel kernel = F.timed() ? pick_fluence<true>(scene) : pick_fluence<false>(scene);
+    if (F.track() && scene->sigma_mode != MER_SIGMA_GRID) {
+        // the track-length weight is built for ANALOG distance sampling: every free flight drawn from one exponential exp(-rho s)
+        const std::string at = "mer_render_fluence: a track-length grid needs analog distance sampling (one exponential per free flight): ";
+        if (P.medium_sampling_weight != 1.0f) return fail(ctx, at + "medium_sampling_weight must be 1");
+        if (scene->strategy == MER_STRATEGY_MAXIMUM) return fail(ctx, at + "strategy maximum samples the maximum of three exponentials");
+        if (scene->strategy == MER_STRATEGY_BALANCE && !(P.sigT.x == P.sigT.y && P.sigT.y == P.sigT.z))
+            return fail(ctx, at + "strategy balance with a channel-dependent sigma_t samples a mixture of exponentials");
+    }
+    const FluenceKernel kernel = F.track() ? pick_fluence_track(scene) : F.timed() ? pick_fluence<true>(scene) : pick_fluence<false>(scene);
     if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
     // the work ids of the shard, as launch_ptracer lays them out (decode_work)
     P.seed = seed;
@@ -132,6 +144,19 @@ int mer_fluence_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluen
     F.desc = *desc;
     F.n_cells = (uint64_t) desc->res[0] * (uint64_t) desc->res[1] * (uint64_t) desc->res[2];
     return alloc_fluence(ctx, F, "mer_fluence_create", out);
+}
+
+int mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out) {
+    if (!ctx) return 1;
+    (void) hipSetDevice(ctx->device);
+    if (!desc || !out) return fail(ctx, "mer_fluence_track_create: invalid arguments");
+    *out = 0;
+    if (check_fluence_desc(ctx, desc, "mer_fluence_track_create: ")) return 1;
+    Fluence F;
+    F.desc = *desc;
+    F.n_cells = (uint64_t) desc->res[0] * (uint64_t) desc->res[1] * (uint64_t) desc->res[2];
+    F.kind = 1;
+    return alloc_fluence(ctx, F, "mer_fluence_track_create", out);
 }
 
 int mer_fluence_time_create(mer_context *ctx, const mer_fluence_time_desc *desc, mer_fluence *out) {

@@ -1121,12 +1121,13 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
 
 // The fluence grid of a `ptracer` scene: one context (a mer_multi of one device, for the uploads it shares with render()), one grid over the
 // medium shape's bounding box, width x height x spp light paths.
-Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const {
-    return renderFluence(scene, device, res, 0, 0.0f, 0.0f, spp, seed);
+Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed, bool trackLength) const {
+    return renderFluence(scene, device, res, 0, 0.0f, 0.0f, spp, seed, trackLength);
 }
-// frames = 0: the steady-state grid; frames > 0: the time-resolved one
-Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed) const {
+// frames = 0: the steady-state grid (trackLength: the track-length estimator's); frames > 0: the time-resolved one
+Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed, bool trackLength) const {
     if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    if (trackLength && frames > 0) Log_EError("a time-resolved track-length grid does not exist: the track-length estimator fills a steady-state grid");
     mer_scene_desc d;
     flatten(scene, d);
     if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
@@ -1146,7 +1147,7 @@ Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, co
     mer_context *ctx = mer_multi_context(mm, 0);
     auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
     mer_fluence f = 0;
-    if (frames > 0 ? mer_fluence_time_create(ctx, &td, &f) : mer_fluence_create(ctx, &fd, &f)) fail();
+    if (frames > 0 ? mer_fluence_time_create(ctx, &td, &f) : trackLength ? mer_fluence_track_create(ctx, &fd, &f) : mer_fluence_create(ctx, &fd, &f)) fail();
     const mer_shard whole = {0, spp, 1, 0, 1};
     if (mer_render_fluence(ctx, &d, &whole, seed, f)) fail();
     out.sums.resize((size_t) (frames > 0 ? frames : 1) * res[0] * res[1] * res[2] * 3);

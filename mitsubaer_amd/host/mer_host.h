@@ -239,10 +239,12 @@ public:
         /// sums / (paths x cell volume), float32 [nz][ny][nx][3]; time-resolved: sums / (paths x cell volume x tBin), [frames][nz][ny][nx][3]
         std::vector<float> phi() const;
     };
-    Fluence renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed) const;
+    /// trackLength: the track-length estimator (mer_fluence_track_create): every free flight deposits along its path, voids included; the scene's
+    /// distance sampling must be analog (mer.h), anything else is refused
+    Fluence renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed, bool trackLength = false) const;
     /// the time-resolved form (mer_fluence_time_create): every deposit also binned by the optical path length at which it happens.  The window is
-    /// the caller's; the scene's film is not read
-    Fluence renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed) const;
+    /// the caller's; the scene's film is not read.  frames = 0: the steady-state grid.  A time-resolved track-length grid does not exist
+    Fluence renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed, bool trackLength = false) const;
 private:
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
     void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;

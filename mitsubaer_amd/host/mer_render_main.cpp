@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved]] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cstdio>
@@ -13,6 +13,7 @@ int main(int argc, char **argv) {
     int meshSdf = -1;              // --mesh-sdf[=N]: -1 off, 0 = the rif volume's grid, N = nodes on the longest axis of the mesh's box
     int fluenceRes[3] = {0, 0, 0}; bool fluence = false, multi = false;   // --fluence=NX,NY,NZ: the fluence grid of a ptracer scene instead of its film
     bool timeResolved = false;     // --time-resolved: that grid per frame of the film's transient window
+    bool trackLength = false;      // --track-length: that grid from the track-length estimator (mer_fluence_track_create)
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -40,8 +41,9 @@ int main(int argc, char **argv) {
             fluence = true;
         }
         else if (a == "--time-resolved") timeResolved = true;
+        else if (a == "--track-length") trackLength = true;
         else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved]] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -53,11 +55,16 @@ int main(int argc, char **argv) {
                                                          "  the cell centres, so that a gridvolume reading it interpolates between them; the totals are printed\n"
                                                          "  --time-resolved (with --fluence=): the scene's film must have decomposition = transient; every deposit is also binned by its optical path\n"
                                                          "  length into the film's window (minBound, binWidth, ceil((maxBound - minBound) / binWidth) frames); -o names a float32 .npy\n"
-                                                         "  [frames][nz][ny][nx][3] = sums / (paths x cell volume x binWidth); the totals also print the weight outside the window\n"); return 0; }
+                                                         "  [frames][nz][ny][nx][3] = sums / (paths x cell volume x binWidth); the totals also print the weight outside the window\n"
+                                                         "  --track-length (with --fluence=, not with --time-resolved): the track-length estimator: every free flight deposits along its path, cut at\n"
+                                                         "  the cell faces, so that cells without extinction hold their fluence too; the distance sampling must be analog (a gridded sigma_t, or a\n"
+                                                         "  homogeneous one with mediumSamplingWeight 1 and strategy single / manual, or balance with equal sigma_t); `dropped` is weight x length\n"); return 0; }
         else scenePath = a;
     }
     if (fluence && multi) { std::fprintf(stderr, "--fluence runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
     if (timeResolved && !fluence) { std::fprintf(stderr, "--time-resolved needs --fluence=NX,NY,NZ\n"); return 2; }
+    if (trackLength && !fluence) { std::fprintf(stderr, "--track-length needs --fluence=NX,NY,NZ\n"); return 2; }
+    if (trackLength && timeResolved) { std::fprintf(stderr, "--track-length and --time-resolved exclude each other: a time-resolved track-length grid does not exist\n"); return 2; }
     if (timeResolved) {
         if (out == "out.npy") out = "fluence_t.npy";
         if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--time-resolved writes a .npy file ([frames][nz][ny][nx][3]): a VOL holds 1 or 3 channels\n"); return 2; }
@@ -79,7 +86,7 @@ int main(int argc, char **argv) {
         }
         if (fluence) {
             if (out == "out.npy") out = "fluence.vol";
-            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, spp, seed);
+            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, spp, seed, trackLength);
             const std::vector<float> phi = f.phi();
             float lo[3], hi[3];                      // the box of the cell centres
             for (int k = 0; k < 3; k++) { const float half = 0.5f * (f.bmax[k] - f.bmin[k]) / (float) f.res[k]; lo[k] = f.bmin[k] + half; hi[k] = f.bmax[k] - half; }
