@@ -268,6 +268,11 @@ typedef struct { int32_t res[3]; float bmin[3], bmax[3]; } mer_fluence_desc;
 /* a time-resolved fluence grid (mer_fluence_time_create): the same box, and `frames` bins of width t_bin from t_min on in optical path
    length; frame f holds the deposits with floorf((l - t_min) / t_bin) == f (half-open).  reserved must be 0. */
 typedef struct { int32_t res[3]; float bmin[3], bmax[3]; int32_t frames; float t_min, t_bin; int32_t reserved; } mer_fluence_time_desc;
+/* an exitance map (mer_exitance_create): res[0] x res[1] (u x v) cells on every face of the medium shape's boundary -- 6 faces for
+   MER_BOUNDARY_AABB, 1 for MER_BOUNDARY_SPHERE -- and `frames` bins of width t_bin from t_min on in optical path length.  A steady map has
+   frames == 1 and t_bin == 0.  cos_min: the acceptance cone about the outward normal (0 accepts every exit).  reserved must be 0. */
+typedef int32_t mer_exitance;                                 /* handle, > 0, from the context's handle counter */
+typedef struct { int32_t boundary; int32_t res[2]; int32_t frames; float t_min, t_bin, cos_min; int32_t reserved; } mer_exitance_desc;
 
 enum {
     MER_C_PATHS = 0, MER_C_STEPS, MER_C_RIF_EVALS, MER_C_TENTATIVE, MER_C_REAL,
@@ -487,6 +492,58 @@ int  mer_fluence_time_read(mer_context *ctx, mer_fluence f, double *sums /* [fra
         mer_fluence_create, not per path.  fluence = sums / (paths * cell volume), as for the collision grid.
         mer_fluence_track_create: the descriptor and the checks of mer_fluence_create, under its own message prefix. ---- */
 int  mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out);
+
+/* ---- exitance maps: where and when light paths leave the medium.  Replaces a grid of `irradiancemeter` probes on the medium shape
+        (src/sensors/irradiancemeter.cpp, driven by `ptracer`): one accumulator over the whole boundary instead of one probe per render.
+        mer_exitance is its own kind of handle: the mer_fluence_* entry points refuse it as an unknown handle, and the entry points below
+        refuse a fluence handle the same way.
+        The walk.  A light path is exactly the one mer_render_fluence walks for the same scene, shard and seed: work id and sampler key,
+        emitter selection and emitted ray, entry with one depth paid for the null boundary, free flights, phase-function samples, roulette
+        and the bounds on the scatterings and march units of a path.  Recording an exit draws no sampler number, fetches no RIF value and
+        advances no counter: mer_counters_read, totals[0] (paths), totals[1..3] (escaped) and totals[7] (ended) equal those of a
+        mer_fluence_create render.
+        The exit.  With the null boundary and a convex shape a path leaves at most once.  At that moment it records
+          x, d   straight rays: x = the intersection of the last flight with the shape (the flight's start when the path stands on the
+                 boundary heading out), d = the flight's direction.  Curved rays: from the walk's last point inside, x0, along
+                 d = normalize(optical momentum), the shape is hit again (the re-hit of the dielectric boundary, after edge.cpp:45-60):
+                 x = x0 + d t, or x0 when there is no hit.
+          w      T * power per channel: what `escaped` receives.
+          l      the optical path length the time-resolved fluence grid carries (the exterior leg at index 1, then per free flight
+                 integral n ds or t * rif_const, in float32) plus the last flight: its length times rif_const, or its integral n ds on a
+                 curved ray.  The piece between x0 and x is not added: it is shorter than one stepsize, the loss the walk and the
+                 track-length grid document.
+        Acceptance.  c = dot(d, outward normal at x).  With cos_min > 0 an exit with c < cos_min is not binned: its w goes to `rejected`.
+        The cone is measured at the surface in the medium's own index: the index-matched boundary does not refract.
+        Window.  A timed map (t_bin > 0): frame = floorf((l - t_min) / t_bin); outside 0 <= frame < frames, w goes to `late`.  A steady
+        map (frames == 1, t_bin == 0) puts everything into frame 0.
+        Cell, cube (6 faces): the axis and sign of the face by the rule of the boundary normal (the axis on which |x - centre| / half
+        size is largest, first axis on a tie; sign + when x >= centre); face = 2 * axis + (sign > 0); ua = (axis + 1) % 3,
+        va = (axis + 2) % 3; iu = clamp(floor((x[ua] - bmin[ua]) / (bmax[ua] - bmin[ua]) * res_u), 0, res_u - 1), iv the same on va.
+        Clamped, not dropped: the point is on the boundary by construction.
+        Cell, sphere (1 face, equal-area cells): q = (x - c) / |x - c|; iv from (1 + q.z) / 2, iu from atan2(q.y, q.x) / 2 pi wrapped
+        into [0, 1); both clamped.
+        An emitted ray that misses the shape has no exit point: its weight goes to `missed`.
+        The map holds raw float64 sums, double[frames][faces][res_v][res_u][3], at most 2^27 keys; raw sums of disjoint shards add (the
+        caller reduces them).  exitance = sums / (paths * cell area [* t_bin for a timed map]).
+        totals[16]: [0] paths; [1..3] escaped, as the fluence grids have it (the missed weight included); [4..6] missed; [7] ended;
+        [8..10] late; [11..13] rejected; [14] the number of exits binned; [15] 0.  Every escaping path goes to exactly one of sums,
+        missed, rejected (tested first) or late: sum(sums) + missed + rejected + late = escaped per channel, up to float64 summation
+        order, for any medium and not only in expectation.  With medium_sampling_weight < 1 the escaped weight carries no 1 / pdfFailure
+        and overstates the power that leaves, as stated for mer_fluence_create.
+        mer_exitance_create refuses, each with its own message and *out = 0: a boundary that is neither kind; res outside 1 ... 4096;
+        frames outside 1 ... 4096; t_bin negative or not finite, or t_bin == 0 with frames != 1; t_min not finite; cos_min outside
+        0 <= cos_min < 1; reserved != 0; more than 2^27 keys.  The map starts zeroed.
+        mer_render_exitance requires integrator = ptracer and the light tracer's scope unchanged, refuses a scene whose boundary differs
+        from the map's, ACCUMULATES (mer_exitance_clear zeroes the map and the totals), launches in the light tracer's chunks on the context
+        stream and returns synchronised.  mer_exitance_read: sums may be NULL (totals only).  mer_context_destroy frees the maps alive.
+        Out of scope, refused by the light tracer's unchanged checks: dielectric and signed-distance boundaries, sensors other than
+        perspective, area / envmap / constant emitters.  Also not built: several GPUs in one call, angular histograms beyond the one
+        acceptance cone. ---- */
+int  mer_exitance_create(mer_context *ctx, const mer_exitance_desc *desc, mer_exitance *out);
+int  mer_exitance_clear(mer_context *ctx, mer_exitance e);
+int  mer_exitance_destroy(mer_context *ctx, mer_exitance e);
+int  mer_render_exitance(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_exitance e);
+int  mer_exitance_read(mer_context *ctx, mer_exitance e, double *sums /* [frames][faces][res_v][res_u][3] or NULL */, double totals[16]);
 
 /* ---- leaf entry points for parity tests (host pointers, batched SoA) ------------------------------ */
 /* GridDataSource::lookupFloat (gridvolume.cpp:337-388); out_idx[4*i..] = x1,y1,z1,linear index or -1 */

@@ -29,6 +29,7 @@ SYMBOLS = [
     "mer_multi_volume_upload", "mer_multi_volume_build_spline", "mer_multi_volume_destroy", "mer_multi_render", "mer_multi_last_stats",
     "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
     "mer_fluence_time_create", "mer_fluence_time_read", "mer_fluence_track_create",
+    "mer_exitance_create", "mer_exitance_clear", "mer_exitance_destroy", "mer_render_exitance", "mer_exitance_read",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -426,6 +427,52 @@ def validate_fluence_time(desc):
         raise MerError(at + "more than 2^27 cells x frames")
 
 
+class ExitanceDesc(C.Structure):
+    """mer_exitance_desc: res = (res_u, res_v) cells on every face of the medium shape's boundary (6 faces for the cube, 1 for the sphere),
+    `frames` bins of width t_bin from t_min on in optical path length (a steady map: frames 1, t_bin 0) and the acceptance cone cos_min"""
+    _fields_ = [("boundary", C.c_int32), ("res", C.c_int32 * 2), ("frames", C.c_int32), ("t_min", C.c_float), ("t_bin", C.c_float),
+                ("cos_min", C.c_float), ("reserved", C.c_int32)]
+
+
+EXITANCE_TOTALS = ("paths", "escaped", "missed", "ended", "late", "rejected", "binned")     # mer_exitance_read's totals: [0], [1..3], [4..6], [7], [8..10], [11..13], [14]
+
+
+def exitance_desc(boundary, res, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0):
+    d = ExitanceDesc()
+    d.boundary = int(boundary)
+    d.res[:] = [int(v) for v in res]
+    d.frames, d.t_min, d.t_bin, d.cos_min, d.reserved = int(frames), float(t_min), float(t_bin), float(cos_min), 0
+    return d
+
+
+def exitance_faces(boundary):
+    return 1 if boundary == P.BOUNDARY_SPHERE else 6
+
+
+def validate_exitance(desc):
+    """The refusals of mer_exitance_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_exitance_create: "
+    if desc.boundary not in (P.BOUNDARY_AABB, P.BOUNDARY_SPHERE):
+        raise MerError(at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)")
+    for a in range(2):
+        if desc.res[a] < 1 or desc.res[a] > 4096:
+            raise MerError(at + "res must lie in 1 ... 4096 on both axes")
+    if desc.frames < 1 or desc.frames > 4096:
+        raise MerError(at + "frames must lie in 1 ... 4096")
+    if not np.isfinite(desc.t_bin) or desc.t_bin < 0:
+        raise MerError(at + "t_bin must be finite and at least 0")
+    if desc.t_bin == 0 and desc.frames != 1:
+        raise MerError(at + "a steady map (t_bin == 0) has one frame")
+    if not np.isfinite(desc.t_min):
+        raise MerError(at + "t_min must be finite")
+    if not (desc.cos_min >= 0 and desc.cos_min < 1):
+        raise MerError(at + "cos_min must lie in 0 <= cos_min < 1")
+    if desc.reserved != 0:
+        raise MerError(at + "reserved must be 0")
+    if desc.frames * exitance_faces(desc.boundary) * desc.res[0] * desc.res[1] > 1 << 27:
+        raise MerError(at + "more than 2^27 cells x faces x frames")
+
+
 def lib(path=None):
     """The C-ABI library (ctypes).  path = None: libmer.so; Context(check=True) loads libmer_check.so beside it."""
     path = path or LIB_PATH
@@ -498,6 +545,7 @@ class Context:
                 raise MerError(self.lib.mer_last_error(None).decode())
         self.device_id = device_id
         self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids; a time-resolved one: (nx, ny, nz, frames)
+        self._exitance_shape = {}                      # handle -> (frames, faces, res_v, res_u) of the live exitance maps
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -884,6 +932,50 @@ class Context:
                 "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64), "cell_volume": volume, "estimator": estimator}
         phi = sums / (t[0] * volume) if t[0] > 0 else np.zeros_like(sums)
         return phi, info
+
+    # ---- the exitance map recorded from light paths (mer_render_exitance) -----------------------
+    def exitance_create(self, boundary, res, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0):
+        """-> handle of a zeroed map of res = (res_u, res_v) cells on every face of the boundary (P.BOUNDARY_AABB: 6, P.BOUNDARY_SPHERE: 1)"""
+        d = exitance_desc(boundary, res, frames, t_min, t_bin, cos_min)
+        validate_exitance(d)
+        h = C.c_int32()
+        self._check(self.lib.mer_exitance_create(self.h, C.byref(d), C.byref(h)))
+        self._exitance_shape[h.value] = (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0])
+        return h.value
+
+    def exitance_clear(self, handle):
+        self._check(self.lib.mer_exitance_clear(self.h, C.c_int32(handle)))
+
+    def exitance_destroy(self, handle):
+        self._check(self.lib.mer_exitance_destroy(self.h, C.c_int32(handle)))
+        self._exitance_shape.pop(handle, None)
+
+    def render_exitance(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
+        """accumulates the exits of the shard's light paths into the map; returns synchronised"""
+        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
+        self._check(self.lib.mer_render_exitance(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+
+    def exitance_read(self, handle, sums=True):
+        """-> (raw sums float64 [frames][faces][res_v][res_u][3], or None with sums = False; totals float64 [16])"""
+        totals = np.zeros(16, np.float64)
+        out = None
+        if sums:
+            shape = self._exitance_shape.get(handle)
+            if shape is None:
+                raise MerError("mer_exitance_read: unknown exitance handle")
+            out = np.zeros(shape + (3,), np.float64)
+        self._check(self.lib.mer_exitance_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
+        return out, totals
+
+    def exitance(self, scene, res, spp_count, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0, seed=0, spp_begin=0):
+        """One exitance map of the scene (integrator = ptracer) over the boundary of its medium shape: (raw sums float64
+        [frames][faces][res_v][res_u][3], totals float64 [16]: capi.EXITANCE_TOTALS).  exitance = sums / (paths x cell area [x t_bin])."""
+        h = self.exitance_create(scene.boundary, res, frames, t_min, t_bin, cos_min)
+        try:
+            self.render_exitance(scene, h, spp_begin, spp_count, seed)
+            return self.exitance_read(h)
+        finally:
+            self.exitance_destroy(h)
 
     def synchronize(self):
         self._check(self.lib.mer_synchronize(self.h))

@@ -175,6 +175,7 @@ void mer_context_destroy(mer_context *ctx) {
     if (ctx->etab) (void) hipFree(ctx->etab);
     for (auto &kv : ctx->envmaps) if (kv.second.dev) (void) hipFree(kv.second.dev);
     for (auto &kv : ctx->fluences) if (kv.second.dev) (void) hipFree(kv.second.dev);
+    for (auto &kv : ctx->exitances) if (kv.second.dev) (void) hipFree(kv.second.dev);
     if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {
         if (pp.slots) (void) hipFree(pp.slots);

@@ -50,6 +50,17 @@ struct Fluence {
     size_t bytes() const { return (n_keys() * 3 + (frames > 0 ? 12 : 8)) * sizeof(double); }
 };
 
+// an exitance map (mer_exitance_create): one device buffer -- the sums double[frames][faces][res_v][res_u][3], then the 16 totals.  Its handle shares
+// the volumes' numbering; the map is its own kind of handle, not a fluence grid's.
+struct Exitance {
+    mer_exitance_desc desc;
+    double *dev = nullptr;
+    int32_t faces() const { return desc.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
+    uint64_t n_keys() const { return (uint64_t) desc.frames * (uint64_t) faces() * (uint64_t) desc.res[1] * (uint64_t) desc.res[0]; }
+    double *totals() const { return dev + n_keys() * 3; }
+    size_t bytes() const { return (n_keys() * 3 + 16) * sizeof(double); }
+};
+
 #define MER_MAX_PIPES 4
 struct Pipe {
     hipStream_t stream = nullptr, own_stream = nullptr;      // pipeline 0 runs on the context stream
@@ -98,6 +109,7 @@ struct mer_context {
     std::map<int, mer::Volume> volumes;
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
     std::map<int, mer::Fluence> fluences;        // mer_fluence_create (handles from next_handle)
+    std::map<int, mer::Exitance> exitances;      // mer_exitance_create (handles from next_handle)
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
@@ -169,6 +181,8 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
 int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, uint64_t n_film);
 
 // mer_render_fluence.hip: the fluence grid recorded from the same light paths (mer_render_fluence and the mer_fluence_* entry points)
+
+// mer_render_exitance.hip: the exitance map recorded from the same light paths (mer_render_exitance and the mer_exitance_* entry points)
 
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
 // validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.

@@ -1179,6 +1179,62 @@ bool parseFluenceRes(const std::string &value, int res[3]) {
     return (long long) res[0] * res[1] * res[2] <= (1LL << 27);
 }
 
+// The exitance map of a `ptracer` scene: one context (a mer_multi of one device, as renderFluence), one map over the medium shape's boundary
+Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const {
+    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the exitance map is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    mer_scene_desc d;
+    flatten(scene, d);
+    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    Exitance out;
+    mer_exitance_desc ed;
+    ed.boundary = out.boundary = d.boundary;
+    ed.res[0] = out.resU = res[0]; ed.res[1] = out.resV = res[1];
+    ed.frames = out.frames = frames; ed.t_min = out.tMin = tMin; ed.t_bin = out.tBin = tBin; ed.cos_min = out.cosMin = cosMin; ed.reserved = 0;
+    out.faces = d.boundary == MER_BOUNDARY_SPHERE ? 1 : 6;
+    for (int f = 0; f < 6; f++) {
+        const int axis = f / 2, ua = (axis + 1) % 3, va = (axis + 2) % 3;
+        out.cellArea[f] = d.boundary == MER_BOUNDARY_SPHERE ? 4.0 * M_PI * (double) d.sph_radius * (double) d.sph_radius / ((double) res[0] * res[1])
+                                                            : ((double) d.bmax[ua] - (double) d.bmin[ua]) * ((double) d.bmax[va] - (double) d.bmin[va]) / ((double) res[0] * res[1]);
+    }
+    mer_multi *mm = NULL;
+    const int32_t id = device;
+    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
+    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
+    mer_context *ctx = mer_multi_context(mm, 0);
+    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
+    mer_exitance e = 0;
+    if (mer_exitance_create(ctx, &ed, &e)) fail();
+    const mer_shard whole = {0, spp, 1, 0, 1};
+    if (mer_render_exitance(ctx, &d, &whole, seed, e)) fail();
+    out.sums.resize((size_t) frames * out.faces * res[1] * res[0] * 3);
+    if (mer_exitance_read(ctx, e, out.sums.data(), out.totals)) fail();
+    mer_multi_destroy(mm);                     // frees the map with its context
+    return out;
+}
+std::vector<float> Integrator::Exitance::exitance() const {
+    std::vector<float> v(sums.size());
+    const size_t perFace = (size_t) resV * resU * 3;
+    for (size_t i = 0; i < sums.size(); i++) {
+        const int face = (int) ((i / perFace) % (size_t) faces);
+        const double unit = totals[0] * cellArea[face] * (tBin > 0 ? (double) tBin : 1.0);
+        v[i] = (float) (unit > 0 ? sums[i] / unit : 0.0);
+    }
+    return v;
+}
+bool parseExitanceRes(const std::string &value, int res[2]) {
+    size_t p = 0;
+    for (int a = 0; a < 2; a++) {
+        size_t e = a < 1 ? value.find(',', p) : value.size();
+        if (e == std::string::npos || e == p) return false;
+        const std::string tok = value.substr(p, e - p);
+        if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
+        res[a] = std::atoi(tok.c_str());
+        if (res[a] < 1 || res[a] > 4096) return false;
+        p = e + 1;
+    }
+    return true;
+}
+
 std::vector<float> develop(const std::vector<float> &film, int w, int h, int frames) {
     const int ch = frames * 3 + 2;
     std::vector<float> rgb((size_t) frames * w * h * 3);

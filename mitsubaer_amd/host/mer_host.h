@@ -245,6 +245,19 @@ public:
     /// the time-resolved form (mer_fluence_time_create): every deposit also binned by the optical path length at which it happens.  The window is
     /// the caller's; the scene's film is not read.  frames = 0: the steady-state grid.  A time-resolved track-length grid does not exist
     Fluence renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed, bool trackLength = false) const;
+    /// where and when the light paths of a `ptracer` scene leave the medium: a map of resU x resV cells on every face of the medium shape's
+    /// boundary (mer_render_exitance: a grid of the reference's `irradiancemeter` probes on the shape), width x height x spp paths on one device
+    struct Exitance {
+        int boundary = 0, faces = 6, resU = 1, resV = 1;
+        int frames = 1; float tMin = 0.0f, tBin = 0.0f, cosMin = 0.0f;   ///< a steady map: frames 1, tBin 0
+        double cellArea[6];                     ///< per face: cube u-extent x v-extent / (resU x resV); sphere 4 pi r^2 / (resU x resV)
+        std::vector<double> sums;               ///< raw sums [frames][faces][resV][resU][3]
+        double totals[16];                      ///< paths, escaped x 3, missed x 3, ended, late x 3, rejected x 3, exits binned, 0 (mer_exitance_read)
+        /// sums / (paths x cell area [x tBin for a timed map]), float32 [frames][faces][resV][resU][3]
+        std::vector<float> exitance() const;
+    };
+    /// frames = 1 and tBin = 0: the steady map.  The window is the caller's; the scene's film is not read
+    Exitance renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const;
 private:
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
     void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;
@@ -278,6 +291,8 @@ void writePfm(const std::string &path, const float *rgb, int h, int w);
 void writeVol(const std::string &path, const float *data, int nx, int ny, int nz, int channels, const float aabbMin[3], const float aabbMax[3]);
 /// `mer_render --fluence=NX,NY,NZ`: three counts between 1 and 1024, at most 2^27 cells; false for anything else
 bool parseFluenceRes(const std::string &value, int res[3]);
+/// `mer_render --exitance=NU,NV`: two counts between 1 and 4096; false for anything else
+bool parseExitanceRes(const std::string &value, int res[2]);
 /// OpenEXR 2 scan-line file, uncompressed, three float32 channels B, G, R (what HDRFilm::develop writes through OpenEXR,
 /// src/films/hdrfilm.cpp:527; no OpenEXR library is needed for this subset)
 void writeExr(const std::string &path, const float *rgb, int h, int w);

@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cstdio>
@@ -14,6 +14,8 @@ int main(int argc, char **argv) {
     int fluenceRes[3] = {0, 0, 0}; bool fluence = false, multi = false;   // --fluence=NX,NY,NZ: the fluence grid of a ptracer scene instead of its film
     bool timeResolved = false;     // --time-resolved: that grid per frame of the film's transient window
     bool trackLength = false;      // --track-length: that grid from the track-length estimator (mer_fluence_track_create)
+    int exitanceRes[2] = {0, 0}; bool exitance = false;                   // --exitance=NU,NV: the exitance map over the medium shape's boundary instead of the film
+    float acceptCos = 0.0f; bool acceptCosSet = false;                    // --accept-cos=C: the acceptance cone of that map
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -40,10 +42,20 @@ int main(int argc, char **argv) {
             if (!merhost::parseFluenceRes(a.substr(10), fluenceRes)) { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
             fluence = true;
         }
+        else if (a.rfind("--exitance=", 0) == 0) {
+            if (!merhost::parseExitanceRes(a.substr(11), exitanceRes)) { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
+            exitance = true;
+        }
+        else if (a == "--exitance") { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
+        else if (a.rfind("--accept-cos=", 0) == 0) {
+            char *e = NULL; acceptCos = std::strtof(a.c_str() + 13, &e);
+            if (e == a.c_str() + 13 || *e || !(acceptCos >= 0.0f && acceptCos < 1.0f)) { std::fprintf(stderr, "--accept-cos=C expects a cosine with 0 <= C < 1\n"); return 2; }
+            acceptCosSet = true;
+        }
         else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--track-length") trackLength = true;
         else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -58,20 +70,48 @@ int main(int argc, char **argv) {
                                                          "  [frames][nz][ny][nx][3] = sums / (paths x cell volume x binWidth); the totals also print the weight outside the window\n"
                                                          "  --track-length (with --fluence=, not with --time-resolved): the track-length estimator: every free flight deposits along its path, cut at\n"
                                                          "  the cell faces, so that cells without extinction hold their fluence too; the distance sampling must be analog (a gridded sigma_t, or a\n"
-                                                         "  homogeneous one with mediumSamplingWeight 1 and strategy single / manual, or balance with equal sigma_t); `dropped` is weight x length\n"); return 0; }
+                                                         "  homogeneous one with mediumSamplingWeight 1 and strategy single / manual, or balance with equal sigma_t); `dropped` is weight x length\n"
+                                                         "  --exitance=NU,NV: a `ptracer` scene: instead of the film, where the light paths leave the medium: NU x NV cells on every face of the medium\n"
+                                                         "  shape's boundary (cube: 6 faces, sphere: 1 face of equal-area cells), from width x height x spp light paths on one GPU; -o names a float32\n"
+                                                         "  .npy [frames][faces][nv][nu][3] = sums / (paths x cell area [x binWidth]); the 16 totals are printed.  --time-resolved takes the window\n"
+                                                         "  from the film as for --fluence; --accept-cos=C bins only the exits within the cone cos >= C about the outward normal\n"); return 0; }
         else scenePath = a;
     }
+    if (exitance && fluence) { std::fprintf(stderr, "--exitance and --fluence exclude each other: one map per run\n"); return 2; }
+    if (exitance && multi) { std::fprintf(stderr, "--exitance runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
+    if (exitance && trackLength) { std::fprintf(stderr, "--track-length belongs to --fluence=NX,NY,NZ: an exitance map has no track-length form\n"); return 2; }
+    if (acceptCosSet && !exitance) { std::fprintf(stderr, "--accept-cos needs --exitance=NU,NV\n"); return 2; }
+    if (exitance) {
+        if (out == "out.npy") out = "exitance.npy";
+        if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--exitance writes a .npy file ([frames][faces][nv][nu][3])\n"); return 2; }
+    }
     if (fluence && multi) { std::fprintf(stderr, "--fluence runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
-    if (timeResolved && !fluence) { std::fprintf(stderr, "--time-resolved needs --fluence=NX,NY,NZ\n"); return 2; }
+    if (timeResolved && !fluence && !exitance) { std::fprintf(stderr, "--time-resolved needs --fluence=NX,NY,NZ\n"); return 2; }
     if (trackLength && !fluence) { std::fprintf(stderr, "--track-length needs --fluence=NX,NY,NZ\n"); return 2; }
     if (trackLength && timeResolved) { std::fprintf(stderr, "--track-length and --time-resolved exclude each other: a time-resolved track-length grid does not exist\n"); return 2; }
-    if (timeResolved) {
+    if (timeResolved && !exitance) {
         if (out == "out.npy") out = "fluence_t.npy";
         if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--time-resolved writes a .npy file ([frames][nz][ny][nx][3]): a VOL holds 1 or 3 channels\n"); return 2; }
     }
     if (scenePath.empty()) { std::fprintf(stderr, "mer_render: no scene file given\n"); return 2; }
     try {
         auto scene = merhost::loadScene(scenePath, defines);
+        if (exitance) {
+            int frames = 1; float tMin = 0.0f, tBin = 0.0f;
+            if (timeResolved) {
+                const merhost::Film &film = *scene->sensor->film;
+                if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
+                frames = (int) std::ceil((film.maxBound - film.minBound) / film.binWidth); tMin = film.minBound; tBin = film.binWidth;
+            }
+            const merhost::Integrator::Exitance x = scene->integrator->renderExitance(*scene, device, exitanceRes, frames, tMin, tBin, acceptCos, spp, seed);
+            const std::vector<float> m = x.exitance();
+            merhost::writeNpy(out, m.data(), std::vector<int>{x.frames, x.faces, x.resV, x.resU, 3});
+            std::printf("paths %.0f  escaped %.9g %.9g %.9g  missed %.9g %.9g %.9g  ended %.0f  late %.9g %.9g %.9g  rejected %.9g %.9g %.9g  binned %.0f  %.0f\n",
+                        x.totals[0], x.totals[1], x.totals[2], x.totals[3], x.totals[4], x.totals[5], x.totals[6], x.totals[7], x.totals[8], x.totals[9], x.totals[10],
+                        x.totals[11], x.totals[12], x.totals[13], x.totals[14], x.totals[15]);
+            std::printf("wrote %s (%d frames of %d faces of %dx%d cells)\n", out.c_str(), x.frames, x.faces, x.resU, x.resV);
+            return 0;
+        }
         if (fluence && timeResolved) {
             const merhost::Film &film = *scene->sensor->film;
             if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
