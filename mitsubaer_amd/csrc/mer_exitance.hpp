@@ -2,21 +2,17 @@
 // (mer_render_exitance), a grid of the reference's `irradiancemeter` probes (src/sensors/irradiancemeter.cpp, driven by `ptracer`) instead of
 // one probe per render.
 //
-// A light path is exactly the one K_fluence (mer_fluence.hpp) walks for the same scene, shard and seed -- work id and sampler key,
-// emitter_select, emit_ray, the entry into the shape (one depth for the null boundary), the free flights, phase_sample, the roulette,
-// PT_MAX_EVENTS and PT_STEP_BUDGET.  Recording an exit draws no sampler number, fetches no RIF value and advances no counter, so counters,
-// paths, escaped weight and ended paths equal K_fluence's.  At each place where K_fluence sets `escaped = T * power` the lane notes the exit
-// point x, the outward direction d, w = T power and the optical path length l (mer.h, mer_render_exitance, has the estimator in full).
+// A light path is the walk of mer_lightpath.hpp.  Recording an exit draws no sampler number, fetches no RIF value and advances no counter, so
+// counters, paths, escaped weight and ended paths equal K_fluence's.  At each place where K_fluence sets `escaped = T * power` the lane notes
+// the exit point x, the outward direction d, w = T power and the optical path length l (mer.h, mer_render_exitance, has the estimator in full).
 //
 // With the null boundary and a convex shape a path leaves at most once, so a lane keeps its one (key, w) in registers and the wave deposits
-// ONCE, after the event loop, with all 64 lanes converged.  The event loop itself needs no wave-uniform trip count for the deposit; it keeps
-// K_fluence's form so that the walk is the same code.
+// ONCE, after the event loop, with all 64 lanes converged (wave_deposit).  The event loop itself needs no wave-uniform trip count for the
+// deposit; it keeps K_fluence's form.
 #pragma once
-#include "mer_fluence.hpp"          // wave_sum_f64 and, through mer_ptracer.hpp, emit_ray and the bounds PT_* of a light path
+#include "mer_lightpath.hpp"
 
 namespace mer {
-
-enum { CHK_EXITANCE = 34 };         // bounds-check kind of the sums of an exitance map (mer_device.hpp numbers the others from 1, mer_sdf_build.hip has 32, 33)
 
 // the map of one mer_exitance handle on the device: sums = double[frames][faces][res_v][res_u][3], totals = double[16] (mer.h)
 struct ExitanceMap {
@@ -57,118 +53,45 @@ __device__ __forceinline__ uint32_t exitance_cell(const mer_scene_desc &S, const
     return ((uint32_t) (2 * axis + pos) * (uint32_t) M.res_v + iv) * (uint32_t) M.res_u + iu;
 }
 
-// Every lane of the wave calls this together, once per path (dep = the lane has an exit w for `key`): the ballot / shuffle merge of
-// fluence_deposit (mer_fluence.hpp) over the map's keys.  Measured against one lane, three atomics (the exitance map; 4.2 M paths):
-// 45 x the speed when a collimated beam through a clear cube puts every exit into one cell (3.3 against 151 ms), 4.5 x in a scattering medium
-// (sigma_s 2) on a 64 x 64 map, 3.6 x on 4 x 4: the beam's cell still takes most exits of a wave.  The merge stays; the other form is deleted.
-__device__ __forceinline__ void exitance_deposit(const ExitanceMap &M, bool dep, uint32_t key, f3 w) {
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(dep);
-    while (todo) {
-        const int leader = __ffsll((long long) todo) - 1;
-        const uint32_t lk = (uint32_t) __shfl((int) key, leader, 64);
-        const bool same = dep && key == lk;
-        const unsigned long long m = __ballot(same);
-        double a = same ? (double) w.x : 0.0, b = same ? (double) w.y : 0.0, c = same ? (double) w.z : 0.0;
-        if (m & (m - 1ULL)) { a = wave_sum_f64(a); b = wave_sum_f64(b); c = wave_sum_f64(c); }
-        if (lane == leader) {
-            double *dst = M.sums + MER_CHK(M.chk, CHK_EXITANCE, (uint64_t) lk * 3u, M.n_keys() * 3u - 2u);
-            atomicAdd(dst, a); atomicAdd(dst + 1, b); atomicAdd(dst + 2, c);
-        }
-        todo &= ~m;
-    }
-}
-
-// K_exitance: light path j = work id `first + j` of the shard, as K_fluence has it
+// K_exitance
 template <bool CURVED, int RIF, int STEPPER, int SIGMA>
 __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, const ExitanceMap M, uint64_t first, uint32_t count) {
     const mer_scene_desc &S = P.sc;
-    const uint32_t j = blockIdx.x * PT_BLOCK + threadIdx.x;
     LaneCounters C; C.clear();
-    int x = 0, y = 0; uint32_t sample = 0;
-    const bool live = j < count && decode_work(P, first + j, x, y, sample);        // a work id of a partial tile may fall outside the image
-    Rng rng; rng.seed(P.seed, live ? (uint32_t) (y * S.width + x) : 0u, sample);
-    const int maxDepth = S.max_depth;
-    f3 ps(0, 0, 0), dcur(0, 0, 1), power(0, 0, 0), T(1, 1, 1);
-    int depth = 1;
-    int alive = 0;                                           // int: a flag that lives across the event loop (compiler note 1)
-    bool entering = false;                                   // the next segment starts on the boundary (ray.mint = Epsilon)
+    LightPath<CURVED, SIGMA> lp;
     f3 escaped(0, 0, 0);                                     // a path escapes once
     int exited = 0, miss = 0;                                // ... through the boundary at xe heading de after the path length plen, or without meeting the shape
     f3 xe(0, 0, 0), de(0, 0, 1);
     uint32_t ended = 0;
     float plen = 0.0f;                                       // the optical path length, accumulated in float32 as K_fluence does for a time-resolved grid
-    // Russian roulette at the end of every loop trip of process() (particleproc.cpp:258-267): q = min(max throughput, 0.95), no eta^2
-    auto roulette = [&]() -> bool {
-        if (depth++ >= S.rr_depth) {
-            const float q = fminf(max3(T), 0.95f);
-            if (rng.next1D() >= q) return false;
-            T = T / q;
-        }
-        return true;
-    };
-    if (live) {
-        C.paths++;
-        // ---- emission (Scene::sampleEmitterRay), as K_ptracer
-        float pk; const int k = emitter_select(P.points, P.n_point, rng, 3, pk);
-        power = emit_ray(P, k, rng, ps, dcur);
-        alive = !is_zero(power);
-        if (alive && !inside_shape(S, ps)) {
-            // an emitter outside the shape: the ray meets the null boundary (a surface vertex: one depth) or nothing
-            alive = 0;
-            if (depth <= maxDepth || maxDepth < 0) {
-                const float tIn = intersect_shape(S, ps, dcur, 0.0f, MER_INF);
-                if (tIn >= 0) { plen += tIn; ps = ps + dcur * tIn; entering = true; alive = roulette(); }      // the exterior leg: index 1
-                else { escaped = power; miss = 1; }          // the emitted ray misses the shape: no exit point
-            }
-        }
-    }
+    int x, y; float tIn;
+    const int how = lp.decode(P, C, first, count, x, y) ? lp.emit(P, tIn) : LP_DEAD;
+    if (how == LP_ENTERED) plen += tIn;
+    else if (how == LP_MISSED) { escaped = lp.power; miss = 1; }      // the emitted ray misses the shape: no exit point
 
     Walk<CURVED, RIF, STEPPER, SIGMA> W;
     for (int event = 0; event < PT_MAX_EVENTS; ++event) {
-        if (!__ballot(alive != 0)) break;                    // wave-uniform, as K_fluence: the wave leaves when its last path has ended
-        if (alive) {
-            alive = 0;
-            if (!is_zero(T) && (depth <= maxDepth || maxDepth < 0)) {
-                // ---- free flight (Medium::sampleDistance over [0, its.t]; curved: to the collision or the boundary)
-                float itsT = 0.0f;
-                if (!CURVED) itsT = intersect_shape(S, ps, dcur, entering ? MER_EPSILON : 0.0f, MER_INF);
-                entering = false;
-                if (!(itsT >= 0)) { escaped = T * power; exited = 1; xe = ps; de = dcur; }      // on the boundary, heading out
+        if (!__ballot(lp.alive != 0)) break;                 // wave-uniform: the wave leaves when its last path has ended
+        if (lp.alive) {
+            lp.alive = 0;
+            if (lp.can_fly()) {
+                const float itsT = lp.boundary_distance(S);
+                if (!(itsT >= 0)) { escaped = lp.T * lp.power; exited = 1; xe = lp.ps; de = lp.dcur; }      // on the boundary, heading out
                 else {
-                    C.segments++;
-                    W.t = 0; W.tmin = 0; W.tmax = 0; W.n0 = 1; W.rem = 0; W.steps_left = 0; W.seg_inf = 0; W.sdens = 0; W.backstep = 0; W.hprev = 0; W.cc.reset();
-                    int ev = W.begin(P, rng, C, K_FREE, ps, dcur, itsT);
                     float sigma = 0.0f;
-                    for (;;) {
-                        if (ev == EV_NONE) { if (C.marched >= PT_STEP_BUDGET) { ev = EV_GATE_FAIL; break; } ev = W.advance(P, rng, C); }
-                        else if (ev == EV_ARRIVED) ev = W.on_arrived(P, rng, C, sigma);
-                        else if (ev == EV_EXITED) ev = EV_FAIL;
-                        else break;
-                    }
+                    const int ev = lp.run_flight(P, C, W, lp.begin_flight(P, C, W, itsT), sigma);
                     if (ev == EV_REAL) {
                         MRec m;
-                        finish_free_flight(P, C, W, true, sigma, m);
-                        if (SIGMA == MER_SIGMA_HOMOGENEOUS && m.p.x == ps.x && m.p.y == ps.y && m.p.z == ps.z) ended++;       // no forward progress
+                        if (!lp.collide(P, C, W, sigma, m)) ended++;
                         else {
-                            C.real++;
                             plen += CURVED ? m.opticalLength : m.t * S.rif_const;
-                            T = T * (m.sigmaS * m.transmittance / m.pdfSuccess);
-                            const f3 wi = CURVED ? normalize(-m.d) : -W.v;
-                            ps = m.p;
-                            // ---- phase-function sampling, then the roulette
-                            const float p2x = rng.next1D(), p2y = rng.next1D();
-                            f3 wo; float phasePdf;
-                            const float pw = phase_sample(S.phase, S.g, wi, p2x, p2y, wo, phasePdf);
-                            T = T * pw;
-                            dcur = wo;
-                            alive = roulette();
+                            lp.scatter(S, lp.arrive(W, m));
                         }
-                    } else if (ev == EV_GATE_FAIL) ended++;  // the step budget ran out, or the start gate of a B-spline field refused the point
+                    } else if (ev == EV_GATE_FAIL) ended++;
                     else {
                         // the path left the convex shape.  The walk's own state is read as it stands: finish_free_flight(..., false, ...)
                         // would fetch the RIF on a curved ray and count it
-                        escaped = T * power; exited = 1;
+                        escaped = lp.T * lp.power; exited = 1;
                         if (CURVED) {
                             // W.pos() is the last point inside; the shape is met again along the momentum (the re-hit of the dielectric
                             // boundary, mer_wavefront.hpp).  The piece x0 -> x, shorter than one stepsize, adds nothing to the path length.
@@ -177,13 +100,13 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
                             const float t = intersect_shape(S, x0, de, 0.0f, MER_INF);
                             xe = t >= 0 ? x0 + de * t : x0;
                             plen += W.opt;
-                        } else { xe = ps + dcur * itsT; de = dcur; plen += itsT * S.rif_const; }
+                        } else { xe = lp.ps + lp.dcur * itsT; de = lp.dcur; plen += itsT * S.rif_const; }
                     }
                 }
             }
         }
     }
-    if (alive) ended++;                                      // PT_MAX_EVENTS
+    if (lp.alive) ended++;                                   // PT_MAX_EVENTS
 
     // ---- the one deposit of the path: cone (tested first), window, cell.  Every lane of the wave gets here.
     double rejected[3] = {0.0, 0.0, 0.0}, late[3] = {0.0, 0.0, 0.0}, missed[3] = {0.0, 0.0, 0.0};
@@ -200,23 +123,18 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
         }
         if (dep) key += exitance_cell(S, M, xe);
     }
-    exitance_deposit(M, dep, key, escaped);
+    wave_deposit(M.sums, M.chk, CHK_EXITANCE, M.n_keys(), dep, key, escaped);
 
     // totals and counters: one wave-aggregated flush each
     const double tot[15] = {(double) wave_sum(C.paths), wave_sum_f64((double) escaped.x), wave_sum_f64((double) escaped.y), wave_sum_f64((double) escaped.z),
                             wave_sum_f64(missed[0]), wave_sum_f64(missed[1]), wave_sum_f64(missed[2]), (double) wave_sum(ended),
                             wave_sum_f64(late[0]), wave_sum_f64(late[1]), wave_sum_f64(late[2]),
                             wave_sum_f64(rejected[0]), wave_sum_f64(rejected[1]), wave_sum_f64(rejected[2]), (double) wave_sum(dep ? 1u : 0u)};
-    const uint32_t sums[8] = {wave_sum(C.paths), wave_sum(C.steps), wave_sum(C.rif_evals), wave_sum(C.tentative), wave_sum(C.real), wave_sum(C.segments),
-                              wave_sum(C.nee), wave_sum(C.marched)};
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int q = 0; q < 15; q++) if (tot[q] != 0.0) atomicAdd(M.totals + q, tot[q]);
-        unsigned long long *dst = P.counters + (size_t) (blockIdx.x % MER_COUNTER_REPLICAS) * MER_C_COUNT;
-#pragma unroll
-        for (int q = 0; q < 7; q++) if (sums[q]) atomicAdd(dst + q, (unsigned long long) sums[q]);
-        if (sums[7]) atomicAdd(dst + MER_C_ACTIVE_LANES, (unsigned long long) sums[7]);
     }
+    flush_counters(P, C);
 }
 
 }  // namespace mer

@@ -1,7 +1,5 @@
-// mer_fluence_track.hpp -- the track-length estimator of the fluence grid (a handle of mer_fluence_track_create): the light path of K_fluence
-// (mer_fluence.hpp), draw for draw -- work id and sampler key, emitter_select, emit_ray, the null-boundary entry, the free flights through
-// Walk::begin / advance / on_arrived and finish_free_flight, phase_sample, the roulette, PT_MAX_EVENTS and PT_STEP_BUDGET -- but instead of one
-// deposit at the real collision every free flight deposits along the piece of path it flew inside the shape, cut at the faces of the grid's
+// mer_fluence_track.hpp -- the track-length estimator of the fluence grid (a handle of mer_fluence_track_create): the light path of
+// mer_lightpath.hpp, as K_fluence (mer_fluence.hpp) walks it, but instead of one deposit at the real collision every free flight deposits along the piece of path it flew inside the shape, cut at the faces of the grid's
 // cells.  Cell c, crossed between the flight parameters a and b (arc length from the flight's start), receives per channel
 //     w_c = T_c power_c  integral_a^b tau_c(s) / S(s) ds,         S(s) = the probability that the sampled distance exceeds s,
 // which is unbiased for any distance sampling (E[integral_0^min(t, L) f / S] = integral_0^L f) and is built here for S = exp(-rho s):
@@ -12,14 +10,14 @@
 // Pieces outside the box add their w to the `dropped` total (weight x length).
 //
 // One lane runs one path and the event loop is wave-uniform, as in K_fluence.  Straight rays: the resolved flight [0, m.t] or [0, itsT] is
-// walked cell by cell (TrackDDA) in a wave-uniform loop, one piece per lane per trip, and every trip ends in fluence_deposit<false>, which
+// walked cell by cell (TrackDDA) in a wave-uniform loop, one piece per lane per trip, and every trip ends in wave_deposit, which
 // merges the pieces of equal cells over the wave -- a collimated beam keeps all 64 lanes in one column in lockstep.  Curved rays: the stepping
 // loop itself is wave-uniform; a step that passed the inside test deposits along its chord W.p(before) -> W.p(after) at the arc length W.dist
 // (the step that left the shape and the step back after it deposit nothing, so the last piece before the boundary, shorter than one step, is
 // lost as it is for the walk).  A lane keeps a run (cell, summed w) in registers while its chords stay in one cell and flushes it when the
 // cell changes or the flight ends: atomics scale with the cells a path crosses, not with its steps.
 #pragma once
-#include "mer_fluence.hpp"          // FluenceGrid, fluence_cell, fluence_deposit; the walk of K_fluence
+#include "mer_fluence.hpp"          // FluenceGrid, fluence_cell
 
 namespace mer {
 
@@ -91,60 +89,27 @@ struct TrackDDA {
     }
 };
 
-// Every lane of the wave calls this together: fluence_deposit<false> merges the pieces of equal cells over the wave before the float64 atomics.
-// Measured against one lane, three atomics per piece (the track-length grid): 6.6 x the paths/s on the grey laser scene at 8^3, 4.3 x
-// at 32^3, 3.2 x at 128^3 -- spread-out flights still share cells along the beam -- and 1.1 x in the acoustic field, where the walk dominates.
-__device__ __forceinline__ void track_deposit(const FluenceGrid &G, bool dep, uint32_t cell, f3 w) { fluence_deposit<false>(G, dep, cell, w); }
-
-// K_fluence_track: light path j = work id `first + j` of the shard, as K_fluence has it
+// K_fluence_track.  Every deposit is a wave_deposit over the steady-state grid's cells.
 template <bool CURVED, int RIF, int STEPPER, int SIGMA>
 __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P, const FluenceGrid G, uint64_t first, uint32_t count) {
     constexpr bool HOMOG = SIGMA == MER_SIGMA_HOMOGENEOUS;
     const mer_scene_desc &S = P.sc;
-    const uint32_t j = blockIdx.x * PT_BLOCK + threadIdx.x;
     LaneCounters C; C.clear();
-    int x = 0, y = 0; uint32_t sample = 0;
-    const bool live = j < count && decode_work(P, first + j, x, y, sample);
-    Rng rng; rng.seed(P.seed, live ? (uint32_t) (y * S.width + x) : 0u, sample);
-    const int maxDepth = S.max_depth;
-    f3 ps(0, 0, 0), dcur(0, 0, 1), power(0, 0, 0), T(1, 1, 1);
-    int depth = 1;
-    int alive = 0;
-    bool entering = false;
+    LightPath<CURVED, SIGMA> lp;
     f3 escaped(0, 0, 0);
     double dropped[3] = {0.0, 0.0, 0.0};                     // weight x length of the pieces outside the box
     uint32_t ended = 0;
-    auto roulette = [&]() -> bool {
-        if (depth++ >= S.rr_depth) {
-            const float q = fminf(max3(T), 0.95f);
-            if (rng.next1D() >= q) return false;
-            T = T / q;
-        }
-        return true;
-    };
-    if (live) {
-        C.paths++;
-        float pk; const int k = emitter_select(P.points, P.n_point, rng, 3, pk);
-        power = emit_ray(P, k, rng, ps, dcur);
-        alive = !is_zero(power);
-        if (alive && !inside_shape(S, ps)) {
-            alive = 0;
-            if (depth <= maxDepth || maxDepth < 0) {
-                const float tIn = intersect_shape(S, ps, dcur, 0.0f, MER_INF);
-                if (tIn >= 0) { ps = ps + dcur * tIn; entering = true; alive = roulette(); }
-                else escaped = power;
-            }
-        }
-    }
+    int x, y; float tIn;
+    if (lp.decode(P, C, first, count, x, y) && lp.emit(P, tIn) == LP_MISSED) escaped = lp.power;
 
     Walk<CURVED, RIF, STEPPER, SIGMA> W;
     TrackDDA D;
     uint32_t run_cell = 0; f3 run_w(0, 0, 0); int run_on = 0;            // CURVED: the lane's run of chords in one cell
     for (int event = 0; event < PT_MAX_EVENTS; ++event) {
-        if (!__ballot(alive != 0)) break;
+        if (!__ballot(lp.alive != 0)) break;
         int ev = EV_FAIL, flight = 0;
         float itsT = 0.0f, sigma = 0.0f;
-        const f3 fo = ps, fd = dcur, fT = T * power;          // the flight's start, direction and T power
+        const f3 fo = lp.ps, fd = lp.dcur, fT = lp.T * lp.power;          // the flight's start, direction and T power
         f3 delta(0, 0, 0);
         auto drop = [&](float a, float l) {
             if (l > 0.0f) {
@@ -152,22 +117,19 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                 dropped[0] += (double) w.x; dropped[1] += (double) w.y; dropped[2] += (double) w.z;
             }
         };
-        if (alive) {
-            alive = 0;
-            if (!is_zero(T) && (depth <= maxDepth || maxDepth < 0)) {
-                if (!CURVED) itsT = intersect_shape(S, ps, dcur, entering ? MER_EPSILON : 0.0f, MER_INF);
-                entering = false;
+        if (lp.alive) {
+            lp.alive = 0;
+            if (lp.can_fly()) {
+                itsT = lp.boundary_distance(S);
                 if (!(itsT >= 0)) escaped = fT;
                 else {
-                    C.segments++;
-                    W.t = 0; W.tmin = 0; W.tmax = 0; W.n0 = 1; W.rem = 0; W.steps_left = 0; W.seg_inf = 0; W.sdens = 0; W.backstep = 0; W.hprev = 0; W.cc.reset();
-                    ev = W.begin(P, rng, C, K_FREE, ps, dcur, itsT);
+                    ev = lp.begin_flight(P, C, W, itsT);
                     flight = 1;
                     if (HOMOG) delta = f3(P.sigT.x - W.sdens, P.sigT.y - W.sdens, P.sigT.z - W.sdens);       // rho = the density the flight was drawn with
                 }
             }
         }
-        // ---- the free flight: K_fluence's transitions, one per trip
+        // ---- the free flight.  Curved rays: the transitions of LightPath::run_flight, one per trip of a wave-uniform loop
         if (CURVED) {
             int go = flight && (ev == EV_NONE || ev == EV_ARRIVED || ev == EV_EXITED);
             uint32_t pc = 0; bool pin = false;               // the cell of W.p
@@ -181,7 +143,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                         else {
                             const f3 p0 = W.p; const int bs0 = W.backstep;
                             a0 = W.dist; h = W.steps_left > 0 ? P.sc.stepsize : W.rem;
-                            ev = W.advance(P, rng, C);
+                            ev = W.advance(P, lp.rng, C);
                             uint32_t nc; const bool nin = fluence_cell(G, W.p, nc);
                             if (!bs0 && !W.backstep && h > 0.0f) {             // the step passed the inside test
                                 if (pin && nin && pc == nc) { mode = 1; c = pc; pa = a0; pl = h; }
@@ -189,7 +151,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                             }
                             pc = nc; pin = nin;
                         }
-                    } else if (ev == EV_ARRIVED) ev = W.on_arrived(P, rng, C, sigma);
+                    } else if (ev == EV_ARRIVED) ev = W.on_arrived(P, lp.rng, C, sigma);
                     else ev = EV_FAIL;                       // EV_EXITED
                     go = ev == EV_NONE || ev == EV_ARRIVED || ev == EV_EXITED;
                 }
@@ -203,46 +165,29 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                     }
                     if (have) w = track_weight<HOMOG>(fT, delta, pa, pl);
                     const bool flush = have && run_on && c != run_cell;
-                    track_deposit(G, flush, run_cell, run_w);
+                    wave_deposit(G.sums, G.chk, CHK_FLUENCE, G.n_cells, flush, run_cell, run_w);
                     if (have) {
                         if (flush || !run_on) { run_cell = c; run_w = w; run_on = 1; }
                         else run_w = run_w + w;
                     }
                 }
             }
-        } else if (flight) {
-            for (;;) {
-                if (ev == EV_NONE) { if (C.marched >= PT_STEP_BUDGET) { ev = EV_GATE_FAIL; break; } ev = W.advance(P, rng, C); }
-                else if (ev == EV_ARRIVED) ev = W.on_arrived(P, rng, C, sigma);
-                else if (ev == EV_EXITED) ev = EV_FAIL;
-                else break;
-            }
-        }
+        } else if (flight) ev = lp.run_flight(P, C, W, ev, sigma);
         float fL = 0.0f;                                     // straight: the length flown, [0, m.t] or [0, itsT]
         if (flight) {
             if (ev == EV_REAL) {
                 MRec m;
-                finish_free_flight(P, C, W, true, sigma, m);
-                if (HOMOG && m.p.x == ps.x && m.p.y == ps.y && m.p.z == ps.z) ended++;
+                if (!lp.collide(P, C, W, sigma, m)) ended++;
                 else {
-                    C.real++;
                     fL = m.t;
-                    T = T * (m.sigmaS * m.transmittance / m.pdfSuccess);
-                    const f3 wi = CURVED ? normalize(-m.d) : -W.v;
-                    ps = m.p;
-                    const float p2x = rng.next1D(), p2y = rng.next1D();
-                    f3 wo; float phasePdf;
-                    const float pw = phase_sample(S.phase, S.g, wi, p2x, p2y, wo, phasePdf);
-                    T = T * pw;
-                    dcur = wo;
-                    alive = roulette();
+                    lp.scatter(S, lp.arrive(W, m));
                 }
             } else if (ev == EV_GATE_FAIL) ended++;
             else { escaped = fT; fL = itsT; }
         }
         // ---- the deposits
         if (CURVED) {
-            track_deposit(G, run_on != 0, run_cell, run_w);  // the flight ended: flush the run
+            wave_deposit(G.sums, G.chk, CHK_FLUENCE, G.n_cells, run_on != 0, run_cell, run_w);      // the flight ended: flush the run
             run_on = 0;
         } else {
             int pend = 0;
@@ -256,24 +201,19 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                     have = l > 0.0f;
                     if (have) w = track_weight<HOMOG>(fT, delta, a, l);
                 }
-                track_deposit(G, have, c, w);
+                wave_deposit(G.sums, G.chk, CHK_FLUENCE, G.n_cells, have, c, w);
             }
         }
     }
-    if (alive) ended++;                                      // PT_MAX_EVENTS
+    if (lp.alive) ended++;                                   // PT_MAX_EVENTS
 
     const double tot[8] = {(double) wave_sum(C.paths), wave_sum_f64((double) escaped.x), wave_sum_f64((double) escaped.y), wave_sum_f64((double) escaped.z),
                            wave_sum_f64(dropped[0]), wave_sum_f64(dropped[1]), wave_sum_f64(dropped[2]), (double) wave_sum(ended)};
-    const uint32_t sums[8] = {wave_sum(C.paths), wave_sum(C.steps), wave_sum(C.rif_evals), wave_sum(C.tentative), wave_sum(C.real), wave_sum(C.segments),
-                              wave_sum(C.nee), wave_sum(C.marched)};
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int q = 0; q < 8; q++) if (tot[q] != 0.0) atomicAdd(G.totals + q, tot[q]);
-        unsigned long long *dst = P.counters + (size_t) (blockIdx.x % MER_COUNTER_REPLICAS) * MER_C_COUNT;
-#pragma unroll
-        for (int q = 0; q < 7; q++) if (sums[q]) atomicAdd(dst + q, (unsigned long long) sums[q]);
-        if (sums[7]) atomicAdd(dst + MER_C_ACTIVE_LANES, (unsigned long long) sums[7]);
     }
+    flush_counters(P, C);
 }
 
 }  // namespace mer

@@ -1,67 +1,21 @@
-// mer_render_ptracer.hip -- the light tracer (integrator = MER_INTEGRATOR_PTRACER): instantiations of K_ptracer (mer_ptracer.hpp), its host
-// loop, and the two leaf entry points of the sensor connection.  The light paths of a shard are the (pixel, sample index) pairs K_gen
-// would enumerate, launched PT_PATHS_PER_LAUNCH (curved rays: PT_PATHS_PER_LAUNCH_CURVED) at a time on the context stream: no launch runs long, and the film is the only output.
-#include "mer_internal.hpp"
+// mer_render_ptracer.hip -- the light tracer (integrator = MER_INTEGRATOR_PTRACER): instantiations of K_ptracer (mer_ptracer.hpp), its launch
+// (launch_light_paths, mer_lightpath_host.hpp: the film is the only output), and the two leaf entry points of the sensor connection.
+#include "mer_lightpath_host.hpp"
 #include "mer_ptracer.hpp"
 
 namespace mer {
 
-typedef void (*PtracerKernel)(const Params, uint64_t, uint32_t);
-
-template <bool CURVED, int RIF, int STEPPER> static PtracerKernel pick_sigma(int sigma) {
-    return sigma == MER_SIGMA_GRID ? ptracer_kernel<CURVED, RIF, STEPPER, MER_SIGMA_GRID> : ptracer_kernel<CURVED, RIF, STEPPER, MER_SIGMA_HOMOGENEOUS>;
-}
-template <int RIF> static PtracerKernel pick_curved(int stepper, int sigma) {
-    if (stepper == MER_STEP_VERLET) return pick_sigma<true, RIF, MER_STEP_VERLET>(sigma);
-    if (stepper == MER_STEP_RK4) return pick_sigma<true, RIF, MER_STEP_RK4>(sigma);
-    return nullptr;
-}
-// a dense trilinear RIF is read with global loads whatever its size (the buffer-load fetch kind is a wavefront-kernel optimisation)
-static PtracerKernel pick_ptracer(const mer_scene_desc *sc) {
-    const int sigma = sc->sigma_mode == MER_SIGMA_GRID ? MER_SIGMA_GRID : MER_SIGMA_HOMOGENEOUS;
-    switch (sc->rif_mode) {
-    case MER_RIF_CONST: return pick_sigma<false, MER_RIF_TRILINEAR, MER_STEP_VERLET>(sigma);
-    case MER_RIF_TRILINEAR: return pick_curved<MER_RIF_TRILINEAR>(sc->stepper, sigma);
-    case MER_RIF_BSPLINE3: return pick_curved<MER_RIF_BSPLINE3>(sc->stepper, sigma);
-    case MER_RIF_ACOUSTIC: return pick_curved<RIFK_ACOUSTIC>(sc->stepper, sigma);
-    }
-    return nullptr;
-}
+struct PtracerFamily {
+    typedef void (*Kernel)(const Params, uint64_t, uint32_t);
+    template <bool CURVED, int RIF, int STEPPER, int SIGMA> static Kernel get() { return ptracer_kernel<CURVED, RIF, STEPPER, SIGMA>; }
+};
 
 int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, uint64_t n_film) {
     Params P;
     if (make_params(ctx, scene, P, false)) return 1;
     if (scene->integrator != MER_INTEGRATOR_PTRACER) return fail(ctx, "launch_ptracer: the scene's integrator is not ptracer");
-    if (!shard || shard->spp_count < 0 || shard->spp_stride <= 0 || shard->tile_count <= 0 || shard->tile_rank < 0 ||
-        shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
-        return fail(ctx, "invalid shard");
-    if (P.n_point <= 0) return fail(ctx, "ptracer: the scene has no emitter (list entries of kind point, spot or collimated)");
-    const PtracerKernel kernel = pick_ptracer(scene);
-    if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
-    // the work ids of the shard, as launch_render lays them out for K_gen (decode_work)
-    P.seed = seed;
-    P.spp_begin = shard->spp_begin; P.spp_count = shard->spp_count; P.spp_stride = shard->spp_stride;
-    P.tile_rank = shard->tile_rank; P.tile_count = shard->tile_count;
-    P.tiles_x = (scene->width + MER_TILE - 1) / MER_TILE; P.tiles_y = (scene->height + MER_TILE - 1) / MER_TILE;
-    P.tile_skew = tile_skew_for(P.tiles_x, shard->tile_count, (int) ctx->opt.tile_deal);
-    const int ntiles = P.tiles_x * P.tiles_y;
-    P.ntiles_mine = (ntiles - shard->tile_rank + shard->tile_count - 1) / shard->tile_count;
-    P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) shard->spp_count;
-    P.film = film_dev; P.path_out = nullptr; P.n_film = n_film; P.n_path_out = 0;
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (P.total_work == 0) return 0;
-    HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    const uint64_t chunk = scene->rif_mode == MER_RIF_CONST ? PT_PATHS_PER_LAUNCH : PT_PATHS_PER_LAUNCH_CURVED;
-    for (uint64_t first = 0; first < P.total_work; first += chunk) {
-        const uint32_t count = (uint32_t) std::min<uint64_t>(chunk, P.total_work - first);
-        hipLaunchKernelGGL(kernel, dim3((count + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, ctx->stream, P, first, count);
-        HIP_CHECK(ctx, hipGetLastError());
-    }
-    HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    ctx->timed = true;
-    HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));                  // mer_render returns synchronised, as the wavefront loop does
-    ctx->last_event_ms = 0; ctx->last_march_ms = 0; ctx->last_passes = 0; ctx->last_pipes = 1;
-    return 0;
+    if (check_light_paths(ctx, P, shard)) return 1;
+    return launch_light_paths(ctx, scene, P, shard, seed, film_dev, n_film, pick_light_kernel<PtracerFamily>(scene));
 }
 
 // the kernels of the two leaf entry points (here, not in mer_ptracer.hpp: a second translation unit includes that header)
