@@ -421,11 +421,18 @@ int  mer_counters_reset(mer_context *ctx);
         The grid holds raw float64 sums, double[nz][ny][nx][3], added with float64 atomics.  fluence = sums / (paths * cell volume), per
         unit of whatever the emitter's intensity / power is in; sigma_a * fluence is the absorbed power density.  Raw sums of disjoint
         shards add (several GPUs: one grid per context, added by the caller).
-        totals[8], kept beside the grid: [0] paths started; [1..3] escaped weight, T * power when the path leaves the shape or the emitted
-        ray misses it; [4..6] dropped deposit weight; [7] paths ended by a budget, a failed start gate (B-spline field) or no forward
-        progress.  sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power in expectation when every free flight is drawn from the
-        medium (medium_sampling_weight = 1, or a gridded sigma_t) and max_depth = -1; with a smaller medium_sampling_weight the escaped
-        weight carries no 1 / pdfFailure and overstates the power that leaves.
+        totals[8], kept beside the grid: [0] paths started; [1..3] escaped weight; [4..6] dropped deposit weight; [7] paths ended by a
+        budget, a failed start gate (B-spline field) or no forward progress.
+        The escaped weight.  A path whose free flight reaches the boundary leaves with  T * power * (transmittance / pdfFailure)  per
+        channel, the light tracer's weight of a failed flight (particleproc.cpp:190-196): 1 for a gridded sigma_t; in a homogeneous
+        medium tau_c(d) / pdfFailure(d) at the distance d to the boundary, pdfFailure = medium_sampling_weight * P(sampled distance > d)
+        + (1 - medium_sampling_weight).  The factor is exactly 1, and not evaluated, when the three sigma_t are equal,
+        medium_sampling_weight == 1 and the strategy is not manual.  On a curved ray d is the arc length of the steps inside plus half of the
+        step that left the shape (the flight fails where it passes the boundary, somewhere inside that step; the relative error left in
+        the weight is of the order (difference of the sigma_t x stepsize)^2 / 24).  A path that starts a flight on the boundary heading out, or whose emitted ray
+        misses the shape, leaves with T * power.  A transmittance that underflowed to 0 over a pdfFailure of 0 weighs 0.
+        sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power per channel in expectation when max_depth = -1, for every
+        strategy, channel-dependent coefficients and any medium_sampling_weight > 0.
         Scope: exactly the light tracer's -- the scene must pass mer_render's checks for integrator = MER_INTEGRATOR_PTRACER unchanged (point,
         spot and collimated list entries; cube or sphere with the null boundary; homogeneous or gridded sigma_t; constant or gridded albedo;
         rif_mode CONST, dense TRILINEAR, BSPLINE3 or ACOUSTIC; both steppers), and any other integrator is refused, before any launch.
@@ -488,7 +495,8 @@ int  mer_fluence_time_read(mer_context *ctx, mer_fluence f, double *sums /* [fra
         the walk has accumulated.  The step that left the shape and the step back after it deposit nothing: the last piece of path
         before the boundary, shorter than one stepsize, is lost, as it is for the walk itself.
         totals[8]: [0] paths; [1..3] escaped weight; [4..6] weight x length of the pieces outside the box; [7] ended.
-        sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power holds in expectation under the conditions stated for
+        The escaped weight is mer_fluence_create's: with rho the sampling density, T_c power_c exp(-Delta_c d) at the distance d to
+        the boundary.  sum(sigma_a * sums) + sigma_a * dropped + escaped = paths * power holds per channel in expectation, as stated for
         mer_fluence_create, not per path.  fluence = sums / (paths * cell volume), as for the collision grid.
         mer_fluence_track_create: the descriptor and the checks of mer_fluence_create, under its own message prefix. ---- */
 int  mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, mer_fluence *out);
@@ -507,7 +515,8 @@ int  mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, me
                  boundary heading out), d = the flight's direction.  Curved rays: from the walk's last point inside, x0, along
                  d = normalize(optical momentum), the shape is hit again (the re-hit of the dielectric boundary, after edge.cpp:45-60):
                  x = x0 + d t, or x0 when there is no hit.
-          w      T * power per channel: what `escaped` receives.
+          w      what `escaped` receives: T * power * (transmittance / pdfFailure) per channel for a flight that reached the boundary
+                 (mer_fluence_create, the escaped weight), T * power for a path that starts a flight on the boundary heading out.
           l      the optical path length the time-resolved fluence grid carries (the exterior leg at index 1, then per free flight
                  integral n ds or t * rif_const, in float32) plus the last flight: its length times rif_const, or its integral n ds on a
                  curved ray.  The piece between x0 and x is not added: it is shorter than one stepsize, the loss the walk and the
@@ -528,8 +537,7 @@ int  mer_fluence_track_create(mer_context *ctx, const mer_fluence_desc *desc, me
         totals[16]: [0] paths; [1..3] escaped, as the fluence grids have it (the missed weight included); [4..6] missed; [7] ended;
         [8..10] late; [11..13] rejected; [14] the number of exits binned; [15] 0.  Every escaping path goes to exactly one of sums,
         missed, rejected (tested first) or late: sum(sums) + missed + rejected + late = escaped per channel, up to float64 summation
-        order, for any medium and not only in expectation.  With medium_sampling_weight < 1 the escaped weight carries no 1 / pdfFailure
-        and overstates the power that leaves, as stated for mer_fluence_create.
+        order, for any medium and not only in expectation.
         mer_exitance_create refuses, each with its own message and *out = 0: a boundary that is neither kind; res outside 1 ... 4096;
         frames outside 1 ... 4096; t_bin negative or not finite, or t_bin == 0 with frames != 1; t_min not finite; cos_min outside
         0 <= cos_min < 1; reserved != 0; more than 2^27 keys.  The map starts zeroed.

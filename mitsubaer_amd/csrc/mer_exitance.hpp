@@ -3,8 +3,9 @@
 // one probe per render.
 //
 // A light path is the walk of mer_lightpath.hpp.  Recording an exit draws no sampler number, fetches no RIF value and advances no counter, so
-// counters, paths, escaped weight and ended paths equal K_fluence's.  At each place where K_fluence sets `escaped = T * power` the lane notes
-// the exit point x, the outward direction d, w = T power and the optical path length l (mer.h, mer_render_exitance, has the estimator in full).
+// counters, paths, escaped weight and ended paths equal K_fluence's.  At each place where K_fluence sets `escaped` the lane notes the exit
+// point x, the outward direction d, the same weight w (LightPath::weigh_exit for a flight that reached the boundary) and the optical path length l
+// (mer.h, mer_render_exitance, has the estimator in full).
 //
 // With the null boundary and a convex shape a path leaves at most once, so a lane keeps its one (key, w) in registers and the wave deposits
 // ONCE, after the event loop, with all 64 lanes converged (wave_deposit).  The event loop itself needs no wave-uniform trip count for the
@@ -60,8 +61,9 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
     LaneCounters C; C.clear();
     LightPath<CURVED, SIGMA> lp;
     f3 escaped(0, 0, 0);                                     // a path escapes once
-    int exited = 0, miss = 0;                                // ... through the boundary at xe heading de after the path length plen, or without meeting the shape
+    int miss = 0;                                            // ... through the boundary at xe heading de after the path length plen (dexit >= 0), or without meeting the shape
     f3 xe(0, 0, 0), de(0, 0, 1);
+    float dexit = -1.0f;                                     // >= 0: the path left through the boundary, after a flight of this length (LightPath::weigh_exit; 0: from the boundary itself)
     uint32_t ended = 0;
     float plen = 0.0f;                                       // the optical path length, accumulated in float32 as K_fluence does for a time-resolved grid
     int x, y; float tIn;
@@ -76,7 +78,7 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
             lp.alive = 0;
             if (lp.can_fly()) {
                 const float itsT = lp.boundary_distance(S);
-                if (!(itsT >= 0)) { escaped = lp.T * lp.power; exited = 1; xe = lp.ps; de = lp.dcur; }      // on the boundary, heading out
+                if (!(itsT >= 0)) { escaped = lp.T * lp.power; dexit = 0.0f; xe = lp.ps; de = lp.dcur; }      // on the boundary, heading out
                 else {
                     float sigma = 0.0f;
                     const int ev = lp.run_flight(P, C, W, lp.begin_flight(P, C, W, itsT), sigma);
@@ -91,7 +93,7 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
                     else {
                         // the path left the convex shape.  The walk's own state is read as it stands: finish_free_flight(..., false, ...)
                         // would fetch the RIF on a curved ray and count it
-                        escaped = lp.T * lp.power; exited = 1;
+                        escaped = lp.T * lp.power; dexit = lp.exit_distance(W); lp.weigh_exit(P, dexit, escaped);
                         if (CURVED) {
                             // W.pos() is the last point inside; the shape is met again along the momentum (the re-hit of the dielectric
                             // boundary, mer_wavefront.hpp).  The piece x0 -> x, shorter than one stepsize, adds nothing to the path length.
@@ -112,7 +114,7 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
     double rejected[3] = {0.0, 0.0, 0.0}, late[3] = {0.0, 0.0, 0.0}, missed[3] = {0.0, 0.0, 0.0};
     bool dep = false; uint32_t key = 0;
     if (miss) { missed[0] = (double) escaped.x; missed[1] = (double) escaped.y; missed[2] = (double) escaped.z; }
-    if (exited) {
+    if (dexit >= 0.0f) {
         dep = true;
         if (M.cos_min > 0.0f && dot(de, shape_normal(S, xe)) < M.cos_min) {
             dep = false; rejected[0] = (double) escaped.x; rejected[1] = (double) escaped.y; rejected[2] = (double) escaped.z;

@@ -49,6 +49,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
     LaneCounters C; C.clear();
     LightPath<CURVED, SIGMA> lp;
     f3 escaped(0, 0, 0);                                     // a path escapes once
+    float dexit = -1.0f;                                     // ... after a flight of this length that reached the boundary (LightPath::weigh_exit)
     double dropped[3] = {0.0, 0.0, 0.0};
     uint32_t ended = 0;
     float plen = 0.0f;                                       // TIMED: the optical path length, accumulated in float32 as K_ptracer does under a TRANSIENT film
@@ -89,13 +90,14 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                             lp.scatter(S, lp.arrive(W, m));
                         }
                     } else if (ev == EV_GATE_FAIL) ended++;
-                    else escaped = lp.T * lp.power;          // the path left the convex shape
+                    else { escaped = lp.T * lp.power; dexit = lp.exit_distance(W); }       // the path left the convex shape
                 }
             }
         }
         wave_deposit(G.sums, G.chk, CHK_FLUENCE, TIMED ? G.n_keys() : G.n_cells, dep, cell, w);
     }
     if (lp.alive) ended++;                                   // PT_MAX_EVENTS
+    lp.weigh_exit(P, dexit, escaped);
 
     // totals and counters: one wave-aggregated flush each (every lane of the wave gets here)
     const double tot[8] = {(double) wave_sum(C.paths), wave_sum_f64((double) escaped.x), wave_sum_f64((double) escaped.y), wave_sum_f64((double) escaped.z),

@@ -97,6 +97,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
     LaneCounters C; C.clear();
     LightPath<CURVED, SIGMA> lp;
     f3 escaped(0, 0, 0);
+    float dexit = -1.0f;                                     // the length of the flight that reached the boundary (LightPath::weigh_exit)
     double dropped[3] = {0.0, 0.0, 0.0};                     // weight x length of the pieces outside the box
     uint32_t ended = 0;
     int x, y; float tIn;
@@ -183,7 +184,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
                     lp.scatter(S, lp.arrive(W, m));
                 }
             } else if (ev == EV_GATE_FAIL) ended++;
-            else { escaped = fT; fL = itsT; }
+            else { escaped = fT; fL = itsT; dexit = lp.exit_distance(W); }
         }
         // ---- the deposits
         if (CURVED) {
@@ -206,6 +207,7 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_track_kernel(const Params P,
         }
     }
     if (lp.alive) ended++;                                   // PT_MAX_EVENTS
+    lp.weigh_exit(P, dexit, escaped);
 
     const double tot[8] = {(double) wave_sum(C.paths), wave_sum_f64((double) escaped.x), wave_sum_f64((double) escaped.y), wave_sum_f64((double) escaped.z),
                            wave_sum_f64(dropped[0]), wave_sum_f64(dropped[1]), wave_sum_f64(dropped[2]), (double) wave_sum(ended)};

@@ -146,6 +146,35 @@ struct LightPath {
         return true;
     }
 
+    // ---- "the flight reached the boundary", in two steps.  A path whose flight fails leaves with T power times the transmittance /
+    // pdfFailure of that flight (process() :190-196).  In a homogeneous medium that factor depends on the flight through its length alone
+    // -- strategy_pdfs with the scene's sampling density: what finish_free_flight(..., false, ...) would produce, without its RIF fetch and
+    // its counter -- and a path leaves once, so K_fluence and K_fluence_track keep T power and this length across their event loop and apply
+    // the factor after it, where the walk's registers are free (inside the loop the second copy of strategy_pdfs cost K_fluence's straight
+    // homogeneous instance its fifth wave; K_exitance applies it in place: after its loop it cost the acoustic Verlet instance 36 bytes of
+    // scratch).  exit_distance: straight rays, W.dist.  A curved flight fails exactly when its sampled distance passes the
+    // boundary, somewhere inside the step that left the shape, but W.dist stops at the last step inside (and one step earlier still after
+    // traceTillBoundary's step back): half of the leaving step is added, which removes the error of first order in the stepsize -- what is
+    // left of it in the weight is (delta sigma_t x stepsize)^2 / 24.  (Intersecting the shape from the last point inside gives the rest
+    // exactly, and costs the curved instances of K_fluence 8 - 12 VGPRs, two of them a wave, and one of K_fluence_track 36 bytes of scratch.)
+    template <class WalkT>
+    __device__ __forceinline__ float exit_distance(const WalkT &W) const {
+        if (SIGMA != MER_SIGMA_HOMOGENEOUS) return 0.0f;
+        return CURVED ? W.dist + (W.seg_inf ? 1.5f : 0.5f) * W.hprev : W.dist;
+    }
+    // w *= transmittance / pdfFailure at the length d of the failed flight (below 0: the path did not leave; 0 weighs 1 exactly).  The factor
+    // is identically 1, and skipped by a scene-uniform test, when one exponential of the medium's own sigma_t draws every flight: the
+    // three sigma_t equal, medium_sampling_weight == 1 and no manual density; a gridded sigma_t has transmittance = pdfFailure.  A
+    // transmittance that underflowed to 0 over a pdfFailure of 0 weighs 0.
+    static __device__ __forceinline__ void weigh_exit(const Params &P, float d, f3 &w) {
+        if (SIGMA != MER_SIGMA_HOMOGENEOUS) return;
+        const bool analog = P.sigT.x == P.sigT.y && P.sigT.y == P.sigT.z && P.medium_sampling_weight == 1.0f && P.sc.strategy != MER_STRATEGY_MANUAL;
+        if (analog || !(d >= 0.0f)) return;
+        f3 tr; float pdfSuccess, pdfFailure;
+        strategy_pdfs(P, d, P.sampling_density, tr, pdfSuccess, pdfFailure);
+        w = pdfFailure > 0.0f ? w * (tr / pdfFailure) : f3(0, 0, 0);
+    }
+
     // ---- scattering, in two steps (K_ptracer connects the vertex to the sensor between them).  arrive: the throughput at the vertex
     // (process() :174) and the direction the path came from; scatter: phase-function sampling (EImportance; hg and isotropic are symmetric),
     // then the roulette.
