@@ -273,6 +273,14 @@ typedef struct { int32_t res[3]; float bmin[3], bmax[3]; int32_t frames; float t
    frames == 1 and t_bin == 0.  cos_min: the acceptance cone about the outward normal (0 accepts every exit).  reserved must be 0. */
 typedef int32_t mer_exitance;                                 /* handle, > 0, from the context's handle counter */
 typedef struct { int32_t boundary; int32_t res[2]; int32_t frames; float t_min, t_bin, cos_min; int32_t reserved; } mer_exitance_desc;
+/* a detector on the boundary of the medium shape (mer_sensitivity_create): the raster of an exitance map of res[0] x res[1] (u x v) cells per
+   face, one `face` of it (0 ... 5 for MER_BOUNDARY_AABB, 0 for MER_BOUNDARY_SPHERE) and on that face the half-open cell window
+   iu0 <= iu < iu1, iv0 <= iv < iv1; the acceptance cone cos_min about the outward normal (0 accepts every exit); the gate (t_min, t_bin) in
+   optical path length (t_bin == 0: no gate).  reserved must be 0. */
+typedef struct { int32_t boundary, res[2], face, iu0, iu1, iv0, iv1; float cos_min, t_min, t_bin; int32_t reserved; } mer_detector_desc;
+/* a sensitivity grid (mer_sensitivity_create): the voxel grid of a fluence grid (res, bmin, bmax: half-open cells) and the detector */
+typedef int32_t mer_sensitivity;                              /* handle, > 0, from the context's handle counter */
+typedef struct { int32_t res[3]; float bmin[3], bmax[3]; mer_detector_desc det; } mer_sensitivity_desc;
 
 enum {
     MER_C_PATHS = 0, MER_C_STEPS, MER_C_RIF_EVALS, MER_C_TENTATIVE, MER_C_REAL,
@@ -552,6 +560,54 @@ int  mer_exitance_clear(mer_context *ctx, mer_exitance e);
 int  mer_exitance_destroy(mer_context *ctx, mer_exitance e);
 int  mer_render_exitance(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_exitance e);
 int  mer_exitance_read(mer_context *ctx, mer_exitance e, double *sums /* [frames][faces][res_v][res_u][3] or NULL */, double totals[16]);
+
+/* ---- sensitivity maps: which part of the medium did the light that reached a detector travel through.  The absorption sensitivity of
+        the detected signal -- the Jacobian of diffuse optical tomography, the photon-measurement density function, the "banana" between
+        a source and a detector, the mean partial path length per voxel -- by the method photon-migration codes call replay.  The
+        reference has no analogue; the nearest is one `irradiancemeter` render per perturbed voxel.
+        mer_sensitivity is its own kind of handle: the mer_fluence_* and mer_exitance_* entry points refuse it as an unknown handle, and
+        the entry points below refuse theirs the same way.
+        The walk.  A light path is exactly the one mer_render_exitance walks for the same scene, shard and seed, and its exit (x, d, w,
+        l) is the one stated there.  totals[0] (paths), totals[7] (ended) and mer_counters_read equal mer_render_exitance's.
+        The detector.  A path is DETECTED when its exit passes, in mer_render_exitance's own expressions: the cone (with cos_min > 0 an
+        exit with dot(d, outward normal at x) < cos_min is rejected), then the gate (t_bin > 0: detected iff
+        floorf((l - t_min) / t_bin) == 0), then the window (the exit's cell lies on `face` with iu0 <= iu < iu1 and iv0 <= iv < iv1).
+        The detected weight totals[1..3] therefore equals the sum over the window's cells of a one-frame exitance map with the same
+        raster, cone and gate, up to float64 summation order.
+        The estimator.  A detected path leaves with weight w (RGB), known only at its exit, so every chunk of paths is walked twice: the
+        first pass lists the detected paths with their w, the second re-walks exactly those -- the sampler stream is keyed by the work
+        id -- and every free flight deposits w * length for the piece of the flight inside each cell of the grid:
+            J_c = sum over the detected paths of w * L_c,      L_c = the length the path travelled inside cell c.
+        The pieces are cut at the faces of the (half-open) cells exactly as the track-length fluence grid cuts them; the exterior leg of
+        an emitter outside the shape deposits nothing.  Curved rays: every eikonal step that passed the inside test deposits along its
+        chord; the step that left the shape and the step back after it deposit nothing, so the last piece of path before the boundary,
+        shorter than one stepsize, is lost, as it is for the walk and for the track-length grid.
+        Interpretation.  With S = W_det / paths the detected signal per emitted path, dS / d sigma_a(c) = -J_c / paths for a change of
+        the absorption in cell c at fixed sigma_s.  This holds for every distance-sampling strategy -- only the integrand depends on
+        sigma_a -- so unlike the track-length fluence grid there is NO analog requirement.  J_c / W_det is the mean partial path length in
+        cell c of the detected light.
+        The grid holds raw float64 sums, double[nz][ny][nx][3], at most 2^27 cells; raw sums of disjoint shards add (the caller reduces).
+        totals[16]: [0] paths; [1..3] the detected weight W_det; [4..6] dropped: w * the length of the pieces outside the box; [7] ended
+        (first pass); [8] the number of detected paths; [9..11] sum over the detected paths of w * the path's length inside the shape,
+        summed per path in float64 from the flight lengths, before any cutting (straight rays: the distance to the collision or to the
+        boundary; curved rays: the length of every step that deposited): sum(sums) + dropped = [9..11] per channel up to the float32
+        arithmetic of the pieces; [12] replay disagreements: the paths whose second walk did not leave with the bits of the recorded w
+        -- 0 unless the two passes walked different paths; [13..15] 0.
+        mer_sensitivity_create refuses, each with its own message and *out = 0: the box checks of mer_fluence_create; the boundary, res,
+        t_bin, t_min, cos_min and reserved checks of mer_exitance_create; a face outside the boundary's faces; a window that is empty or
+        leaves the raster.  The grid starts zeroed.
+        mer_render_sensitivity requires integrator = ptracer and the light tracer's scope unchanged, refuses a scene whose boundary
+        differs from the detector's, ACCUMULATES (mer_sensitivity_clear zeroes the grid and the totals) and returns synchronised.  Per
+        chunk of the light tracer's launches it reads the number of detected paths back and launches the second pass over exactly that
+        many (none when it is 0); the list of one chunk's paths lives in the context and is freed with it.  mer_sensitivity_read: sums
+        may be NULL (totals only).  mer_context_destroy frees the grids alive.
+        Not built: several detectors per call, sensitivities to scattering or to the index field, time-resolved Jacobians beyond the one
+        gate, several GPUs in one call. ---- */
+int  mer_sensitivity_create(mer_context *ctx, const mer_sensitivity_desc *desc, mer_sensitivity *out);
+int  mer_sensitivity_clear(mer_context *ctx, mer_sensitivity s);
+int  mer_sensitivity_destroy(mer_context *ctx, mer_sensitivity s);
+int  mer_render_sensitivity(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_sensitivity s);
+int  mer_sensitivity_read(mer_context *ctx, mer_sensitivity s, double *sums /* [nz][ny][nx][3] or NULL */, double totals[16]);
 
 /* ---- leaf entry points for parity tests (host pointers, batched SoA) ------------------------------ */
 /* GridDataSource::lookupFloat (gridvolume.cpp:337-388); out_idx[4*i..] = x1,y1,z1,linear index or -1 */

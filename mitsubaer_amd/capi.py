@@ -30,6 +30,7 @@ SYMBOLS = [
     "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
     "mer_fluence_time_create", "mer_fluence_time_read", "mer_fluence_track_create",
     "mer_exitance_create", "mer_exitance_clear", "mer_exitance_destroy", "mer_render_exitance", "mer_exitance_read",
+    "mer_sensitivity_create", "mer_sensitivity_clear", "mer_sensitivity_destroy", "mer_render_sensitivity", "mer_sensitivity_read",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -473,6 +474,70 @@ def validate_exitance(desc):
         raise MerError(at + "more than 2^27 cells x faces x frames")
 
 
+class DetectorDesc(C.Structure):
+    """mer_detector_desc: the raster of an exitance map (res = (res_u, res_v) cells per face), one face of it, the half-open cell window
+    iu0 <= iu < iu1, iv0 <= iv < iv1 on that face, the acceptance cone cos_min and the gate (t_min, t_bin) in optical path length (t_bin 0: none)"""
+    _fields_ = [("boundary", C.c_int32), ("res", C.c_int32 * 2), ("face", C.c_int32), ("iu0", C.c_int32), ("iu1", C.c_int32),
+                ("iv0", C.c_int32), ("iv1", C.c_int32), ("cos_min", C.c_float), ("t_min", C.c_float), ("t_bin", C.c_float), ("reserved", C.c_int32)]
+
+
+class SensitivityDesc(C.Structure):
+    """mer_sensitivity_desc: the box of a FluenceDesc and the detector"""
+    _fields_ = [("res", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("det", DetectorDesc)]
+
+
+# mer_sensitivity_read's totals: [0], [1..3], [4..6], [7], [8], [9..11], [12]
+SENSITIVITY_TOTALS = ("paths", "detected_weight", "dropped", "ended", "detected", "weight_length", "disagreements")
+
+
+def detector_desc(boundary, res, face, window=None, cos_min=0.0, t_min=0.0, t_bin=0.0):
+    """window = (iu0, iu1, iv0, iv1); None: the whole face"""
+    d = DetectorDesc()
+    d.boundary, d.face = int(boundary), int(face)
+    d.res[:] = [int(v) for v in res]
+    d.iu0, d.iu1, d.iv0, d.iv1 = [int(v) for v in (window if window is not None else (0, d.res[0], 0, d.res[1]))]
+    d.cos_min, d.t_min, d.t_bin, d.reserved = float(cos_min), float(t_min), float(t_bin), 0
+    return d
+
+
+def sensitivity_desc(res, bmin, bmax, detector):
+    d = SensitivityDesc()
+    d.res[:] = [int(v) for v in res]
+    d.bmin[:] = [float(v) for v in bmin]
+    d.bmax[:] = [float(v) for v in bmax]
+    C.memmove(C.byref(d.det), C.byref(detector), C.sizeof(DetectorDesc))
+    return d
+
+
+def validate_sensitivity(desc):
+    """The refusals of mer_sensitivity_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_sensitivity_create: "
+    try:
+        validate_fluence(desc)                         # the box checks, unchanged
+    except MerError as e:
+        raise MerError(at + str(e)[len("mer_fluence_create: "):]) from None
+    t = desc.det
+    if t.boundary not in (P.BOUNDARY_AABB, P.BOUNDARY_SPHERE):
+        raise MerError(at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)")
+    for a in range(2):
+        if t.res[a] < 1 or t.res[a] > 4096:
+            raise MerError(at + "detector res must lie in 1 ... 4096 on both axes")
+    if not np.isfinite(t.t_bin) or t.t_bin < 0:
+        raise MerError(at + "t_bin must be finite and at least 0")
+    if not np.isfinite(t.t_min):
+        raise MerError(at + "t_min must be finite")
+    if not (t.cos_min >= 0 and t.cos_min < 1):
+        raise MerError(at + "cos_min must lie in 0 <= cos_min < 1")
+    if t.reserved != 0:
+        raise MerError(at + "reserved must be 0")
+    if t.face < 0 or t.face >= exitance_faces(t.boundary):
+        raise MerError(at + "face must be one of the boundary's faces (0 ... 5 for the cube, 0 for the sphere)")
+    if t.iu0 < 0 or t.iu1 > t.res[0] or t.iv0 < 0 or t.iv1 > t.res[1]:
+        raise MerError(at + "the window must lie inside the raster (0 <= iu0, iu1 <= res[0], 0 <= iv0, iv1 <= res[1])")
+    if not (t.iu0 < t.iu1 and t.iv0 < t.iv1):
+        raise MerError(at + "the window is empty (iu0 < iu1 and iv0 < iv1 are required)")
+
+
 def lib(path=None):
     """The C-ABI library (ctypes).  path = None: libmer.so; Context(check=True) loads libmer_check.so beside it."""
     path = path or LIB_PATH
@@ -546,6 +611,7 @@ class Context:
         self.device_id = device_id
         self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids; a time-resolved one: (nx, ny, nz, frames)
         self._exitance_shape = {}                      # handle -> (frames, faces, res_v, res_u) of the live exitance maps
+        self._sensitivity_res = {}                     # handle -> (nx, ny, nz) of the live sensitivity grids
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -976,6 +1042,61 @@ class Context:
             return self.exitance_read(h)
         finally:
             self.exitance_destroy(h)
+
+    # ---- the sensitivity grid of a detector on the boundary (mer_render_sensitivity) ------------
+    def sensitivity_create(self, res, bmin, bmax, detector):
+        """-> handle of a zeroed grid of res = (nx, ny, nz) cells over the box bmin ... bmax for the detector (capi.detector_desc)"""
+        d = sensitivity_desc(res, bmin, bmax, detector)
+        validate_sensitivity(d)
+        h = C.c_int32()
+        self._check(self.lib.mer_sensitivity_create(self.h, C.byref(d), C.byref(h)))
+        self._sensitivity_res[h.value] = (d.res[0], d.res[1], d.res[2])
+        return h.value
+
+    def sensitivity_clear(self, handle):
+        self._check(self.lib.mer_sensitivity_clear(self.h, C.c_int32(handle)))
+
+    def sensitivity_destroy(self, handle):
+        self._check(self.lib.mer_sensitivity_destroy(self.h, C.c_int32(handle)))
+        self._sensitivity_res.pop(handle, None)
+
+    def render_sensitivity(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
+        """accumulates w x length of the shard's detected light paths into the grid; returns synchronised"""
+        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
+        self._check(self.lib.mer_render_sensitivity(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+
+    def sensitivity_read(self, handle, sums=True):
+        """-> (raw sums float64 [nz][ny][nx][3], or None with sums = False; totals float64 [16]: capi.SENSITIVITY_TOTALS)"""
+        totals = np.zeros(16, np.float64)
+        out = None
+        if sums:
+            res = self._sensitivity_res.get(handle)
+            if res is None:
+                raise MerError("mer_sensitivity_read: unknown sensitivity handle")
+            out = np.zeros((res[2], res[1], res[0], 3), np.float64)
+        self._check(self.lib.mer_sensitivity_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
+        return out, totals
+
+    def sensitivity(self, scene, res, detector, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
+        """One sensitivity map of the scene (integrator = ptracer) for a detector on the boundary of its medium shape (capi.detector_desc,
+        or a dict of its arguments without the boundary): (J / paths float64 [nz][ny][nx][3], info).  With S = detected weight / paths the
+        detected signal, dS / d sigma_a of cell c is -J_c / paths, whatever the distance sampling; J_c / detected weight is the mean
+        partial path length in c.  The box defaults to the bounding box of the medium shape.  info: the totals by name (paths,
+        detected_weight [3], dropped [3], ended, detected, weight_length [3], disagreements), the raw sums and the box."""
+        if isinstance(detector, dict):
+            detector = detector_desc(scene.boundary, **detector)
+        bmin, bmax = self._fluence_box(scene, bmin, bmax)
+        h = self.sensitivity_create(res, bmin, bmax, detector)
+        try:
+            self.render_sensitivity(scene, h, spp_begin, spp_count, seed)
+            sums, t = self.sensitivity_read(h)
+        finally:
+            self.sensitivity_destroy(h)
+        d = fluence_desc(res, bmin, bmax)
+        info = {"paths": t[0], "detected_weight": t[1:4].copy(), "dropped": t[4:7].copy(), "ended": t[7], "detected": t[8],
+                "weight_length": t[9:12].copy(), "disagreements": t[12], "sums": sums, "totals": t,
+                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64)}
+        return (sums / t[0] if t[0] > 0 else np.zeros_like(sums)), info
 
     def synchronize(self):
         self._check(self.lib.mer_synchronize(self.h))

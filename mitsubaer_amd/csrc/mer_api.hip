@@ -176,6 +176,8 @@ void mer_context_destroy(mer_context *ctx) {
     for (auto &kv : ctx->envmaps) if (kv.second.dev) (void) hipFree(kv.second.dev);
     for (auto &kv : ctx->fluences) if (kv.second.dev) (void) hipFree(kv.second.dev);
     for (auto &kv : ctx->exitances) if (kv.second.dev) (void) hipFree(kv.second.dev);
+    for (auto &kv : ctx->sensitivities) if (kv.second.dev) (void) hipFree(kv.second.dev);
+    if (ctx->detect_list) (void) hipFree(ctx->detect_list);
     if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {
         if (pp.slots) (void) hipFree(pp.slots);

@@ -43,7 +43,9 @@ __device__ __forceinline__ bool is_zero(f3 a) { return a.x == 0.0f && a.y == 0.0
 enum { CHK_SLOT = 1, CHK_QUEUE_SEG, CHK_QUEUE_ITEM, CHK_HITQ, CHK_FILM, CHK_PATHOUT, CHK_GRID_DENSE, CHK_GRID_RECORD, CHK_GRID_COEFF,
        CHK_GRID_RGB, CHK_LIVE_ROW, CHK_ENVMAP, CHK_FLUENCE /* the sums of a fluence grid (mer_fluence.hpp) */,
        CHK_SIDE_STATE /* the busy bytes of the side-walk slots (mer_wavefront.hpp) */,
-       CHK_EXITANCE = 34 /* the sums of an exitance map (mer_exitance.hpp); mer_sdf_build.hip has 32, 33 */ };
+       CHK_EXITANCE = 34 /* the sums of an exitance map (mer_exitance.hpp); mer_sdf_build.hip has 32, 33 */,
+       CHK_DETECT_LIST /* the records of the detected-path list (mer_sensitivity.hpp) */,
+       CHK_SENSITIVITY /* the sums of a sensitivity grid (mer_sensitivity.hpp) */ };
 #ifdef MER_BOUNDS_CHECK
 __device__ __forceinline__ uint64_t mer_chk(unsigned long long *chk, int kind, uint64_t idx, uint64_t limit) {
     if (idx < limit) return idx;

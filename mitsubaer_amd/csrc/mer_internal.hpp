@@ -61,6 +61,16 @@ struct Exitance {
     size_t bytes() const { return (n_keys() * 3 + 16) * sizeof(double); }
 };
 
+// a sensitivity grid (mer_sensitivity_create): one device buffer -- the sums double[nz][ny][nx][3], then the 16 totals.  Its handle shares the
+// volumes' numbering; the grid is its own kind of handle, neither a fluence grid's nor an exitance map's.
+struct Sensitivity {
+    mer_sensitivity_desc desc;
+    double *dev = nullptr;
+    uint64_t n_keys() const { return (uint64_t) desc.res[0] * (uint64_t) desc.res[1] * (uint64_t) desc.res[2]; }
+    double *totals() const { return dev + n_keys() * 3; }
+    size_t bytes() const { return (n_keys() * 3 + 16) * sizeof(double); }
+};
+
 #define MER_MAX_PIPES 4
 struct Pipe {
     hipStream_t stream = nullptr, own_stream = nullptr;      // pipeline 0 runs on the context stream
@@ -110,6 +120,8 @@ struct mer_context {
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
     std::map<int, mer::Fluence> fluences;        // mer_fluence_create (handles from next_handle)
     std::map<int, mer::Exitance> exitances;      // mer_exitance_create (handles from next_handle)
+    std::map<int, mer::Sensitivity> sensitivities;   // mer_sensitivity_create (handles from next_handle)
+    uint32_t *detect_list = nullptr; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 4 arrays of detect_cap words
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
     float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
@@ -183,6 +195,9 @@ int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shar
 // mer_render_fluence.hip: the fluence grid recorded from the same light paths (mer_render_fluence and the mer_fluence_* entry points)
 
 // mer_render_exitance.hip: the exitance map recorded from the same light paths (mer_render_exitance and the mer_exitance_* entry points)
+
+// mer_render_sensitivity.hip: the sensitivity grid of a detector on the boundary, two passes over the same light paths (mer_render_sensitivity
+// and the mer_sensitivity_* entry points)
 
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
 // validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.

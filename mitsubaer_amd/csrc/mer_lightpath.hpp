@@ -1,5 +1,6 @@
 // mer_lightpath.hpp -- the walk of one light path, shared by every kernel that records something from light paths: K_ptracer (mer_ptracer.hpp),
-// K_fluence (mer_fluence.hpp), K_fluence_track (mer_fluence_track.hpp) and K_exitance (mer_exitance.hpp).  ParticleTracer::process
+// K_fluence (mer_fluence.hpp), K_fluence_track (mer_fluence_track.hpp), K_exitance (mer_exitance.hpp) and K_detect / K_replay
+// (mer_sensitivity.hpp).  ParticleTracer::process
 // (src/librender/particleproc.cpp:107-270) restricted to one convex index-matched shape with an interior medium: work id and sampler key,
 // emitter_select, emit_ray, the entry into the shape (one depth for the null boundary), the free flights through Walk, phase_sample, the
 // roulette, PT_MAX_EVENTS and PT_STEP_BUDGET.  For one scene, shard and seed the four kernels walk the same paths draw for draw because they
@@ -77,11 +78,16 @@ struct LightPath {
     // (decode_work); its sampler stream is keyed by that pair.  false: no path -- the work id lies past the launch or, in a partial tile,
     // outside the image; the lane seeds pixel 0, draws nothing and idles (alive = 0) through a wave-uniform loop.
     __device__ __forceinline__ bool decode(const Params &P, LaneCounters &C, uint64_t first, uint32_t count, int &x, int &y) {
-        const mer_scene_desc &S = P.sc;
         const uint32_t j = blockIdx.x * PT_BLOCK + threadIdx.x;
+        return decode_id(P, C, j < count, first + j, x, y);
+    }
+    // decode_id: the same start from a work id the caller holds (have = false: the lane has none).  K_replay (mer_sensitivity.hpp) reads
+    // its ids from the list K_detect wrote, so that a lane re-walks exactly the path that lane of K_detect walked.
+    __device__ __forceinline__ bool decode_id(const Params &P, LaneCounters &C, bool have, uint64_t w, int &x, int &y) {
+        const mer_scene_desc &S = P.sc;
         uint32_t sample = 0;
         x = 0; y = 0;
-        const bool live = j < count && decode_work(P, first + j, x, y, sample);        // a work id of a partial tile may fall outside the image
+        const bool live = have && decode_work(P, w, x, y, sample);        // a work id of a partial tile may fall outside the image
         rng.seed(P.seed, live ? (uint32_t) (y * S.width + x) : 0u, sample);
         ps = f3(0, 0, 0); dcur = f3(0, 0, 1); power = f3(0, 0, 0); T = f3(1, 1, 1);
         depth = 1; maxDepth = S.max_depth; alive = 0; entering = false;

@@ -1,6 +1,6 @@
 // mer_lightpath_host.hpp -- the host side every light-path kernel family shares (mer_render_ptracer.hip, mer_render_fluence.hip,
-// mer_render_fluence_track.hip, mer_render_exitance.hip): the choice among a family's 14 instantiations, the launch loop over the work ids of
-// a shard, and the device buffer behind a mer_fluence / mer_exitance handle.
+// mer_render_fluence_track.hip, mer_render_exitance.hip, mer_render_sensitivity.hip): the choice among a family's 14 instantiations, the launch
+// loop over the work ids of a shard, and the device buffer behind a mer_fluence / mer_exitance / mer_sensitivity handle.
 #pragma once
 #include "mer_internal.hpp"
 #include "mer_lightpath.hpp"
@@ -42,10 +42,10 @@ static inline int check_light_paths(mer_context *ctx, const Params &P, const mer
 // The light paths of a shard are the (pixel, sample index) pairs K_gen would enumerate: the work ids are laid out as launch_render lays them
 // out (decode_work) and launched PT_PATHS_PER_LAUNCH (curved rays: PT_PATHS_PER_LAUNCH_CURVED) at a time on the context stream as
 // kernel(P, extra ..., first, count).  Returns synchronised, as the wavefront loop does.  film = nullptr: the sensor fields only enumerate the paths.
-template <class Kernel, class... Extra>
-static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Params &P, const mer_shard *shard, uint64_t seed, float *film_dev,
-                              uint64_t n_film, Kernel kernel, const Extra &... extra) {
-    if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
+// The loop itself: per_chunk(first, count) launches what one chunk of work ids needs and returns nonzero (with the context's message set) to stop.
+template <class PerChunk>
+static int for_light_path_chunks(mer_context *ctx, const mer_scene_desc *scene, Params &P, const mer_shard *shard, uint64_t seed, float *film_dev,
+                                 uint64_t n_film, PerChunk per_chunk) {
     P.seed = seed;
     P.spp_begin = shard->spp_begin; P.spp_count = shard->spp_count; P.spp_stride = shard->spp_stride;
     P.tile_rank = shard->tile_rank; P.tile_count = shard->tile_count;
@@ -61,13 +61,36 @@ static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Par
     const uint64_t chunk = scene->rif_mode == MER_RIF_CONST ? PT_PATHS_PER_LAUNCH : PT_PATHS_PER_LAUNCH_CURVED;
     for (uint64_t first = 0; first < P.total_work; first += chunk) {
         const uint32_t count = (uint32_t) std::min<uint64_t>(chunk, P.total_work - first);
-        hipLaunchKernelGGL(kernel, dim3((count + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, ctx->stream, P, extra..., first, count);
-        HIP_CHECK(ctx, hipGetLastError());
+        if (per_chunk(first, count)) return 1;
     }
     HIP_CHECK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->timed = true;
     HIP_CHECK(ctx, hipEventSynchronize(ctx->ev1));
     ctx->last_event_ms = 0; ctx->last_march_ms = 0; ctx->last_passes = 0; ctx->last_pipes = 1;
+    return 0;
+}
+// one kernel per chunk, as kernel(P, extra ..., first, count)
+template <class Kernel, class... Extra>
+static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Params &P, const mer_shard *shard, uint64_t seed, float *film_dev,
+                              uint64_t n_film, Kernel kernel, const Extra &... extra) {
+    if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
+    return for_light_path_chunks(ctx, scene, P, shard, seed, film_dev, n_film, [&](uint64_t first, uint32_t count) {
+        hipLaunchKernelGGL(kernel, dim3((count + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, ctx->stream, P, extra..., first, count);
+        HIP_CHECK(ctx, hipGetLastError());
+        return 0;
+    });
+}
+
+// ---- The box of a voxel grid over the medium (fluence grids, sensitivity grids): the checks of mer_fluence_create under the caller's prefix
+static inline int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d, const std::string &at = "mer_fluence_create: ") {
+    uint64_t cells = 1;
+    for (int a = 0; a < 3; a++) {
+        if (d->res[a] < 1 || d->res[a] > 1024) return fail(ctx, at + "res must lie in 1 ... 1024 on every axis");
+        if (!std::isfinite(d->bmin[a]) || !std::isfinite(d->bmax[a])) return fail(ctx, at + "bmin / bmax must be finite");
+        if (!(d->bmin[a] < d->bmax[a])) return fail(ctx, at + "bmin must be below bmax on every axis");
+        cells *= (uint64_t) d->res[a];
+    }
+    if (cells > ((uint64_t) 1 << 27)) return fail(ctx, at + "more than 2^27 cells");
     return 0;
 }
 

@@ -17,18 +17,6 @@ typedef FluenceFamily<false>::Kernel FluenceKernel;
 // mer_render_fluence_track.hip: the same 14 combinations of K_fluence_track, for a handle of mer_fluence_track_create
 FluenceKernel pick_fluence_track(const mer_scene_desc *sc);
 
-static int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d, const std::string &at = "mer_fluence_create: ") {
-    uint64_t cells = 1;
-    for (int a = 0; a < 3; a++) {
-        if (d->res[a] < 1 || d->res[a] > 1024) return fail(ctx, at + "res must lie in 1 ... 1024 on every axis");
-        if (!std::isfinite(d->bmin[a]) || !std::isfinite(d->bmax[a])) return fail(ctx, at + "bmin / bmax must be finite");
-        if (!(d->bmin[a] < d->bmax[a])) return fail(ctx, at + "bmin must be below bmax on every axis");
-        cells *= (uint64_t) d->res[a];
-    }
-    if (cells > ((uint64_t) 1 << 27)) return fail(ctx, at + "more than 2^27 cells");
-    return 0;
-}
-
 // the box checks of mer_fluence_create, then the window's
 static int check_fluence_time_desc(mer_context *ctx, const mer_fluence_time_desc *d) {
     const std::string at = "mer_fluence_time_create: ";

@@ -1235,6 +1235,58 @@ bool parseExitanceRes(const std::string &value, int res[2]) {
     return true;
 }
 
+// The sensitivity grid of a `ptracer` scene: one context (a mer_multi of one device, as renderFluence), one grid over the medium shape's bounding box
+Integrator::Sensitivity Integrator::renderSensitivity(const Scene &scene, int device, const int res[3], mer_detector_desc det, int spp, unsigned long long seed) const {
+    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the sensitivity grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    mer_scene_desc d;
+    flatten(scene, d);
+    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    Sensitivity out;
+    mer_sensitivity_desc sd;
+    for (int a = 0; a < 3; a++) {
+        sd.res[a] = out.res[a] = res[a];
+        sd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
+        sd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
+    }
+    det.boundary = d.boundary; det.reserved = 0;
+    sd.det = det;
+    mer_multi *mm = NULL;
+    const int32_t id = device;
+    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
+    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
+    mer_context *ctx = mer_multi_context(mm, 0);
+    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
+    mer_sensitivity s = 0;
+    if (mer_sensitivity_create(ctx, &sd, &s)) fail();
+    const mer_shard whole = {0, spp, 1, 0, 1};
+    if (mer_render_sensitivity(ctx, &d, &whole, seed, s)) fail();
+    out.sums.resize((size_t) res[0] * res[1] * res[2] * 3);
+    if (mer_sensitivity_read(ctx, s, out.sums.data(), out.totals)) fail();
+    mer_multi_destroy(mm);                     // frees the grid and the detected-path list with its context
+    return out;
+}
+std::vector<float> Integrator::Sensitivity::jacobian() const {
+    const double inv = totals[0] > 0 ? 1.0 / totals[0] : 0.0;
+    std::vector<float> v(sums.size());
+    for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
+    return v;
+}
+bool parseDetector(const std::string &value, mer_detector_desc &det) {
+    int v[7]; size_t p = 0;
+    for (int a = 0; a < 7; a++) {
+        size_t e = a < 6 ? value.find(',', p) : value.size();
+        if (e == std::string::npos || e == p) return false;
+        const std::string tok = value.substr(p, e - p);
+        if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
+        v[a] = std::atoi(tok.c_str());
+        p = e + 1;
+    }
+    if (v[0] > 5 || v[1] < 1 || v[1] > 4096 || v[2] < 1 || v[2] > 4096) return false;
+    if (!(v[3] < v[4] && v[4] <= v[1] && v[5] < v[6] && v[6] <= v[2])) return false;
+    det.face = v[0]; det.res[0] = v[1]; det.res[1] = v[2]; det.iu0 = v[3]; det.iu1 = v[4]; det.iv0 = v[5]; det.iv1 = v[6];
+    return true;
+}
+
 std::vector<float> develop(const std::vector<float> &film, int w, int h, int frames) {
     const int ch = frames * 3 + 2;
     std::vector<float> rgb((size_t) frames * w * h * 3);

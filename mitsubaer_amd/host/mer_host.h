@@ -258,6 +258,18 @@ public:
     };
     /// frames = 1 and tBin = 0: the steady map.  The window is the caller's; the scene's film is not read
     Exitance renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const;
+    /// which part of the medium the light that reached a detector travelled through: the absorption sensitivity (Jacobian) of a detector on the
+    /// boundary of the medium shape, on a grid of res[0] x res[1] x res[2] cells over the shape's bounding box (mer_render_sensitivity: the
+    /// detected light paths of a `ptracer` scene are walked a second time and deposit w x length), width x height x spp paths on one device
+    struct Sensitivity {
+        int res[3]; float bmin[3], bmax[3];
+        std::vector<double> sums;               ///< raw sums J [nz][ny][nx][3]
+        double totals[16];                      ///< paths, detected weight x 3, dropped x 3, ended, detected paths, weight x length x 3, replay disagreements, 0 x 3 (mer_sensitivity_read)
+        /// J / paths, float32 [nz][ny][nx][3]: minus the derivative of the detected signal per path by the cell's sigma_a
+        std::vector<float> jacobian() const;
+    };
+    /// det: the detector (mer.h); its boundary is set to the scene's.  tBin = 0: no gate
+    Sensitivity renderSensitivity(const Scene &scene, int device, const int res[3], mer_detector_desc det, int spp, unsigned long long seed) const;
 private:
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
     void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;
@@ -293,6 +305,9 @@ void writeVol(const std::string &path, const float *data, int nx, int ny, int nz
 bool parseFluenceRes(const std::string &value, int res[3]);
 /// `mer_render --exitance=NU,NV`: two counts between 1 and 4096; false for anything else
 bool parseExitanceRes(const std::string &value, int res[2]);
+/// `mer_render --detector=FACE,NU,NV,IU0,IU1,IV0,IV1`: a face 0 ... 5, two counts between 1 and 4096 and a window 0 <= IU0 < IU1 <= NU,
+/// 0 <= IV0 < IV1 <= NV, into the face, res and window fields of det; false for anything else
+bool parseDetector(const std::string &value, mer_detector_desc &det);
 /// OpenEXR 2 scan-line file, uncompressed, three float32 channels B, G, R (what HDRFilm::develop writes through OpenEXR,
 /// src/films/hdrfilm.cpp:527; no OpenEXR library is needed for this subset)
 void writeExr(const std::string &path, const float *rgb, int h, int w);

@@ -1,6 +1,7 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,8 @@ int main(int argc, char **argv) {
     bool trackLength = false;      // --track-length: that grid from the track-length estimator (mer_fluence_track_create)
     int exitanceRes[2] = {0, 0}; bool exitance = false;                   // --exitance=NU,NV: the exitance map over the medium shape's boundary instead of the film
     float acceptCos = 0.0f; bool acceptCosSet = false;                    // --accept-cos=C: the acceptance cone of that map
+    int sensitivityRes[3] = {0, 0, 0}; bool sensitivity = false;          // --sensitivity=NX,NY,NZ: the sensitivity grid of a detector on the boundary instead of the film
+    mer_detector_desc detector; std::memset(&detector, 0, sizeof(detector)); bool detectorSet = false, gateSet = false;   // --detector=..., --gate=TMIN,TBIN
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -46,6 +49,21 @@ int main(int argc, char **argv) {
             if (!merhost::parseExitanceRes(a.substr(11), exitanceRes)) { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
             exitance = true;
         }
+        else if (a.rfind("--sensitivity=", 0) == 0) {
+            if (!merhost::parseFluenceRes(a.substr(14), sensitivityRes)) { std::fprintf(stderr, "--sensitivity=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+            sensitivity = true;
+        }
+        else if (a == "--sensitivity") { std::fprintf(stderr, "--sensitivity=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+        else if (a.rfind("--detector=", 0) == 0) {
+            if (!merhost::parseDetector(a.substr(11), detector)) { std::fprintf(stderr, "--detector=FACE,NU,NV,IU0,IU1,IV0,IV1 expects a face 0 ... 5, two cell counts between 1 and 4096 and a window 0 <= IU0 < IU1 <= NU, 0 <= IV0 < IV1 <= NV\n"); return 2; }
+            detectorSet = true;
+        }
+        else if (a.rfind("--gate=", 0) == 0) {
+            char *e = NULL, *e2 = NULL; detector.t_min = std::strtof(a.c_str() + 7, &e);
+            if (e != a.c_str() + 7 && *e == ',') detector.t_bin = std::strtof(e + 1, &e2);
+            if (!e2 || e2 == e + 1 || *e2 || !std::isfinite(detector.t_min) || !std::isfinite(detector.t_bin) || !(detector.t_bin > 0.0f)) { std::fprintf(stderr, "--gate=TMIN,TBIN expects a finite start and a width greater than 0, in optical path length\n"); return 2; }
+            gateSet = true;
+        }
         else if (a == "--exitance") { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
         else if (a.rfind("--accept-cos=", 0) == 0) {
             char *e = NULL; acceptCos = std::strtof(a.c_str() + 13, &e);
@@ -55,7 +73,7 @@ int main(int argc, char **argv) {
         else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--track-length") trackLength = true;
         else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -74,13 +92,24 @@ int main(int argc, char **argv) {
                                                          "  --exitance=NU,NV: a `ptracer` scene: instead of the film, where the light paths leave the medium: NU x NV cells on every face of the medium\n"
                                                          "  shape's boundary (cube: 6 faces, sphere: 1 face of equal-area cells), from width x height x spp light paths on one GPU; -o names a float32\n"
                                                          "  .npy [frames][faces][nv][nu][3] = sums / (paths x cell area [x binWidth]); the 16 totals are printed.  --time-resolved takes the window\n"
-                                                         "  from the film as for --fluence; --accept-cos=C bins only the exits within the cone cos >= C about the outward normal\n"); return 0; }
+                                                         "  from the film as for --fluence; --accept-cos=C bins only the exits within the cone cos >= C about the outward normal\n"
+                                                         "  --sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1: a `ptracer` scene: instead of the film, which part of the medium the light\n"
+                                                         "  that reached a detector travelled through (the absorption Jacobian).  The detector is the cell window IU0 <= iu < IU1, IV0 <= iv < IV1 on\n"
+                                                         "  face FACE of an --exitance raster of NU x NV cells; --accept-cos=C narrows it to a cone, --gate=TMIN,TBIN to the optical path lengths\n"
+                                                         "  TMIN <= l < TMIN + TBIN.  The detected paths are walked a second time and deposit weight x length on a grid of NX x NY x NZ cells over\n"
+                                                         "  the medium shape's bounding box; -o names a 3-channel float32 VOL of J / paths (minus the derivative of the detected signal per path by\n"
+                                                         "  a cell's sigma_a), laid out as --fluence lays its VOL out; the totals are printed.  One GPU; not with --fluence, --exitance, --gpus or --devices\n"); return 0; }
         else scenePath = a;
     }
     if (exitance && fluence) { std::fprintf(stderr, "--exitance and --fluence exclude each other: one map per run\n"); return 2; }
     if (exitance && multi) { std::fprintf(stderr, "--exitance runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
     if (exitance && trackLength) { std::fprintf(stderr, "--track-length belongs to --fluence=NX,NY,NZ: an exitance map has no track-length form\n"); return 2; }
-    if (acceptCosSet && !exitance) { std::fprintf(stderr, "--accept-cos needs --exitance=NU,NV\n"); return 2; }
+    if (sensitivity && (fluence || exitance)) { std::fprintf(stderr, "--sensitivity excludes --fluence and --exitance: one map per run\n"); return 2; }
+    if (sensitivity && multi) { std::fprintf(stderr, "--sensitivity runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
+    if (sensitivity && (timeResolved || trackLength)) { std::fprintf(stderr, "--time-resolved and --track-length belong to --fluence / --exitance: a sensitivity grid has the one gate of --gate=TMIN,TBIN\n"); return 2; }
+    if (sensitivity && !detectorSet) { std::fprintf(stderr, "--sensitivity needs --detector=FACE,NU,NV,IU0,IU1,IV0,IV1\n"); return 2; }
+    if ((detectorSet || gateSet) && !sensitivity) { std::fprintf(stderr, "--detector and --gate need --sensitivity=NX,NY,NZ\n"); return 2; }
+    if (acceptCosSet && !exitance && !sensitivity) { std::fprintf(stderr, "--accept-cos needs --exitance=NU,NV\n"); return 2; }
     if (exitance) {
         if (out == "out.npy") out = "exitance.npy";
         if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--exitance writes a .npy file ([frames][faces][nv][nu][3])\n"); return 2; }
@@ -110,6 +139,20 @@ int main(int argc, char **argv) {
                         x.totals[0], x.totals[1], x.totals[2], x.totals[3], x.totals[4], x.totals[5], x.totals[6], x.totals[7], x.totals[8], x.totals[9], x.totals[10],
                         x.totals[11], x.totals[12], x.totals[13], x.totals[14], x.totals[15]);
             std::printf("wrote %s (%d frames of %d faces of %dx%d cells)\n", out.c_str(), x.frames, x.faces, x.resU, x.resV);
+            return 0;
+        }
+        if (sensitivity) {
+            if (out == "out.npy") out = "sensitivity.vol";
+            detector.cos_min = acceptCos;
+            const merhost::Integrator::Sensitivity j = scene->integrator->renderSensitivity(*scene, device, sensitivityRes, detector, spp, seed);
+            const std::vector<float> v = j.jacobian();
+            float lo[3], hi[3];                      // the box of the cell centres
+            for (int k = 0; k < 3; k++) { const float half = 0.5f * (j.bmax[k] - j.bmin[k]) / (float) j.res[k]; lo[k] = j.bmin[k] + half; hi[k] = j.bmax[k] - half; }
+            merhost::writeVol(out, v.data(), j.res[0], j.res[1], j.res[2], 3, lo, hi);
+            std::printf("paths %.0f  detected weight %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f  detected %.0f  weight x length %.9g %.9g %.9g  disagreements %.0f\n",
+                        j.totals[0], j.totals[1], j.totals[2], j.totals[3], j.totals[4], j.totals[5], j.totals[6], j.totals[7], j.totals[8], j.totals[9], j.totals[10],
+                        j.totals[11], j.totals[12]);
+            std::printf("wrote %s (%dx%dx%d cells)\n", out.c_str(), j.res[0], j.res[1], j.res[2]);
             return 0;
         }
         if (fluence && timeResolved) {
