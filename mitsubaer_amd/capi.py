@@ -1,5 +1,6 @@
 """ctypes binding of libmer.so (include/mer.h): the HIP hot path.  No CPU fallback exists --
 loading fails loudly if the library is missing, and context creation fails without a GPU."""
+import collections
 import ctypes as C
 import os
 import numpy as np
@@ -378,9 +379,8 @@ def fluence_desc(res, bmin, bmax):
     return d
 
 
-def validate_fluence(desc):
-    """The refusals of mer_fluence_create, with its messages: MerError.  No GPU needed."""
-    at = "mer_fluence_create: "
+def _validate_box(desc, at):
+    """the box checks every voxel grid shares (res, bmin, bmax of desc), under the entry point's prefix"""
     cells = 1
     for a in range(3):
         if desc.res[a] < 1 or desc.res[a] > 1024:
@@ -392,6 +392,37 @@ def validate_fluence(desc):
         cells *= desc.res[a]
     if cells > 1 << 27:
         raise MerError(at + "more than 2^27 cells")
+
+
+def _validate_raster(t, at, res_what, frames):
+    """the raster / gate / cone checks an exitance map and a detector (one frame) share, under the entry point's prefix"""
+    if t.boundary not in (P.BOUNDARY_AABB, P.BOUNDARY_SPHERE):
+        raise MerError(at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)")
+    for a in range(2):
+        if t.res[a] < 1 or t.res[a] > 4096:
+            raise MerError(at + res_what + " must lie in 1 ... 4096 on both axes")
+    if frames < 1 or frames > 4096:
+        raise MerError(at + "frames must lie in 1 ... 4096")
+    if not np.isfinite(t.t_bin) or t.t_bin < 0:
+        raise MerError(at + "t_bin must be finite and at least 0")
+    if t.t_bin == 0 and frames != 1:
+        raise MerError(at + "a steady map (t_bin == 0) has one frame")
+    if not np.isfinite(t.t_min):
+        raise MerError(at + "t_min must be finite")
+    if not (t.cos_min >= 0 and t.cos_min < 1):
+        raise MerError(at + "cos_min must lie in 0 <= cos_min < 1")
+    if t.reserved != 0:
+        raise MerError(at + "reserved must be 0")
+
+
+def validate_fluence(desc):
+    """The refusals of mer_fluence_create, with its messages: MerError.  No GPU needed."""
+    _validate_box(desc, "mer_fluence_create: ")
+
+
+def validate_fluence_track(desc):
+    """The refusals of mer_fluence_track_create: the same checks under its own prefix"""
+    _validate_box(desc, "mer_fluence_track_create: ")
 
 
 class FluenceTimeDesc(C.Structure):
@@ -412,10 +443,7 @@ def fluence_time_desc(res, bmin, bmax, frames, t_min, t_bin):
 def validate_fluence_time(desc):
     """The refusals of mer_fluence_time_create, with its messages: MerError.  No GPU needed."""
     at = "mer_fluence_time_create: "
-    try:
-        validate_fluence(desc)                         # the box checks, unchanged
-    except MerError as e:
-        raise MerError(at + str(e)[len("mer_fluence_create: "):]) from None
+    _validate_box(desc, at)
     if desc.frames < 1 or desc.frames > 4096:
         raise MerError(at + "frames must lie in 1 ... 4096")
     if not np.isfinite(desc.t_min):
@@ -453,23 +481,7 @@ def exitance_faces(boundary):
 def validate_exitance(desc):
     """The refusals of mer_exitance_create, with its messages: MerError.  No GPU needed."""
     at = "mer_exitance_create: "
-    if desc.boundary not in (P.BOUNDARY_AABB, P.BOUNDARY_SPHERE):
-        raise MerError(at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)")
-    for a in range(2):
-        if desc.res[a] < 1 or desc.res[a] > 4096:
-            raise MerError(at + "res must lie in 1 ... 4096 on both axes")
-    if desc.frames < 1 or desc.frames > 4096:
-        raise MerError(at + "frames must lie in 1 ... 4096")
-    if not np.isfinite(desc.t_bin) or desc.t_bin < 0:
-        raise MerError(at + "t_bin must be finite and at least 0")
-    if desc.t_bin == 0 and desc.frames != 1:
-        raise MerError(at + "a steady map (t_bin == 0) has one frame")
-    if not np.isfinite(desc.t_min):
-        raise MerError(at + "t_min must be finite")
-    if not (desc.cos_min >= 0 and desc.cos_min < 1):
-        raise MerError(at + "cos_min must lie in 0 <= cos_min < 1")
-    if desc.reserved != 0:
-        raise MerError(at + "reserved must be 0")
+    _validate_raster(desc, at, "res", desc.frames)
     if desc.frames * exitance_faces(desc.boundary) * desc.res[0] * desc.res[1] > 1 << 27:
         raise MerError(at + "more than 2^27 cells x faces x frames")
 
@@ -512,30 +524,37 @@ def sensitivity_desc(res, bmin, bmax, detector):
 def validate_sensitivity(desc):
     """The refusals of mer_sensitivity_create, with its messages: MerError.  No GPU needed."""
     at = "mer_sensitivity_create: "
-    try:
-        validate_fluence(desc)                         # the box checks, unchanged
-    except MerError as e:
-        raise MerError(at + str(e)[len("mer_fluence_create: "):]) from None
+    _validate_box(desc, at)
     t = desc.det
-    if t.boundary not in (P.BOUNDARY_AABB, P.BOUNDARY_SPHERE):
-        raise MerError(at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)")
-    for a in range(2):
-        if t.res[a] < 1 or t.res[a] > 4096:
-            raise MerError(at + "detector res must lie in 1 ... 4096 on both axes")
-    if not np.isfinite(t.t_bin) or t.t_bin < 0:
-        raise MerError(at + "t_bin must be finite and at least 0")
-    if not np.isfinite(t.t_min):
-        raise MerError(at + "t_min must be finite")
-    if not (t.cos_min >= 0 and t.cos_min < 1):
-        raise MerError(at + "cos_min must lie in 0 <= cos_min < 1")
-    if t.reserved != 0:
-        raise MerError(at + "reserved must be 0")
+    _validate_raster(t, at, "detector res", 1)
     if t.face < 0 or t.face >= exitance_faces(t.boundary):
         raise MerError(at + "face must be one of the boundary's faces (0 ... 5 for the cube, 0 for the sphere)")
     if t.iu0 < 0 or t.iu1 > t.res[0] or t.iv0 < 0 or t.iv1 > t.res[1]:
         raise MerError(at + "the window must lie inside the raster (0 <= iu0, iu1 <= res[0], 0 <= iv0, iv1 <= res[1])")
     if not (t.iu0 < t.iu1 and t.iv0 < t.iv1):
         raise MerError(at + "the window is empty (iu0 < iu1 and iv0 < iv1 are required)")
+
+
+def _box_shape(d):
+    return (d.res[2], d.res[1], d.res[0])
+
+
+# The kinds of recorder a context hands out (Context._recorder_*): the family whose clear / destroy / render entry points take the handle
+# (mer_<family>_clear, mer_<family>_destroy, mer_render_<family>), the C create function, the desc builder, the validator, the read entry point
+# with its totals count, the shape of the sums (without the 3 channels) from the desc and what the family's other read says of this kind.
+# A new kind is one row here and the public methods that name it.
+_Recorder = collections.namedtuple("_Recorder", "family create desc validate read totals shape other_read")
+_RECORDERS = {
+    "fluence": _Recorder("fluence", "mer_fluence_create", fluence_desc, validate_fluence, "mer_fluence_read", 8, _box_shape,
+                         "mer_fluence_time_read: steady-state grid: use mer_fluence_read"),
+    "fluence_track": _Recorder("fluence", "mer_fluence_track_create", fluence_desc, validate_fluence_track, "mer_fluence_read", 8, _box_shape,
+                               "mer_fluence_time_read: steady-state grid: use mer_fluence_read"),
+    "fluence_time": _Recorder("fluence", "mer_fluence_time_create", fluence_time_desc, validate_fluence_time, "mer_fluence_time_read", 12,
+                              lambda d: (d.frames,) + _box_shape(d), "mer_fluence_read: time-resolved grid: use mer_fluence_time_read"),
+    "exitance": _Recorder("exitance", "mer_exitance_create", exitance_desc, validate_exitance, "mer_exitance_read", 16,
+                          lambda d: (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0]), None),
+    "sensitivity": _Recorder("sensitivity", "mer_sensitivity_create", sensitivity_desc, validate_sensitivity, "mer_sensitivity_read", 16, _box_shape, None),
+}
 
 
 def lib(path=None):
@@ -609,9 +628,7 @@ class Context:
             if rc != 0:
                 raise MerError(self.lib.mer_last_error(None).decode())
         self.device_id = device_id
-        self._fluence_res = {}                         # handle -> (nx, ny, nz) of the live fluence grids; a time-resolved one: (nx, ny, nz, frames)
-        self._exitance_shape = {}                      # handle -> (frames, faces, res_v, res_u) of the live exitance maps
-        self._sensitivity_res = {}                     # handle -> (nx, ny, nz) of the live sensitivity grids
+        self._recorders = {}                           # handle -> (kind in _RECORDERS, shape of its sums) of the live grids and maps
         for k, v in options.items():
             self.set_option(k, v)
 
@@ -872,78 +889,75 @@ class Context:
         finally:
             self.film_free(f)
 
+    # ---- what light paths record: fluence grids, exitance maps, sensitivity grids (one implementation over _RECORDERS) ----
+    def _recorder_create(self, kind, *args):
+        k = _RECORDERS[kind]
+        d = k.desc(*args)
+        k.validate(d)
+        h = C.c_int32()
+        self._check(getattr(self.lib, k.create)(self.h, C.byref(d), C.byref(h)))
+        self._recorders[h.value] = (kind, k.shape(d))
+        return h.value
+
+    def _recorder_clear(self, family, handle):
+        self._check(getattr(self.lib, "mer_%s_clear" % family)(self.h, C.c_int32(handle)))
+
+    def _recorder_destroy(self, family, handle):
+        self._check(getattr(self.lib, "mer_%s_destroy" % family)(self.h, C.c_int32(handle)))
+        self._recorders.pop(handle, None)
+
+    def _recorder_render(self, family, scene, handle, spp_begin, spp_count, seed, spp_stride, tile_rank, tile_count):
+        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
+        self._check(getattr(self.lib, "mer_render_%s" % family)(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+
+    def _recorder_read(self, kind, handle, sums):
+        """the read entry point of `kind` on the handle: (sums or None, totals).  The shape is the handle's own; one of another family, or of
+        the family's other read, is refused here as the library refuses it"""
+        k = _RECORDERS[kind]
+        totals = np.zeros(k.totals, np.float64)
+        out = None
+        if sums:
+            mine, shape = self._recorders.get(handle, (None, None))
+            if mine is None or _RECORDERS[mine].family != k.family:
+                raise MerError("%s: unknown %s handle" % (k.read, k.family))
+            if _RECORDERS[mine].read != k.read:
+                raise MerError(_RECORDERS[mine].other_read)
+            out = np.zeros(shape + (3,), np.float64)
+        self._check(getattr(self.lib, k.read)(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
+        return out, totals
+
     # ---- the fluence grid recorded from light paths (mer_render_fluence) ------------------------
     def fluence_create(self, res, bmin, bmax):
         """-> handle of a zeroed grid of res = (nx, ny, nz) cells over the box bmin ... bmax"""
-        d = fluence_desc(res, bmin, bmax)
-        validate_fluence(d)
-        h = C.c_int32()
-        self._check(self.lib.mer_fluence_create(self.h, C.byref(d), C.byref(h)))
-        self._fluence_res[h.value] = tuple(d.res)
-        return h.value
+        return self._recorder_create("fluence", res, bmin, bmax)
 
     def fluence_track_create(self, res, bmin, bmax):
         """-> handle of a zeroed track-length grid (mer_fluence_track_create): the layout of fluence_create, filled by the track-length
         estimator.  fluence_clear, fluence_destroy, render_fluence and fluence_read take it like a fluence_create handle."""
-        d = fluence_desc(res, bmin, bmax)
-        try:
-            validate_fluence(d)                            # the same checks, under the entry point's own prefix
-        except MerError as e:
-            raise MerError("mer_fluence_track_create: " + str(e)[len("mer_fluence_create: "):]) from None
-        h = C.c_int32()
-        self._check(self.lib.mer_fluence_track_create(self.h, C.byref(d), C.byref(h)))
-        self._fluence_res[h.value] = tuple(d.res)
-        return h.value
+        return self._recorder_create("fluence_track", res, bmin, bmax)
 
     def fluence_time_create(self, res, bmin, bmax, frames, t_min, t_bin):
         """-> handle of a zeroed time-resolved grid: the box of fluence_create, `frames` bins of width t_bin from t_min on in optical path
         length.  fluence_clear, fluence_destroy and render_fluence take it like any other fluence handle."""
-        d = fluence_time_desc(res, bmin, bmax, frames, t_min, t_bin)
-        validate_fluence_time(d)
-        h = C.c_int32()
-        self._check(self.lib.mer_fluence_time_create(self.h, C.byref(d), C.byref(h)))
-        self._fluence_res[h.value] = tuple(d.res) + (d.frames,)
-        return h.value
+        return self._recorder_create("fluence_time", res, bmin, bmax, frames, t_min, t_bin)
 
     def fluence_clear(self, handle):
-        self._check(self.lib.mer_fluence_clear(self.h, C.c_int32(handle)))
+        self._recorder_clear("fluence", handle)
 
     def fluence_destroy(self, handle):
-        self._check(self.lib.mer_fluence_destroy(self.h, C.c_int32(handle)))
-        self._fluence_res.pop(handle, None)
+        self._recorder_destroy("fluence", handle)
 
     def render_fluence(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
         """accumulates the light paths of the shard into the grid; returns synchronised"""
-        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
-        self._check(self.lib.mer_render_fluence(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+        self._recorder_render("fluence", scene, handle, spp_begin, spp_count, seed, spp_stride, tile_rank, tile_count)
 
     def fluence_read(self, handle, sums=True):
         """-> (raw sums float64 [nz][ny][nx][3], or None with sums = False; totals float64 [8])"""
-        totals = np.zeros(8, np.float64)
-        out = None
-        if sums:
-            res = self._fluence_res.get(handle)
-            if res is None:
-                raise MerError("mer_fluence_read: unknown fluence handle")
-            if len(res) == 4:
-                raise MerError("mer_fluence_read: time-resolved grid: use mer_fluence_time_read")
-            out = np.zeros((res[2], res[1], res[0], 3), np.float64)
-        self._check(self.lib.mer_fluence_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
-        return out, totals
+        return self._recorder_read("fluence", handle, sums)
 
     def fluence_time_read(self, handle, sums=True):
         """-> (raw sums float64 [frames][nz][ny][nx][3], or None with sums = False; totals float64 [12])"""
-        totals = np.zeros(12, np.float64)
-        out = None
-        if sums:
-            res = self._fluence_res.get(handle)
-            if res is None:
-                raise MerError("mer_fluence_time_read: unknown fluence handle")
-            if len(res) != 4:
-                raise MerError("mer_fluence_time_read: steady-state grid: use mer_fluence_read")
-            out = np.zeros((res[3], res[2], res[1], res[0], 3), np.float64)
-        self._check(self.lib.mer_fluence_time_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
-        return out, totals
+        return self._recorder_read("fluence_time", handle, sums)
 
     def _fluence_box(self, scene, bmin, bmax):
         """the box of a fluence map: the caller's, or the bounding box of the medium shape"""
@@ -1002,36 +1016,21 @@ class Context:
     # ---- the exitance map recorded from light paths (mer_render_exitance) -----------------------
     def exitance_create(self, boundary, res, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0):
         """-> handle of a zeroed map of res = (res_u, res_v) cells on every face of the boundary (P.BOUNDARY_AABB: 6, P.BOUNDARY_SPHERE: 1)"""
-        d = exitance_desc(boundary, res, frames, t_min, t_bin, cos_min)
-        validate_exitance(d)
-        h = C.c_int32()
-        self._check(self.lib.mer_exitance_create(self.h, C.byref(d), C.byref(h)))
-        self._exitance_shape[h.value] = (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0])
-        return h.value
+        return self._recorder_create("exitance", boundary, res, frames, t_min, t_bin, cos_min)
 
     def exitance_clear(self, handle):
-        self._check(self.lib.mer_exitance_clear(self.h, C.c_int32(handle)))
+        self._recorder_clear("exitance", handle)
 
     def exitance_destroy(self, handle):
-        self._check(self.lib.mer_exitance_destroy(self.h, C.c_int32(handle)))
-        self._exitance_shape.pop(handle, None)
+        self._recorder_destroy("exitance", handle)
 
     def render_exitance(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
         """accumulates the exits of the shard's light paths into the map; returns synchronised"""
-        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
-        self._check(self.lib.mer_render_exitance(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+        self._recorder_render("exitance", scene, handle, spp_begin, spp_count, seed, spp_stride, tile_rank, tile_count)
 
     def exitance_read(self, handle, sums=True):
         """-> (raw sums float64 [frames][faces][res_v][res_u][3], or None with sums = False; totals float64 [16])"""
-        totals = np.zeros(16, np.float64)
-        out = None
-        if sums:
-            shape = self._exitance_shape.get(handle)
-            if shape is None:
-                raise MerError("mer_exitance_read: unknown exitance handle")
-            out = np.zeros(shape + (3,), np.float64)
-        self._check(self.lib.mer_exitance_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
-        return out, totals
+        return self._recorder_read("exitance", handle, sums)
 
     def exitance(self, scene, res, spp_count, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0, seed=0, spp_begin=0):
         """One exitance map of the scene (integrator = ptracer) over the boundary of its medium shape: (raw sums float64
@@ -1046,36 +1045,21 @@ class Context:
     # ---- the sensitivity grid of a detector on the boundary (mer_render_sensitivity) ------------
     def sensitivity_create(self, res, bmin, bmax, detector):
         """-> handle of a zeroed grid of res = (nx, ny, nz) cells over the box bmin ... bmax for the detector (capi.detector_desc)"""
-        d = sensitivity_desc(res, bmin, bmax, detector)
-        validate_sensitivity(d)
-        h = C.c_int32()
-        self._check(self.lib.mer_sensitivity_create(self.h, C.byref(d), C.byref(h)))
-        self._sensitivity_res[h.value] = (d.res[0], d.res[1], d.res[2])
-        return h.value
+        return self._recorder_create("sensitivity", res, bmin, bmax, detector)
 
     def sensitivity_clear(self, handle):
-        self._check(self.lib.mer_sensitivity_clear(self.h, C.c_int32(handle)))
+        self._recorder_clear("sensitivity", handle)
 
     def sensitivity_destroy(self, handle):
-        self._check(self.lib.mer_sensitivity_destroy(self.h, C.c_int32(handle)))
-        self._sensitivity_res.pop(handle, None)
+        self._recorder_destroy("sensitivity", handle)
 
     def render_sensitivity(self, scene, handle, spp_begin, spp_count, seed=0, spp_stride=1, tile_rank=0, tile_count=1):
         """accumulates w x length of the shard's detected light paths into the grid; returns synchronised"""
-        sh = Shard(spp_begin, spp_count, spp_stride, tile_rank, tile_count)
-        self._check(self.lib.mer_render_sensitivity(self.h, C.byref(scene), C.byref(sh), C.c_uint64(seed), C.c_int32(handle)))
+        self._recorder_render("sensitivity", scene, handle, spp_begin, spp_count, seed, spp_stride, tile_rank, tile_count)
 
     def sensitivity_read(self, handle, sums=True):
         """-> (raw sums float64 [nz][ny][nx][3], or None with sums = False; totals float64 [16]: capi.SENSITIVITY_TOTALS)"""
-        totals = np.zeros(16, np.float64)
-        out = None
-        if sums:
-            res = self._sensitivity_res.get(handle)
-            if res is None:
-                raise MerError("mer_sensitivity_read: unknown sensitivity handle")
-            out = np.zeros((res[2], res[1], res[0], 3), np.float64)
-        self._check(self.lib.mer_sensitivity_read(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
-        return out, totals
+        return self._recorder_read("sensitivity", handle, sums)
 
     def sensitivity(self, scene, res, detector, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
         """One sensitivity map of the scene (integrator = ptracer) for a detector on the boundary of its medium shape (capi.detector_desc,

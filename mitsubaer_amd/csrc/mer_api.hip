@@ -174,9 +174,7 @@ void mer_context_destroy(mer_context *ctx) {
     if (ctx->ftable) (void) hipFree(ctx->ftable);
     if (ctx->etab) (void) hipFree(ctx->etab);
     for (auto &kv : ctx->envmaps) if (kv.second.dev) (void) hipFree(kv.second.dev);
-    for (auto &kv : ctx->fluences) if (kv.second.dev) (void) hipFree(kv.second.dev);
-    for (auto &kv : ctx->exitances) if (kv.second.dev) (void) hipFree(kv.second.dev);
-    for (auto &kv : ctx->sensitivities) if (kv.second.dev) (void) hipFree(kv.second.dev);
+    for (auto &kv : ctx->recorders) if (kv.second.dev) (void) hipFree(kv.second.dev);
     if (ctx->detect_list) (void) hipFree(ctx->detect_list);
     if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {

@@ -33,42 +33,28 @@ struct EnvMap {
     size_t off_cols = 0, off_rows = 0, off_weights = 0;
 };
 
-// a fluence grid (mer_fluence_create): one device buffer -- the sums double[nz][ny][nx][3], then the 8 totals.  Its handle shares the volumes' numbering.
-// A time-resolved grid (mer_fluence_time_create, frames > 0) is the second kind of the same handle: the sums double[frames][nz][ny][nx][3], then 12 totals.
-// A track-length grid (mer_fluence_track_create, kind = 1) is the third: the steady-state layout, filled by K_fluence_track (mer_fluence_track.hpp).
-struct Fluence {
-    mer_fluence_desc desc;
+// what a light-path render records into (mer_fluence_create / _track_create / _time_create, mer_exitance_create, mer_sensitivity_create): one device
+// buffer -- n_keys x 3 float64 sums, then n_totals totals -- and what the launch needs to fill it.  Handles share the volumes' numbering and one map;
+// the family decides which entry points know a handle (the other two families refuse it as unknown), the kind which kernel a fluence handle renders with.
+//   fluence      sums [frames][nz][ny][nx][3] over `box`, 8 totals; timed: frames > 0 bins of det.t_bin from det.t_min on, 12 totals; track: K_fluence_track
+//   exitance     sums [frames][faces][res_v][res_u][3], 16 totals: det holds the boundary, raster, window and cone
+//   sensitivity  sums [nz][ny][nx][3] over `box`, 16 totals: det is the detector
+enum { REC_FLUENCE = 0, REC_EXITANCE = 1, REC_SENSITIVITY = 2 };      // Recorder::family
+enum { REC_COLLISION = 0, REC_TRACK = 1, REC_TIMED = 2 };             // Recorder::kind (fluence; the other families have the first only)
+struct Recorder {
+    int32_t family = REC_FLUENCE, kind = REC_COLLISION;
+    mer_fluence_desc box{};
+    mer_detector_desc det{};
+    int32_t frames = 0;                          // 0: a steady-state fluence grid, a sensitivity grid
     double *dev = nullptr;
-    uint64_t n_cells = 0;
-    int32_t frames = 0;                          // 0: a steady-state grid
-    float t_min = 0, t_bin = 0;
-    int32_t kind = 0;                            // 0: deposits at the collisions; 1: a track-length grid (mer_fluence_track_create), steady-state only
-    bool timed() const { return frames > 0; }
-    bool track() const { return kind == 1; }
-    uint64_t n_keys() const { return n_cells * (uint64_t) (frames > 0 ? frames : 1); }
-    double *totals() const { return dev + n_keys() * 3; }
-    size_t bytes() const { return (n_keys() * 3 + (frames > 0 ? 12 : 8)) * sizeof(double); }
-};
-
-// an exitance map (mer_exitance_create): one device buffer -- the sums double[frames][faces][res_v][res_u][3], then the 16 totals.  Its handle shares
-// the volumes' numbering; the map is its own kind of handle, not a fluence grid's.
-struct Exitance {
-    mer_exitance_desc desc;
-    double *dev = nullptr;
-    int32_t faces() const { return desc.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
-    uint64_t n_keys() const { return (uint64_t) desc.frames * (uint64_t) faces() * (uint64_t) desc.res[1] * (uint64_t) desc.res[0]; }
-    double *totals() const { return dev + n_keys() * 3; }
-    size_t bytes() const { return (n_keys() * 3 + 16) * sizeof(double); }
-};
-
-// a sensitivity grid (mer_sensitivity_create): one device buffer -- the sums double[nz][ny][nx][3], then the 16 totals.  Its handle shares the
-// volumes' numbering; the grid is its own kind of handle, neither a fluence grid's nor an exitance map's.
-struct Sensitivity {
-    mer_sensitivity_desc desc;
-    double *dev = nullptr;
-    uint64_t n_keys() const { return (uint64_t) desc.res[0] * (uint64_t) desc.res[1] * (uint64_t) desc.res[2]; }
-    double *totals() const { return dev + n_keys() * 3; }
-    size_t bytes() const { return (n_keys() * 3 + 16) * sizeof(double); }
+    uint64_t n_keys = 0;
+    int32_t n_totals = 0;                        // as allocated: 8 or 12 (timed) for fluence, 16 for the others
+    bool timed() const { return kind == REC_TIMED; }
+    bool track() const { return kind == REC_TRACK; }
+    uint64_t n_cells() const { return (uint64_t) box.res[0] * (uint64_t) box.res[1] * (uint64_t) box.res[2]; }
+    int32_t faces() const { return det.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
+    double *totals() const { return dev + n_keys * 3; }
+    size_t bytes() const { return (n_keys * 3 + (uint64_t) n_totals) * sizeof(double); }
 };
 
 #define MER_MAX_PIPES 4
@@ -118,9 +104,7 @@ struct mer_context {
     std::string error;
     std::map<int, mer::Volume> volumes;
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
-    std::map<int, mer::Fluence> fluences;        // mer_fluence_create (handles from next_handle)
-    std::map<int, mer::Exitance> exitances;      // mer_exitance_create (handles from next_handle)
-    std::map<int, mer::Sensitivity> sensitivities;   // mer_sensitivity_create (handles from next_handle)
+    std::map<int, mer::Recorder> recorders;      // fluence grids, exitance maps, sensitivity grids (handles from next_handle)
     uint32_t *detect_list = nullptr; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 4 arrays of detect_cap words
     int next_handle = 1;
     unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
@@ -192,12 +176,8 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
 // mer_render_ptracer.hip: integrator = MER_INTEGRATOR_PTRACER -- one lane per light path, launched a fixed number of paths at a time
 int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, uint64_t n_film);
 
-// mer_render_fluence.hip: the fluence grid recorded from the same light paths (mer_render_fluence and the mer_fluence_* entry points)
-
-// mer_render_exitance.hip: the exitance map recorded from the same light paths (mer_render_exitance and the mer_exitance_* entry points)
-
-// mer_render_sensitivity.hip: the sensitivity grid of a detector on the boundary, two passes over the same light paths (mer_render_sensitivity
-// and the mer_sensitivity_* entry points)
+// mer_render_fluence.hip, mer_render_exitance.hip, mer_render_sensitivity.hip: what the same light paths record into a Recorder (above), each
+// family's kernels, launch and entry points; what they share is mer_lightpath_host.hpp
 
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
 // validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.

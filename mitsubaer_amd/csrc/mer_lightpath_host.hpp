@@ -1,6 +1,7 @@
 // mer_lightpath_host.hpp -- the host side every light-path kernel family shares (mer_render_ptracer.hip, mer_render_fluence.hip,
 // mer_render_fluence_track.hip, mer_render_exitance.hip, mer_render_sensitivity.hip): the choice among a family's 14 instantiations, the launch
-// loop over the work ids of a shard, and the device buffer behind a mer_fluence / mer_exitance / mer_sensitivity handle.
+// loop over the work ids of a shard, and the Recorder behind a mer_fluence / mer_exitance / mer_sensitivity handle: its description's checks,
+// its lookup by family, its device buffer and the shared opening of its launch.
 #pragma once
 #include "mer_internal.hpp"
 #include "mer_lightpath.hpp"
@@ -29,15 +30,24 @@ template <class F> static typename F::Kernel pick_light_kernel(const mer_scene_d
     return nullptr;
 }
 
-// ---- One render from light paths.  P is the caller's make_params(ctx, scene, P, false): each entry point makes it among refusals of its
-// own, in its own order (and the track-length grid has more to refuse between the checks and the launch), so the launcher comes in two steps.
-// The shard and the emitters:
+// ---- One render from light paths.  The launcher comes in two steps: open_light_paths makes P = make_params(ctx, scene, P, false) among the
+// refusals every recorder's launch shares, in their one order, and the launch follows once the caller has refused what is its own (the
+// track-length grid's analog requirement) and filled its kernel arguments.  The light tracer itself (launch_ptracer) has other refusals around
+// the same check of the shard and the emitters:
 static inline int check_light_paths(mer_context *ctx, const Params &P, const mer_shard *shard) {
     if (!shard || shard->spp_count < 0 || shard->spp_stride <= 0 || shard->tile_count <= 0 || shard->tile_rank < 0 ||
         shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
         return fail(ctx, "invalid shard");
     if (P.n_point <= 0) return fail(ctx, "ptracer: the scene has no emitter (list entries of kind point, spot or collimated)");
     return 0;
+}
+// not_ptracer / other_boundary: the entry point's own sentences; other_boundary = nullptr for a recorder without a boundary (the fluence grids)
+static inline int open_light_paths(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, const Recorder &R, Params &P,
+                                   const char *not_ptracer, const char *other_boundary) {
+    if (scene->integrator != MER_INTEGRATOR_PTRACER) return fail(ctx, not_ptracer);
+    if (make_params(ctx, scene, P, false)) return 1;
+    if (other_boundary && scene->boundary != R.det.boundary) return fail(ctx, other_boundary);
+    return check_light_paths(ctx, P, shard);
 }
 // The light paths of a shard are the (pixel, sample index) pairs K_gen would enumerate: the work ids are laid out as launch_render lays them
 // out (decode_work) and launched PT_PATHS_PER_LAUNCH (curved rays: PT_PATHS_PER_LAUNCH_CURVED) at a time on the context stream as
@@ -81,55 +91,93 @@ static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Par
     });
 }
 
-// ---- The box of a voxel grid over the medium (fluence grids, sensitivity grids): the checks of mer_fluence_create under the caller's prefix
-static inline int check_fluence_desc(mer_context *ctx, const mer_fluence_desc *d, const std::string &at = "mer_fluence_create: ") {
+// ---- The checks of a description, under the entry point's prefix.  The box of a voxel grid over the medium (fluence, sensitivity):
+static inline int check_box(mer_context *ctx, const std::string &at, const int32_t res[3], const float bmin[3], const float bmax[3]) {
     uint64_t cells = 1;
     for (int a = 0; a < 3; a++) {
-        if (d->res[a] < 1 || d->res[a] > 1024) return fail(ctx, at + "res must lie in 1 ... 1024 on every axis");
-        if (!std::isfinite(d->bmin[a]) || !std::isfinite(d->bmax[a])) return fail(ctx, at + "bmin / bmax must be finite");
-        if (!(d->bmin[a] < d->bmax[a])) return fail(ctx, at + "bmin must be below bmax on every axis");
-        cells *= (uint64_t) d->res[a];
+        if (res[a] < 1 || res[a] > 1024) return fail(ctx, at + "res must lie in 1 ... 1024 on every axis");
+        if (!std::isfinite(bmin[a]) || !std::isfinite(bmax[a])) return fail(ctx, at + "bmin / bmax must be finite");
+        if (!(bmin[a] < bmax[a])) return fail(ctx, at + "bmin must be below bmax on every axis");
+        cells *= (uint64_t) res[a];
     }
     if (cells > ((uint64_t) 1 << 27)) return fail(ctx, at + "more than 2^27 cells");
     return 0;
 }
+// The raster on the boundary, its gate and its cone (exitance maps; the detector of a sensitivity grid, which has one frame).  res_what: "res" / "detector res"
+static inline int check_raster(mer_context *ctx, const std::string &at, const char *res_what, const mer_detector_desc &t, int32_t frames) {
+    if (t.boundary != MER_BOUNDARY_AABB && t.boundary != MER_BOUNDARY_SPHERE) return fail(ctx, at + "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)");
+    for (int a = 0; a < 2; a++)
+        if (t.res[a] < 1 || t.res[a] > 4096) return fail(ctx, at + res_what + " must lie in 1 ... 4096 on both axes");
+    if (frames < 1 || frames > 4096) return fail(ctx, at + "frames must lie in 1 ... 4096");
+    if (!std::isfinite(t.t_bin) || t.t_bin < 0) return fail(ctx, at + "t_bin must be finite and at least 0");
+    if (t.t_bin == 0 && frames != 1) return fail(ctx, at + "a steady map (t_bin == 0) has one frame");
+    if (!std::isfinite(t.t_min)) return fail(ctx, at + "t_min must be finite");
+    if (!(t.cos_min >= 0 && t.cos_min < 1)) return fail(ctx, at + "cos_min must lie in 0 <= cos_min < 1");
+    if (t.reserved != 0) return fail(ctx, at + "reserved must be 0");
+    return 0;
+}
 
-// ---- The device buffer behind a handle H (Fluence, Exitance: mer_internal.hpp): n_keys() * 3 sums, then the totals, bytes() in all.
-// `what` names the kind of handle in messages ("fluence" / "exitance"); the two kinds keep a map each, so a handle of one is unknown to the other.
-template <class H> static H *find_sums(mer_context *ctx, std::map<int, H> &handles, int h, const char *who, const char *what) {
-    auto it = handles.find(h);
-    if (it == handles.end()) { ctx->error = std::string(who) + ": unknown " + what + " handle"; return nullptr; }
+// ---- The Recorder behind a handle (mer_internal.hpp).  Every entry point opens with one of these two: false / nullptr means return 1 (the
+// message is set unless ctx is null).  create_args: the arguments of a *_create.
+static inline bool create_args(mer_context *ctx, const void *desc, int *out, const char *who) {
+    if (!ctx) return false;
+    (void) hipSetDevice(ctx->device);
+    if (!desc || !out) { ctx->error = std::string(who) + ": invalid arguments"; return false; }
+    *out = 0;
+    return true;
+}
+// find_recorder: the handle, which must be of the entry point's family -- one of another is as unknown as a number never issued.
+// has_scene: the render entry points pass scene != nullptr
+static inline Recorder *find_recorder(mer_context *ctx, int h, int family, const char *who, bool has_scene = true) {
+    static const char *const names[3] = {"fluence", "exitance", "sensitivity"};
+    if (!ctx) return nullptr;
+    (void) hipSetDevice(ctx->device);
+    if (!has_scene) { ctx->error = std::string(who) + ": no scene"; return nullptr; }
+    auto it = ctx->recorders.find(h);
+    if (it == ctx->recorders.end() || it->second.family != family) { ctx->error = std::string(who) + ": unknown " + names[family] + " handle"; return nullptr; }
     return &it->second;
 }
-// the zeroed buffer of a checked description and its handle
-template <class H> static int alloc_sums(mer_context *ctx, std::map<int, H> &handles, H &v, const std::string &clearing_failed, int *out) {
+// the zeroed buffer of a checked description (family, kind, n_keys and n_totals set) and its handle
+static inline int alloc_sums(mer_context *ctx, Recorder &v, const std::string &clearing_failed, int *out) {
     HIP_CHECK(ctx, hipMalloc((void **) &v.dev, v.bytes()));
     if (hipMemsetAsync(v.dev, 0, v.bytes(), ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
         (void) hipFree(v.dev);
         return fail(ctx, clearing_failed);
     }
     const int h = ctx->next_handle++;
-    handles[h] = v;
+    ctx->recorders[h] = v;
     *out = h;
     return 0;
 }
-template <class H> static int clear_sums(mer_context *ctx, const H &v) {
-    HIP_CHECK(ctx, hipMemsetAsync(v.dev, 0, v.bytes(), ctx->stream));
+static inline int clear_sums(mer_context *ctx, const Recorder *v) {
+    if (!v) return 1;
+    HIP_CHECK(ctx, hipMemsetAsync(v->dev, 0, v->bytes(), ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
-template <class H> static int destroy_sums(mer_context *ctx, std::map<int, H> &handles, int h, const H &v) {
+static inline int destroy_sums(mer_context *ctx, int h, const Recorder *v) {
+    if (!v) return 1;
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void) hipFree(v.dev);
-    handles.erase(h);
+    (void) hipFree(v->dev);
+    ctx->recorders.erase(h);
     return 0;
 }
-// sums (optional) and the first n_totals totals
-template <class H> static int read_sums(mer_context *ctx, const H &v, double *sums, double *totals, int n_totals) {
+// sums (optional) and the totals, n_totals of them
+static inline int read_sums(mer_context *ctx, const Recorder &v, double *sums, double *totals, const char *who) {
+    if (!totals) return fail(ctx, std::string(who) + ": invalid arguments");
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (sums) HIP_CHECK(ctx, hipMemcpy(sums, v.dev, v.n_keys() * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_CHECK(ctx, hipMemcpy(totals, v.totals(), (size_t) n_totals * sizeof(double), hipMemcpyDeviceToHost));
+    if (sums) HIP_CHECK(ctx, hipMemcpy(sums, v.dev, v.n_keys * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(totals, v.totals(), (size_t) v.n_totals * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+// the voxel grid K_fluence, K_fluence_track and K_replay deposit into: the recorder's box, and the time bins of a timed fluence grid
+// (Grid = FluenceGrid, mer_fluence.hpp, which only the translation units of those kernels include)
+template <class Grid> static Grid fluence_grid(const mer_context *ctx, const Recorder &R) {
+    Grid G;
+    G.sums = R.dev; G.totals = R.totals(); G.chk = ctx->chk; G.n_cells = R.n_cells();
+    G.frames = R.timed() ? R.frames : 0; G.t_min = R.timed() ? R.det.t_min : 0; G.t_bin = R.timed() ? R.det.t_bin : 0;
+    for (int a = 0; a < 3; a++) { G.res[a] = R.box.res[a]; G.bmin[a] = R.box.bmin[a]; G.bmax[a] = R.box.bmax[a]; }
+    return G;
 }
 
 }  // namespace mer

@@ -1119,41 +1119,57 @@ std::vector<float> Integrator::render(const Scene &scene, const std::vector<int>
     return film;
 }
 
-// The fluence grid of a `ptracer` scene: one context (a mer_multi of one device, for the uploads it shares with render()), one grid over the
-// medium shape's bounding box, width x height x spp light paths.
+// One session of what a `ptracer` scene's light paths record (renderFluence, renderExitance, renderSensitivity): the flattened scene, one context
+// (a mer_multi of one device, for the uploads it shares with render()) with the media uploaded, and the shard of the whole image at `spp`
+// samples.  The mer_multi, and with it whatever was created in its context, is destroyed on every path out, a thrown Log_EError included.
+struct Integrator::LightPathSession {
+    mer_scene_desc d;
+    mer_multi *mm = NULL;
+    mer_context *ctx = NULL;
+    mer_shard whole;
+    // notPtracer: the caller's sentence for any other integrator
+    LightPathSession(const Integrator &integrator, const Scene &scene, int device, int spp, const char *notPtracer) {
+        if (integrator.kind != MER_INTEGRATOR_PTRACER) Log_EError(notPtracer);
+        integrator.flatten(scene, d);
+        whole = {0, spp <= 0 ? scene.sensor->sampler->sampleCount : spp, 1, 0, 1};
+        const int32_t id = device;
+        if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
+        integrator.uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);       // destroys mm itself before it throws: nothing to destroy here then
+        ctx = mer_multi_context(mm, 0);
+    }
+    ~LightPathSession() { mer_multi_destroy(mm); }
+    LightPathSession(const LightPathSession &) = delete;
+    [[noreturn]] void fail() const { Log_EError(mer_last_error(ctx)); }
+    // the bounding box of the medium shape
+    void boundingBox(float bmin[3], float bmax[3]) const {
+        for (int a = 0; a < 3; a++) {
+            bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
+            bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
+        }
+    }
+};
+
+// The fluence grid of a `ptracer` scene: one grid over the medium shape's bounding box, width x height x spp light paths.
 Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int spp, unsigned long long seed, bool trackLength) const {
     return renderFluence(scene, device, res, 0, 0.0f, 0.0f, spp, seed, trackLength);
 }
 // frames = 0: the steady-state grid (trackLength: the track-length estimator's); frames > 0: the time-resolved one
 Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed, bool trackLength) const {
-    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
-    if (trackLength && frames > 0) Log_EError("a time-resolved track-length grid does not exist: the track-length estimator fills a steady-state grid");
-    mer_scene_desc d;
-    flatten(scene, d);
-    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    // (another integrator is refused first, by the session)
+    if (kind == MER_INTEGRATOR_PTRACER && trackLength && frames > 0) Log_EError("a time-resolved track-length grid does not exist: the track-length estimator fills a steady-state grid");
+    LightPathSession s(*this, scene, device, spp, "the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
     Fluence out;
+    s.boundingBox(out.bmin, out.bmax);
     mer_fluence_desc fd;
     mer_fluence_time_desc td;
-    for (int a = 0; a < 3; a++) {
-        td.res[a] = fd.res[a] = out.res[a] = res[a];
-        td.bmin[a] = fd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
-        td.bmax[a] = fd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
-    }
+    for (int a = 0; a < 3; a++) { td.res[a] = fd.res[a] = out.res[a] = res[a]; td.bmin[a] = fd.bmin[a] = out.bmin[a]; td.bmax[a] = fd.bmax[a] = out.bmax[a]; }
     td.frames = out.frames = frames; td.t_min = out.tMin = tMin; td.t_bin = out.tBin = tBin; td.reserved = 0;
-    mer_multi *mm = NULL;
-    const int32_t id = device;
-    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
-    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
-    mer_context *ctx = mer_multi_context(mm, 0);
-    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
     mer_fluence f = 0;
-    if (frames > 0 ? mer_fluence_time_create(ctx, &td, &f) : trackLength ? mer_fluence_track_create(ctx, &fd, &f) : mer_fluence_create(ctx, &fd, &f)) fail();
-    const mer_shard whole = {0, spp, 1, 0, 1};
-    if (mer_render_fluence(ctx, &d, &whole, seed, f)) fail();
+    if (frames > 0 ? mer_fluence_time_create(s.ctx, &td, &f) : trackLength ? mer_fluence_track_create(s.ctx, &fd, &f) : mer_fluence_create(s.ctx, &fd, &f)) s.fail();
+    if (mer_render_fluence(s.ctx, &s.d, &s.whole, seed, f)) s.fail();
     out.sums.resize((size_t) (frames > 0 ? frames : 1) * res[0] * res[1] * res[2] * 3);
     for (int q = 8; q < 12; q++) out.totals[q] = 0.0;
-    if (frames > 0 ? mer_fluence_time_read(ctx, f, out.sums.data(), out.totals) : mer_fluence_read(ctx, f, out.sums.data(), out.totals)) fail();
-    mer_multi_destroy(mm);                     // frees the grid with its context
+    if (frames > 0 ? mer_fluence_time_read(s.ctx, f, out.sums.data(), out.totals) : mer_fluence_read(s.ctx, f, out.sums.data(), out.totals)) s.fail();
     return out;
 }
 std::vector<float> Integrator::Fluence::phi() const {
@@ -1165,26 +1181,28 @@ std::vector<float> Integrator::Fluence::phi() const {
     for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
     return v;
 }
-bool parseFluenceRes(const std::string &value, int res[3]) {
+// `value` as exactly n comma-separated counts of at most four digits each (no sign, no spaces), every one within lo ... hi
+static bool parseCounts(const std::string &value, int n, int lo, int hi, int *v) {
     size_t p = 0;
-    for (int a = 0; a < 3; a++) {
-        size_t e = a < 2 ? value.find(',', p) : value.size();
+    for (int a = 0; a < n; a++) {
+        size_t e = a < n - 1 ? value.find(',', p) : value.size();
         if (e == std::string::npos || e == p) return false;
         const std::string tok = value.substr(p, e - p);
         if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
-        res[a] = std::atoi(tok.c_str());
-        if (res[a] < 1 || res[a] > 1024) return false;
+        v[a] = std::atoi(tok.c_str());
+        if (v[a] < lo || v[a] > hi) return false;
         p = e + 1;
     }
-    return (long long) res[0] * res[1] * res[2] <= (1LL << 27);
+    return true;
+}
+bool parseFluenceRes(const std::string &value, int res[3]) {
+    return parseCounts(value, 3, 1, 1024, res) && (long long) res[0] * res[1] * res[2] <= (1LL << 27);
 }
 
-// The exitance map of a `ptracer` scene: one context (a mer_multi of one device, as renderFluence), one map over the medium shape's boundary
+// The exitance map of a `ptracer` scene: one map over the medium shape's boundary
 Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const {
-    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the exitance map is recorded from light paths: the scene's integrator must be \"ptracer\"");
-    mer_scene_desc d;
-    flatten(scene, d);
-    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    LightPathSession s(*this, scene, device, spp, "the exitance map is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    const mer_scene_desc &d = s.d;
     Exitance out;
     mer_exitance_desc ed;
     ed.boundary = out.boundary = d.boundary;
@@ -1196,19 +1214,11 @@ Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, 
         out.cellArea[f] = d.boundary == MER_BOUNDARY_SPHERE ? 4.0 * M_PI * (double) d.sph_radius * (double) d.sph_radius / ((double) res[0] * res[1])
                                                             : ((double) d.bmax[ua] - (double) d.bmin[ua]) * ((double) d.bmax[va] - (double) d.bmin[va]) / ((double) res[0] * res[1]);
     }
-    mer_multi *mm = NULL;
-    const int32_t id = device;
-    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
-    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
-    mer_context *ctx = mer_multi_context(mm, 0);
-    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
     mer_exitance e = 0;
-    if (mer_exitance_create(ctx, &ed, &e)) fail();
-    const mer_shard whole = {0, spp, 1, 0, 1};
-    if (mer_render_exitance(ctx, &d, &whole, seed, e)) fail();
+    if (mer_exitance_create(s.ctx, &ed, &e)) s.fail();
+    if (mer_render_exitance(s.ctx, &d, &s.whole, seed, e)) s.fail();
     out.sums.resize((size_t) frames * out.faces * res[1] * res[0] * 3);
-    if (mer_exitance_read(ctx, e, out.sums.data(), out.totals)) fail();
-    mer_multi_destroy(mm);                     // frees the map with its context
+    if (mer_exitance_read(s.ctx, e, out.sums.data(), out.totals)) s.fail();
     return out;
 }
 std::vector<float> Integrator::Exitance::exitance() const {
@@ -1221,48 +1231,22 @@ std::vector<float> Integrator::Exitance::exitance() const {
     }
     return v;
 }
-bool parseExitanceRes(const std::string &value, int res[2]) {
-    size_t p = 0;
-    for (int a = 0; a < 2; a++) {
-        size_t e = a < 1 ? value.find(',', p) : value.size();
-        if (e == std::string::npos || e == p) return false;
-        const std::string tok = value.substr(p, e - p);
-        if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
-        res[a] = std::atoi(tok.c_str());
-        if (res[a] < 1 || res[a] > 4096) return false;
-        p = e + 1;
-    }
-    return true;
-}
+bool parseExitanceRes(const std::string &value, int res[2]) { return parseCounts(value, 2, 1, 4096, res); }
 
-// The sensitivity grid of a `ptracer` scene: one context (a mer_multi of one device, as renderFluence), one grid over the medium shape's bounding box
+// The sensitivity grid of a `ptracer` scene: one grid over the medium shape's bounding box (the detected-path list goes with the context)
 Integrator::Sensitivity Integrator::renderSensitivity(const Scene &scene, int device, const int res[3], mer_detector_desc det, int spp, unsigned long long seed) const {
-    if (kind != MER_INTEGRATOR_PTRACER) Log_EError("the sensitivity grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
-    mer_scene_desc d;
-    flatten(scene, d);
-    if (spp <= 0) spp = scene.sensor->sampler->sampleCount;
+    LightPathSession s(*this, scene, device, spp, "the sensitivity grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
     Sensitivity out;
+    s.boundingBox(out.bmin, out.bmax);
     mer_sensitivity_desc sd;
-    for (int a = 0; a < 3; a++) {
-        sd.res[a] = out.res[a] = res[a];
-        sd.bmin[a] = out.bmin[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] - d.sph_radius : d.bmin[a];
-        sd.bmax[a] = out.bmax[a] = d.boundary == MER_BOUNDARY_SPHERE ? d.sph_center[a] + d.sph_radius : d.bmax[a];
-    }
-    det.boundary = d.boundary; det.reserved = 0;
+    for (int a = 0; a < 3; a++) { sd.res[a] = out.res[a] = res[a]; sd.bmin[a] = out.bmin[a]; sd.bmax[a] = out.bmax[a]; }
+    det.boundary = s.d.boundary; det.reserved = 0;
     sd.det = det;
-    mer_multi *mm = NULL;
-    const int32_t id = device;
-    if (mer_multi_create(&id, 1, &mm)) Log_EError(mer_multi_last_error(NULL));
-    uploadMedia(scene, mm, d, MER_LAYOUT_DENSE);
-    mer_context *ctx = mer_multi_context(mm, 0);
-    auto fail = [&](void) { std::string msg = mer_last_error(ctx); mer_multi_destroy(mm); Log_EError(msg); };
-    mer_sensitivity s = 0;
-    if (mer_sensitivity_create(ctx, &sd, &s)) fail();
-    const mer_shard whole = {0, spp, 1, 0, 1};
-    if (mer_render_sensitivity(ctx, &d, &whole, seed, s)) fail();
+    mer_sensitivity j = 0;
+    if (mer_sensitivity_create(s.ctx, &sd, &j)) s.fail();
+    if (mer_render_sensitivity(s.ctx, &s.d, &s.whole, seed, j)) s.fail();
     out.sums.resize((size_t) res[0] * res[1] * res[2] * 3);
-    if (mer_sensitivity_read(ctx, s, out.sums.data(), out.totals)) fail();
-    mer_multi_destroy(mm);                     // frees the grid and the detected-path list with its context
+    if (mer_sensitivity_read(s.ctx, j, out.sums.data(), out.totals)) s.fail();
     return out;
 }
 std::vector<float> Integrator::Sensitivity::jacobian() const {
@@ -1272,15 +1256,8 @@ std::vector<float> Integrator::Sensitivity::jacobian() const {
     return v;
 }
 bool parseDetector(const std::string &value, mer_detector_desc &det) {
-    int v[7]; size_t p = 0;
-    for (int a = 0; a < 7; a++) {
-        size_t e = a < 6 ? value.find(',', p) : value.size();
-        if (e == std::string::npos || e == p) return false;
-        const std::string tok = value.substr(p, e - p);
-        if (tok.size() > 4 || tok.find_first_not_of("0123456789") != std::string::npos) return false;
-        v[a] = std::atoi(tok.c_str());
-        p = e + 1;
-    }
+    int v[7];
+    if (!parseCounts(value, 7, 0, 9999, v)) return false;
     if (v[0] > 5 || v[1] < 1 || v[1] > 4096 || v[2] < 1 || v[2] > 4096) return false;
     if (!(v[3] < v[4] && v[4] <= v[1] && v[5] < v[6] && v[6] <= v[2])) return false;
     det.face = v[0]; det.res[0] = v[1]; det.res[1] = v[2]; det.iu0 = v[3]; det.iu1 = v[4]; det.iv0 = v[5]; det.iv1 = v[6];

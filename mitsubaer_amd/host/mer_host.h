@@ -271,6 +271,7 @@ public:
     /// det: the detector (mer.h); its boundary is set to the scene's.  tBin = 0: no gate
     Sensitivity renderSensitivity(const Scene &scene, int device, const int res[3], mer_detector_desc det, int spp, unsigned long long seed) const;
 private:
+    struct LightPathSession;                    ///< mer_host.cpp: the one-device session the three recorders above share
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws
     void uploadMedia(const Scene &scene, mer_multi *mm, mer_scene_desc &d, int layout) const;
 };

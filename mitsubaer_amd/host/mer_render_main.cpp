@@ -6,6 +6,20 @@
 #include <cstdlib>
 #include <cstring>
 
+// the window of --time-resolved: the film's transient window (minBound, binWidth, ceil((maxBound - minBound) / binWidth) frames)
+struct Window { int frames; float tMin, tBin; };
+static Window filmWindow(const merhost::Scene &scene) {
+    const merhost::Film &film = *scene.sensor->film;
+    if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
+    return {(int) std::ceil((film.maxBound - film.minBound) / film.binWidth), film.minBound, film.binWidth};
+}
+// a VOL of cell values: its box is that of the cell centres, so that a gridvolume reading it interpolates between them
+static void writeCellVol(const std::string &path, const std::vector<float> &v, const int res[3], const float bmin[3], const float bmax[3]) {
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; k++) { const float half = 0.5f * (bmax[k] - bmin[k]) / (float) res[k]; lo[k] = bmin[k] + half; hi[k] = bmax[k] - half; }
+    merhost::writeVol(path, v.data(), res[0], res[1], res[2], 3, lo, hi);
+}
+
 int main(int argc, char **argv) {
     std::map<std::string, std::string> defines;
     std::string out = "out.npy", scenePath;
@@ -41,19 +55,18 @@ int main(int argc, char **argv) {
             if (e == a.c_str() + 11 || *e || n < 2 || n > 4096) { std::fprintf(stderr, "--mesh-sdf=N expects a node count between 2 and 4096\n"); return 2; }
             meshSdf = (int) n;
         }
-        else if (a.rfind("--fluence=", 0) == 0) {
-            if (!merhost::parseFluenceRes(a.substr(10), fluenceRes)) { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+        else if (a == "--fluence" || a.rfind("--fluence=", 0) == 0) {
+            if (a.size() < 10 || !merhost::parseFluenceRes(a.substr(10), fluenceRes)) { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
             fluence = true;
         }
-        else if (a.rfind("--exitance=", 0) == 0) {
-            if (!merhost::parseExitanceRes(a.substr(11), exitanceRes)) { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
+        else if (a == "--exitance" || a.rfind("--exitance=", 0) == 0) {
+            if (a.size() < 11 || !merhost::parseExitanceRes(a.substr(11), exitanceRes)) { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
             exitance = true;
         }
-        else if (a.rfind("--sensitivity=", 0) == 0) {
-            if (!merhost::parseFluenceRes(a.substr(14), sensitivityRes)) { std::fprintf(stderr, "--sensitivity=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
+        else if (a == "--sensitivity" || a.rfind("--sensitivity=", 0) == 0) {
+            if (a.size() < 14 || !merhost::parseFluenceRes(a.substr(14), sensitivityRes)) { std::fprintf(stderr, "--sensitivity=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
             sensitivity = true;
         }
-        else if (a == "--sensitivity") { std::fprintf(stderr, "--sensitivity=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
         else if (a.rfind("--detector=", 0) == 0) {
             if (!merhost::parseDetector(a.substr(11), detector)) { std::fprintf(stderr, "--detector=FACE,NU,NV,IU0,IU1,IV0,IV1 expects a face 0 ... 5, two cell counts between 1 and 4096 and a window 0 <= IU0 < IU1 <= NU, 0 <= IV0 < IV1 <= NV\n"); return 2; }
             detectorSet = true;
@@ -64,7 +77,6 @@ int main(int argc, char **argv) {
             if (!e2 || e2 == e + 1 || *e2 || !std::isfinite(detector.t_min) || !std::isfinite(detector.t_bin) || !(detector.t_bin > 0.0f)) { std::fprintf(stderr, "--gate=TMIN,TBIN expects a finite start and a width greater than 0, in optical path length\n"); return 2; }
             gateSet = true;
         }
-        else if (a == "--exitance") { std::fprintf(stderr, "--exitance=NU,NV expects two cell counts between 1 and 4096\n"); return 2; }
         else if (a.rfind("--accept-cos=", 0) == 0) {
             char *e = NULL; acceptCos = std::strtof(a.c_str() + 13, &e);
             if (e == a.c_str() + 13 || *e || !(acceptCos >= 0.0f && acceptCos < 1.0f)) { std::fprintf(stderr, "--accept-cos=C expects a cosine with 0 <= C < 1\n"); return 2; }
@@ -72,7 +84,6 @@ int main(int argc, char **argv) {
         }
         else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--track-length") trackLength = true;
-        else if (a == "--fluence") { std::fprintf(stderr, "--fluence=NX,NY,NZ expects three cell counts between 1 and 1024 (at most 2^27 cells)\n"); return 2; }
         else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
@@ -126,13 +137,8 @@ int main(int argc, char **argv) {
     try {
         auto scene = merhost::loadScene(scenePath, defines);
         if (exitance) {
-            int frames = 1; float tMin = 0.0f, tBin = 0.0f;
-            if (timeResolved) {
-                const merhost::Film &film = *scene->sensor->film;
-                if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
-                frames = (int) std::ceil((film.maxBound - film.minBound) / film.binWidth); tMin = film.minBound; tBin = film.binWidth;
-            }
-            const merhost::Integrator::Exitance x = scene->integrator->renderExitance(*scene, device, exitanceRes, frames, tMin, tBin, acceptCos, spp, seed);
+            const Window w = timeResolved ? filmWindow(*scene) : Window{1, 0.0f, 0.0f};
+            const merhost::Integrator::Exitance x = scene->integrator->renderExitance(*scene, device, exitanceRes, w.frames, w.tMin, w.tBin, acceptCos, spp, seed);
             const std::vector<float> m = x.exitance();
             merhost::writeNpy(out, m.data(), std::vector<int>{x.frames, x.faces, x.resV, x.resU, 3});
             std::printf("paths %.0f  escaped %.9g %.9g %.9g  missed %.9g %.9g %.9g  ended %.0f  late %.9g %.9g %.9g  rejected %.9g %.9g %.9g  binned %.0f  %.0f\n",
@@ -146,9 +152,7 @@ int main(int argc, char **argv) {
             detector.cos_min = acceptCos;
             const merhost::Integrator::Sensitivity j = scene->integrator->renderSensitivity(*scene, device, sensitivityRes, detector, spp, seed);
             const std::vector<float> v = j.jacobian();
-            float lo[3], hi[3];                      // the box of the cell centres
-            for (int k = 0; k < 3; k++) { const float half = 0.5f * (j.bmax[k] - j.bmin[k]) / (float) j.res[k]; lo[k] = j.bmin[k] + half; hi[k] = j.bmax[k] - half; }
-            merhost::writeVol(out, v.data(), j.res[0], j.res[1], j.res[2], 3, lo, hi);
+            writeCellVol(out, v, j.res, j.bmin, j.bmax);
             std::printf("paths %.0f  detected weight %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f  detected %.0f  weight x length %.9g %.9g %.9g  disagreements %.0f\n",
                         j.totals[0], j.totals[1], j.totals[2], j.totals[3], j.totals[4], j.totals[5], j.totals[6], j.totals[7], j.totals[8], j.totals[9], j.totals[10],
                         j.totals[11], j.totals[12]);
@@ -156,10 +160,8 @@ int main(int argc, char **argv) {
             return 0;
         }
         if (fluence && timeResolved) {
-            const merhost::Film &film = *scene->sensor->film;
-            if (film.decomposition != MER_DECOMPOSITION_TRANSIENT) merhost::Log_EError("--time-resolved takes its window from the film: the film needs decomposition = transient");
-            const int frames = (int) std::ceil((film.maxBound - film.minBound) / film.binWidth);
-            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, frames, film.minBound, film.binWidth, spp, seed);
+            const Window w = filmWindow(*scene);
+            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, w.frames, w.tMin, w.tBin, spp, seed);
             const std::vector<float> phi = f.phi();
             merhost::writeNpy(out, phi.data(), std::vector<int>{f.frames, f.res[2], f.res[1], f.res[0], 3});
             std::printf("paths %.0f  escaped %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f  out of window %.9g %.9g %.9g\n", f.totals[0], f.totals[1], f.totals[2],
@@ -171,9 +173,7 @@ int main(int argc, char **argv) {
             if (out == "out.npy") out = "fluence.vol";
             const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, spp, seed, trackLength);
             const std::vector<float> phi = f.phi();
-            float lo[3], hi[3];                      // the box of the cell centres
-            for (int k = 0; k < 3; k++) { const float half = 0.5f * (f.bmax[k] - f.bmin[k]) / (float) f.res[k]; lo[k] = f.bmin[k] + half; hi[k] = f.bmax[k] - half; }
-            merhost::writeVol(out, phi.data(), f.res[0], f.res[1], f.res[2], 3, lo, hi);
+            writeCellVol(out, phi, f.res, f.bmin, f.bmax);
             std::printf("paths %.0f  escaped %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f\n", f.totals[0], f.totals[1], f.totals[2], f.totals[3],
                         f.totals[4], f.totals[5], f.totals[6], f.totals[7]);
             std::printf("wrote %s (%dx%dx%d cells)\n", out.c_str(), f.res[0], f.res[1], f.res[2]);

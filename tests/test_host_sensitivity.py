@@ -133,3 +133,39 @@ def test_mer_render_usage_names_the_option_and_what_it_excludes():
     assert r.returncode == 0
     assert "--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]" in r.stdout
     assert "not with --fluence, --exitance, --gpus or --devices" in r.stdout
+
+
+# the box checks are one helper under the caller's prefix: each composed form says its own entry point's name, once, and no other's
+BOX_REFUSALS = [(dict(res=(0, 8, 8)), "res must lie in 1 ... 1024 on every axis"), (dict(bmin=(-1, float("nan"), -1)), "bmin / bmax must be finite"),
+                (dict(bmin=(-1, 1, -1)), "bmin must be below bmax on every axis"), (dict(res=(1024, 1024, 256)), "more than 2^27 cells")]
+COMPOSED = {
+    "mer_fluence_create": lambda res, bmin, bmax: capi.validate_fluence(capi.fluence_desc(res, bmin, bmax)),
+    "mer_fluence_track_create": lambda res, bmin, bmax: capi.validate_fluence_track(capi.fluence_desc(res, bmin, bmax)),
+    "mer_fluence_time_create": lambda res, bmin, bmax: capi.validate_fluence_time(capi.fluence_time_desc(res, bmin, bmax, 4, 0.0, 1.0)),
+    "mer_sensitivity_create": lambda res, bmin, bmax: capi.validate_sensitivity(_desc(res=res, bmin=bmin, bmax=bmax)),
+}
+
+
+@pytest.mark.parametrize("who", sorted(COMPOSED))
+@pytest.mark.parametrize("kw,msg", BOX_REFUSALS)
+def test_box_refusals_carry_their_own_prefix_once(who, kw, msg):
+    box = dict(res=(8, 8, 8), bmin=(-1, -1, -1), bmax=(1, 1, 1))
+    COMPOSED[who](**box)                                # accepted as it stands
+    box.update(kw)
+    with pytest.raises(capi.MerError) as e:
+        COMPOSED[who](**box)
+    assert str(e.value) == who + ": " + msg
+    assert len(re.findall(r"mer_\w+_create", str(e.value))) == 1
+
+
+def test_raster_refusals_carry_their_own_prefix_once():
+    """the raster / gate / cone checks are shared the same way between the exitance map and the detector"""
+    for make, who, res_what in ((lambda **kw: capi.validate_exitance(capi.exitance_desc(kw.pop("boundary", P.BOUNDARY_AABB), kw.pop("dres", (8, 8)), **kw)),
+                                 "mer_exitance_create", "res"),
+                                (lambda **kw: capi.validate_sensitivity(_desc(**kw)), "mer_sensitivity_create", "detector res")):
+        for kw, msg in ((dict(boundary=P.BOUNDARY_SDF), "boundary must be the cube (MER_BOUNDARY_AABB) or the sphere (MER_BOUNDARY_SPHERE)"),
+                        (dict(dres=(0, 8)), res_what + " must lie in 1 ... 4096 on both axes"), (dict(t_bin=-0.5), "t_bin must be finite and at least 0"),
+                        (dict(t_min=float("inf")), "t_min must be finite"), (dict(cos_min=1.0), "cos_min must lie in 0 <= cos_min < 1")):
+            with pytest.raises(capi.MerError) as e:
+                make(**kw)
+            assert str(e.value) == who + ": " + msg
