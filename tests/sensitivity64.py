@@ -1,11 +1,13 @@
-"""The sensitivity grid of mer_render_sensitivity (include/mer.h) restated in float64 with numpy, for a homogeneous RGB medium with the
-null boundary in the cube [-1, 1]^3.  Vectorised over the paths of a batch; independent of the library.
+"""The sensitivity grid of mer_render_sensitivity (include/mer.h) restated in float64 with numpy, for a homogeneous RGB medium or the
+sigma_t ramp of tests/lightpath64.py (ramp(...): a constant RGB albedo or an albedo grid) with the null boundary in the cube [-1, 1]^3.
+Vectorised over the paths of a batch; independent of the library.
 
 The walk is tests/lightpath64.py's (render): emitter, one depth and one roulette trip for the null boundary when the emitter lies outside,
 free flights by the medium's distance-sampling strategy, the weights transmittance / pdfSuccess at a collision and transmittance /
 pdfFailure at the exit, Henyey-Greenstein, roulette.  `manual(...)` adds the strategy the derivative test needs: one exponential of a
 FIXED density rho, whatever sigma_t is (Walk::sample_exp_distance with MER_STRATEGY_MANUAL), so that the walks at two values of sigma_a
-draw the same paths.
+draw the same paths.  In a ramp the free flights come from lightpath64._sample_ramp (the closed-form inversion of the optical depth), a
+collision multiplies T by lightpath64.ramp_albedo at its point, and a path leaves with T power and no strategy factor.
 
 What is new: nothing is deposited while a path walks.  Every flight is cut at the planes of the grid (fluence_track64._pieces) and the
 lengths of its pieces are added to the path's own row of a dense matrix L[path, cell] (the grids here are small).  A path that leaves
@@ -55,7 +57,8 @@ def render(emitter, power, medium, g, res, det, bmin=(-1, -1, -1), bmax=(1, 1, 1
     rng = np.random.default_rng(seed)
     power = np.broadcast_to(np.asarray(power, np.float64), (3,))
     ncell = int(np.prod(res))
-    clear = not medium["st"].any()
+    homog = medium["kind"] == "homogeneous"
+    clear = homog and not medium["st"].any()
     J = np.zeros((batches, ncell, 3)); totals = np.zeros((batches, 16))
     outside = not np.all(np.abs(emitter["o"]) <= 1)
     for b in range(batches):
@@ -78,7 +81,7 @@ def render(emitter, power, medium, g, res, det, bmin=(-1, -1, -1), bmax=(1, 1, 1
             if len(T) == 0 or not (depth <= max_depth or max_depth < 0):
                 break
             _, tex = _slabs(x, d)
-            tfl = np.full(len(T), np.inf) if clear else LP._sample_homogeneous(medium, rng, len(T))
+            tfl = np.full(len(T), np.inf) if clear else LP._sample_homogeneous(medium, rng, len(T)) if homog else LP._sample_ramp(medium, rng, x, d)
             sc = tfl < tex
             ex = ~sc
             # ---- the lengths of every flight, collided or not
@@ -90,7 +93,7 @@ def render(emitter, power, medium, g, res, det, bmin=(-1, -1, -1), bmax=(1, 1, 1
             Lin[pid] += fl
             # ---- the flights that reach the boundary
             we = T[ex] * power
-            if not clear:
+            if homog and not clear:
                 tr, _, pf = LP.strategy_pdfs(medium, tex[ex])
                 we = we * tr / pf[:, None]
             ok = detected(det, x[ex] + d[ex] * tex[ex, None], d[ex], plen[ex] + tex[ex] * n)
@@ -99,8 +102,11 @@ def render(emitter, power, medium, g, res, det, bmin=(-1, -1, -1), bmax=(1, 1, 1
             x, d, T, plen, pid = x[sc] + d[sc] * tfl[sc, None], d[sc], T[sc], plen[sc] + tfl[sc] * n, pid[sc]
             if len(T) == 0:
                 break
-            tr, ps, _ = LP.strategy_pdfs(medium, tfl[sc])
-            T = T * medium["ss"] * tr / ps[:, None]
+            if homog:
+                tr, ps, _ = LP.strategy_pdfs(medium, tfl[sc])
+                T = T * medium["ss"] * tr / ps[:, None]
+            else:
+                T = T * LP.ramp_albedo(medium, x)
             live = T.max(1) > 0
             x, d, T, plen, pid = x[live], d[live], T[live], plen[live], pid[live]
             d = hg_sample(g, d, rng.random((len(T), 2)))

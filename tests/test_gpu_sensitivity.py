@@ -142,9 +142,11 @@ def test_same_walk_and_window_sum_as_the_exitance_map(ctx, which):
 
 # ---- 3. the accounting identity --------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("which", ["straight homogeneous RGB", "straight homogeneous RGB sphere", "trilinear Verlet", "acoustic RK4"])
+@pytest.mark.parametrize("which", ["straight homogeneous RGB", "straight homogeneous RGB sphere", "trilinear Verlet", "acoustic RK4",
+                                   "straight gridded sigma_t", "trilinear RK4", "B-spline Verlet"])
 def test_cells_and_dropped_hold_all_of_the_path_length(ctx, which):
     make, dk = WALKS[which]
+    dk = {k: v for k, v in dk.items() if k != "t_bin"}                   # the width of the walk test's gate, which starts at CONE_GATE's t_min
     s, t = _render(ctx, make(), dk, 16, res=(5, 4, 3), box=((-0.6, -0.5, -0.7), (0.5, 0.7, 0.4)), seed=11)
     lhs = s.reshape(-1, 3).sum(0) + t[4:7]
     print(which, "cells + dropped", lhs, "w x length", t[9:12], "dropped", t[4:7])
