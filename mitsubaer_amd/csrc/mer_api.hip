@@ -47,25 +47,6 @@ template <typename F> static int dispatch_modes(mer_context *ctx, const mer_scen
 }
 }  // namespace mer
 
-// staging helpers for the leaf entry points -------------------------------------------------------------
-struct DevBuf {
-    mer_context *ctx; void *p = nullptr;
-    DevBuf(mer_context *c) : ctx(c) {}
-    ~DevBuf() { if (p) (void) hipFree(p); }
-    int alloc(size_t bytes) { HIP_CHECK(ctx, hipMalloc(&p, bytes ? bytes : 4)); return 0; }
-    int upload(const void *host, size_t bytes) {
-        if (alloc(bytes)) return 1;
-        if (bytes) HIP_CHECK(ctx, hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return 0;
-    }
-    int download(void *host, size_t bytes) {
-        if (bytes) HIP_CHECK(ctx, hipMemcpyAsync(host, p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return 0;
-    }
-    template <typename T> T *as() { return (T *) p; }
-};
-
 extern "C" {
 
 int mer_abi_version(void) { return MER_ABI_VERSION; }
@@ -85,16 +66,14 @@ int mer_context_create(int32_t device_id, mer_context **out) {
     if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&ctx->prop, device_id) != hipSuccess) {
         g_create_error = "mer_context_create: hipSetDevice failed"; delete ctx; return 1;
     }
-    if (hipMalloc((void **) &ctx->counters, sizeof(unsigned long long) * (MER_C_COUNT * MER_COUNTER_REPLICAS + 8)) != hipSuccess ||
-        hipMemset(ctx->counters, 0, sizeof(unsigned long long) * (MER_C_COUNT * MER_COUNTER_REPLICAS + 8)) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
-        g_create_error = "mer_context_create: device allocation failed"; delete ctx; return 1;
-    }
+    const size_t counter_bytes = sizeof(unsigned long long) * (MER_C_COUNT * MER_COUNTER_REPLICAS + 8);
+    bool ok = !ctx->counters.alloc(ctx, counter_bytes) && hipMemset(ctx->counters.p, 0, counter_bytes) == hipSuccess &&
+              hipEventCreate(&ctx->ev0) == hipSuccess && hipEventCreate(&ctx->ev1) == hipSuccess;
 #ifdef MER_BOUNDS_CHECK
-    if (hipMalloc((void **) &ctx->chk, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(ctx->chk, 0, 4 * sizeof(unsigned long long)) != hipSuccess) {
-        g_create_error = "mer_context_create: device allocation failed"; delete ctx; return 1;
-    }
+    ok = ok && !ctx->chk_buf.alloc(ctx, 4 * sizeof(unsigned long long)) && hipMemset(ctx->chk_buf.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess;
+    ctx->chk = ctx->chk_buf.as<unsigned long long>();
 #endif
+    if (!ok) { g_create_error = "mer_context_create: device allocation failed"; mer_context_destroy(ctx); return 1; }
     // MER_OPTIONS="name=value,name=value": initial option values for A/B scripts (read once, here; mer_context_set_option afterwards)
     if (const char *e = getenv("MER_OPTIONS")) {
         std::string all(e); size_t pos = 0;
@@ -111,42 +90,42 @@ int mer_context_create(int32_t device_id, mer_context **out) {
     return 0;
 }
 
-static int64_t *option_slot(mer_context *ctx, const char *name) {
+// every option: its name, its field and its range (ANY: every value).  The one table behind mer_context_set_option, mer_context_get_option and
+// MER_OPTIONS; p = nullptr, with the context's message set, for a name it does not hold.
+struct OptionEntry { const char *name; int64_t *p; int64_t min, max; };
+static OptionEntry option_slot(mer_context *ctx, const char *name) {
     Options &o = ctx->opt;
-    const struct { const char *n; int64_t *p; } table[] = {
-        {"pipes", &o.pipes}, {"nslots", &o.nslots}, {"ksteps", &o.ksteps}, {"mq_sort", &o.mq_sort}, {"connect_launches", &o.connect_launches},
-        {"adaptive_k", &o.adaptive_k}, {"pass_events", &o.pass_events}, {"buffer_loads", &o.buffer_loads}, {"gen_all", &o.gen_all},
-        {"prefilter", &o.prefilter}, {"verbose", &o.verbose}, {"debug_pixel", &o.debug_pixel}, {"lds_bricks", &o.lds_bricks}, {"march_lds_kb", &o.march_lds_kb},
-        {"tile_deal", &o.tile_deal}, {"small_render_slots", &o.small_render_slots}, {"inline_walks", &o.inline_walks}, {"spawn_walks", &o.spawn_walks},
-        {"grid_fit", &o.grid_fit}, {"check_every", &o.check_every}, {"march_sort", &o.march_sort}, {"march_sort_major", &o.march_sort_major}};
-    for (const auto &t : table) if (std::strcmp(t.n, name) == 0) return t.p;
-    return nullptr;
+    const int64_t ANY = INT64_MAX;
+    const OptionEntry table[] = {
+        {"pipes", &o.pipes, 1, MER_MAX_PIPES}, {"nslots", &o.nslots, 0, (int64_t) 1 << 28}, {"ksteps", &o.ksteps, 1, 1 << 20}, {"mq_sort", &o.mq_sort, -1, 1},
+        {"connect_launches", &o.connect_launches, 1, 64}, {"adaptive_k", &o.adaptive_k, 0, 2}, {"pass_events", &o.pass_events, -ANY - 1, ANY},
+        {"buffer_loads", &o.buffer_loads, -ANY - 1, ANY}, {"gen_all", &o.gen_all, -ANY - 1, ANY}, {"prefilter", &o.prefilter, 0, 5},
+        {"verbose", &o.verbose, -ANY - 1, ANY}, {"debug_pixel", &o.debug_pixel, -1, ((int64_t) 1 << 31) - 1}, {"lds_bricks", &o.lds_bricks, -ANY - 1, ANY},
+        {"march_lds_kb", &o.march_lds_kb, 0, 64},          // dynamic LDS above 64 KiB would need hipFuncSetAttribute
+        {"tile_deal", &o.tile_deal, 0, 1}, {"small_render_slots", &o.small_render_slots, 0, 1}, {"inline_walks", &o.inline_walks, 0, 1},
+        {"spawn_walks", &o.spawn_walks, 0, 1}, {"grid_fit", &o.grid_fit, 0, 1}, {"check_every", &o.check_every, 1, 64},
+        {"march_sort", &o.march_sort, 0, 4}, {"march_sort_major", &o.march_sort_major, 0, 1}};
+    for (const auto &t : table) if (std::strcmp(t.name, name) == 0) return t;
+    ctx->error = std::string("unknown option '") + name + "'";
+    return OptionEntry{name, nullptr, 0, 0};
 }
 int mer_context_set_option(mer_context *ctx, const char *name, int64_t value) {
     MER_USE_DEVICE(ctx);
     if (!ctx || !name) return 1;
-    int64_t *p = option_slot(ctx, name);
-    if (!p) return fail(ctx, std::string("unknown option '") + name + "'");
-    const std::string n(name);
-    if ((n == "pipes" && (value < 1 || value > MER_MAX_PIPES)) || (n == "ksteps" && (value < 1 || value > (1 << 20))) ||
-        (n == "connect_launches" && (value < 1 || value > 64)) ||
-        // nslots: 0 = default, otherwise at least one block per pipeline (a smaller value would launch empty grids)
-        (n == "nslots" && (value < 0 || (value > 0 && value < MER_BLOCK * MER_MAX_PIPES) || value > ((int64_t) 1 << 28))) ||
-        (n == "prefilter" && (value < 0 || value > 5)) || (n == "mq_sort" && (value < -1 || value > 1)) ||
-        (n == "march_lds_kb" && (value < 0 || value > 64)) ||          // dynamic LDS above 64 KiB would need hipFuncSetAttribute
-        (n == "debug_pixel" && (value < -1 || value > ((int64_t) 1 << 31) - 1)) || (n == "tile_deal" && (value < 0 || value > 1)) ||
-        (n == "small_render_slots" && (value < 0 || value > 1)) || (n == "inline_walks" && (value < 0 || value > 1)) || (n == "spawn_walks" && (value < 0 || value > 1)) || (n == "adaptive_k" && (value < 0 || value > 2)) ||
-        (n == "grid_fit" && (value < 0 || value > 1)) || (n == "check_every" && (value < 1 || value > 64)) || (n == "march_sort" && (value < 0 || value > 4)) || (n == "march_sort_major" && (value < 0 || value > 1)))
-        return fail(ctx, std::string("option '") + name + "': value out of range");
-    *p = value;
+    const OptionEntry t = option_slot(ctx, name);
+    if (!t.p) return 1;
+    // nslots: 0 = default, otherwise at least one block per pipeline (a smaller value would launch empty grids)
+    const bool nslots_too_few = t.p == &ctx->opt.nslots && value > 0 && value < MER_BLOCK * MER_MAX_PIPES;
+    if (value < t.min || value > t.max || nslots_too_few) return fail(ctx, std::string("option '") + name + "': value out of range");
+    *t.p = value;
     return 0;
 }
 int mer_context_get_option(mer_context *ctx, const char *name, int64_t *value) {
     MER_USE_DEVICE(ctx);
     if (!ctx || !name || !value) return 1;
-    int64_t *p = option_slot(ctx, name);
-    if (!p) return fail(ctx, std::string("unknown option '") + name + "'");
-    *value = *p;
+    const OptionEntry t = option_slot(ctx, name);
+    if (!t.p) return 1;
+    *value = *t.p;
     return 0;
 }
 int mer_debug_bounds(mer_context *ctx, int32_t *enabled, uint64_t out[4]) {
@@ -162,31 +141,12 @@ int mer_debug_bounds(mer_context *ctx, int32_t *enabled, uint64_t out[4]) {
     return 0;
 }
 
+// what is not memory: the device buffers of the context, its pipelines, volumes, envmaps and recorders free themselves with `delete ctx`,
+// on the device selected here
 void mer_context_destroy(mer_context *ctx) {
     if (!ctx) return;
     (void) hipSetDevice(ctx->device);
-    for (auto &kv : ctx->volumes) {
-        if (kv.second.dense && kv.second.owns_dense) (void) hipFree(kv.second.dense);
-        if (kv.second.cell8) (void) hipFree(kv.second.cell8);
-        if (kv.second.coeff) (void) hipFree(kv.second.coeff);
-    }
-    if (ctx->counters) (void) hipFree(ctx->counters);
-    if (ctx->ftable) (void) hipFree(ctx->ftable);
-    if (ctx->etab) (void) hipFree(ctx->etab);
-    for (auto &kv : ctx->envmaps) if (kv.second.dev) (void) hipFree(kv.second.dev);
-    for (auto &kv : ctx->recorders) if (kv.second.dev) (void) hipFree(kv.second.dev);
-    if (ctx->detect_list) (void) hipFree(ctx->detect_list);
-    if (ctx->chk) (void) hipFree(ctx->chk);
     for (Pipe &pp : ctx->pipes) {
-        if (pp.slots) (void) hipFree(pp.slots);
-        if (pp.live) (void) hipFree(pp.live);
-        for (SegQueue *q : {&pp.eq, &pp.mq[0], &pp.mq[1], &pp.sq[0], &pp.sq[1], &pp.cq[0], &pp.cq[1]}) { if (q->items) (void) hipFree(q->items); if (q->counts) (void) hipFree(q->counts); if (q->keys) (void) hipFree(q->keys); }
-        if (pp.msort) (void) hipFree(pp.msort);
-        if (pp.cstate) (void) hipFree(pp.cstate);
-        if (pp.side_state) (void) hipFree(pp.side_state);
-        if (pp.hitq) (void) hipFree(pp.hitq);
-        if (pp.hitq_ctr) (void) hipFree(pp.hitq_ctr);
-        if (pp.host_live) (void) hipHostFree(pp.host_live);
         for (hipEvent_t e : pp.readback) if (e) (void) hipEventDestroy(e);
         if (pp.finished) (void) hipEventDestroy(pp.finished);
         for (hipEvent_t e : pp.pass_events) (void) hipEventDestroy(e);
@@ -219,8 +179,8 @@ static int volume_finish(mer_context *ctx, Volume &v, int32_t layout, mer_volume
     if (layout == MER_LAYOUT_CELL8) {
         if (v.desc.channels != 1 || v.desc.dtype != MER_VOL_F32) return fail(ctx, "CELL8 layout needs a 1-channel float32 grid");
         const size_t ncell = (size_t) (v.desc.res[0] - 1) * (v.desc.res[1] - 1) * (v.desc.res[2] - 1);
-        HIP_CHECK(ctx, hipMalloc((void **) &v.cell8, ncell * 8 * sizeof(float)));
-        hipLaunchKernelGGL(relayout_cell8_kernel, dim3(4096), dim3(256), 0, ctx->stream, (const float *) v.dense, v.cell8,
+        if (v.cell8.alloc(ctx, ncell * 8 * sizeof(float))) return 1;
+        hipLaunchKernelGGL(relayout_cell8_kernel, dim3(4096), dim3(256), 0, ctx->stream, v.dense.as<const float>(), v.cell8.as<float>(),
                            v.desc.res[0], v.desc.res[1], v.desc.res[2]);
         HIP_CHECK(ctx, hipGetLastError());
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -229,15 +189,15 @@ static int volume_finish(mer_context *ctx, Volume &v, int32_t layout, mer_volume
         const int bshift = layout == MER_LAYOUT_BRICK125 ? 2 : 1, bc = 1 << bshift, recw = layout == MER_LAYOUT_BRICK125 ? 128 : 32;
         for (int i = 0; i < 3; i++) if (v.desc.res[i] < 2) return fail(ctx, "the BRICK layouts need at least 2 nodes per axis");
         const int nbx = (v.desc.res[0] - 2) / bc + 1, nby = (v.desc.res[1] - 2) / bc + 1, nbz = (v.desc.res[2] - 2) / bc + 1;
-        HIP_CHECK(ctx, hipMalloc((void **) &v.cell8, (size_t) nbx * nby * nbz * recw * sizeof(float)));
-        hipLaunchKernelGGL(relayout_brick_kernel, dim3(4096), dim3(256), 0, ctx->stream, (const float *) v.dense, v.cell8,
+        if (v.cell8.alloc(ctx, (size_t) nbx * nby * nbz * recw * sizeof(float))) return 1;
+        hipLaunchKernelGGL(relayout_brick_kernel, dim3(4096), dim3(256), 0, ctx->stream, v.dense.as<const float>(), v.cell8.as<float>(),
                            v.desc.res[0], v.desc.res[1], v.desc.res[2], nbx, nby, nbz, bshift, recw);
         HIP_CHECK(ctx, hipGetLastError());
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     } else if (layout != MER_LAYOUT_DENSE) return fail(ctx, "unknown volume layout");
     v.layout = layout;
     const int h = ctx->next_handle++;
-    ctx->volumes[h] = v;
+    ctx->volumes[h] = std::move(v);
     *out = h;
     return 0;
 }
@@ -278,12 +238,12 @@ static int volume_upload(mer_context *ctx, const mer_grid_desc *desc, const void
     Volume v; v.desc = *desc;
     const size_t n = (size_t) desc->res[0] * desc->res[1] * desc->res[2] * desc->channels;
     v.bytes_dense = n * (desc->dtype == MER_VOL_F32 ? 4 : 1);
-    HIP_CHECK(ctx, hipMalloc(&v.dense, v.bytes_dense));
+    if (v.dense.alloc(ctx, v.bytes_dense)) return 1;
     if (from_device) {
-        HIP_CHECK(ctx, hipMemcpyAsync(v.dense, data, v.bytes_dense, hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_CHECK(ctx, hipMemcpyAsync(v.dense.p, data, v.bytes_dense, hipMemcpyDeviceToDevice, ctx->stream));
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     } else {
-        HIP_CHECK(ctx, hipMemcpy(v.dense, data, v.bytes_dense, hipMemcpyHostToDevice));
+        HIP_CHECK(ctx, hipMemcpy(v.dense.p, data, v.bytes_dense, hipMemcpyHostToDevice));
     }
     return volume_finish(ctx, v, layout, out);
 }
@@ -326,14 +286,11 @@ int mer_sdf_from_mesh(mer_context *ctx, const mer_grid_desc *desc, const float *
     }
     const int64_t kept = (int64_t) (tri12.size() / 12);
     if (kept == 0) return fail(ctx, "mer_sdf_from_mesh: no triangle left after dropping the degenerate ones");
-    float *sdf_dev = nullptr, *w_dev = nullptr;
-    if (sdf_build(ctx, desc, tri12.data(), kept, max_triangles_per_launch, &sdf_dev, &w_dev)) return 1;
+    DeviceBuffer sdf, winding;
+    if (sdf_build(ctx, desc, tri12.data(), kept, max_triangles_per_launch, sdf, winding)) return 1;
     const size_t nodes = (size_t) desc->res[0] * desc->res[1] * desc->res[2];
-    int rc = 0;
-    if (winding_host && hipMemcpy(winding_host, w_dev, nodes * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ctx, "mer_sdf_from_mesh: copy of the winding numbers failed");
-    if (!rc) rc = volume_upload(ctx, desc, sdf_dev, true, layout, out);         // the path of mer_volume_upload_dev
-    (void) hipFree(sdf_dev); (void) hipFree(w_dev);
-    return rc;
+    if (winding_host && hipMemcpy(winding_host, winding.p, nodes * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(ctx, "mer_sdf_from_mesh: copy of the winding numbers failed");
+    return volume_upload(ctx, desc, sdf.p, true, layout, out);         // the path of mer_volume_upload_dev
 }
 
 int mer_volume_download(mer_context *ctx, mer_volume h, float *data_host) {
@@ -345,7 +302,7 @@ int mer_volume_download(mer_context *ctx, mer_volume h, float *data_host) {
     const Volume &v = it->second;
     if (v.desc.channels != 1 || v.desc.dtype != MER_VOL_F32) return fail(ctx, "mer_volume_download: only a 1-channel float32 volume can be downloaded");
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_CHECK(ctx, hipMemcpy(data_host, v.dense, v.bytes_dense, hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(data_host, v.dense.p, v.bytes_dense, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -358,21 +315,22 @@ int mer_volume_build_spline(mer_context *ctx, mer_volume h) {
     if (v.coeff) return 0;
     const int nx = v.desc.res[0], ny = v.desc.res[1], nz = v.desc.res[2];
     const size_t n = (size_t) nx * ny * nz;
-    float *a = nullptr, *b = nullptr, *t = nullptr;
-    HIP_CHECK(ctx, hipMalloc((void **) &a, n * 4));
-    HIP_CHECK(ctx, hipMalloc((void **) &b, n * 4));
+    DeviceBuffer abuf, bbuf, tbuf;
+    if (abuf.alloc(ctx, n * 4) || bbuf.alloc(ctx, n * 4)) return 1;
+    float *a = abuf.as<float>(), *b = bbuf.as<float>(), *t = nullptr;
+    const float *dense = v.dense.as<const float>();
     // along y (lines indexed by x and z), then x (by y and z), then z (by x and y): basisspline.h:868-887
     const int64_t form = ctx->opt.prefilter;
     const bool seq = form == 1 || std::min(nx, std::min(ny, nz)) < 16;
     if (seq) {                 // one thread per line (reference order of operations; tiny grids)
         hipLaunchKernelGGL(bspline_pass_kernel, dim3(nblocks((int64_t) nx * nz)), dim3(256), 0, ctx->stream,
-                           (const float *) v.dense, a, nx, nz, (int64_t) 1, (int64_t) nx * ny, (int64_t) nx, ny);
+                           dense, a, nx, nz, (int64_t) 1, (int64_t) nx * ny, (int64_t) nx, ny);
         hipLaunchKernelGGL(bspline_pass_kernel, dim3(nblocks((int64_t) ny * nz)), dim3(256), 0, ctx->stream,
                            (const float *) a, b, ny, nz, (int64_t) nx, (int64_t) nx * ny, (int64_t) 1, nx);
         hipLaunchKernelGGL(bspline_pass_kernel, dim3(nblocks((int64_t) nx * ny)), dim3(256), 0, ctx->stream,
                            (const float *) b, a, nx, ny, (int64_t) 1, (int64_t) nx, (int64_t) nx * ny, nz);
     } else {
-        if (form == 2 || form == 3) HIP_CHECK(ctx, hipMalloc((void **) &t, n * 4));
+        if (form == 2 || form == 3) { if (tbuf.alloc(ctx, n * 4)) return 1; t = tbuf.as<float>(); }
         auto pass = [&](const float *src, float *dst, int na, int nb, int64_t sa, int64_t sb, int64_t sl, int size) {
             const int64_t threads = (int64_t) na * nb * ((size + MER_PF_SEG - 1) / MER_PF_SEG);
             hipLaunchKernelGGL(bspline_causal_kernel, dim3(nblocks(threads)), dim3(256), 0, ctx->stream, src, t, na, nb, sa, sb, sl, size);
@@ -394,8 +352,8 @@ int mer_volume_build_spline(mer_context *ctx, mer_volume h) {
             if (threads > 0) hipLaunchKernelGGL(bspline_win_kernel, dim3(nblocks(threads)), dim3(256), 0, ctx->stream, src, dst, na, nb, sb, sl, size, s_lo, s_hi);
         };
         const bool two_kernel = form == 2;
-        if (two_kernel) pass((const float *) v.dense, a, nx, nz, 1, (int64_t) nx * ny, nx, ny);          // y
-        else win((const float *) v.dense, a, nx, nz, (int64_t) nx * ny, nx, ny);
+        if (two_kernel) pass(dense, a, nx, nz, 1, (int64_t) nx * ny, nx, ny);          // y
+        else win(dense, a, nx, nz, (int64_t) nx * ny, nx, ny);
         if (form == 3) pass(a, b, ny, nz, nx, (int64_t) nx * ny, 1, nx);           // x, strided form
         else {                                                                                        // x: lines are contiguous -> LDS tiles
             const int64_t nlines = (int64_t) ny * nz;
@@ -422,9 +380,7 @@ int mer_volume_build_spline(mer_context *ctx, mer_volume h) {
     }
     HIP_CHECK(ctx, hipGetLastError());
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void) hipFree(b);
-    if (t) (void) hipFree(t);
-    v.coeff = a;
+    v.coeff = std::move(abuf);
     return 0;
 }
 
@@ -433,23 +389,16 @@ int mer_volume_download_spline(mer_context *ctx, mer_volume h, float *coeff_host
     auto it = ctx->volumes.find(h);
     if (it == ctx->volumes.end() || !it->second.coeff) return fail(ctx, "volume has no spline coefficients");
     const size_t n = (size_t) it->second.desc.res[0] * it->second.desc.res[1] * it->second.desc.res[2];
-    HIP_CHECK(ctx, hipMemcpy(coeff_host, it->second.coeff, n * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(coeff_host, it->second.coeff.p, n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
 int mer_volume_destroy(mer_context *ctx, mer_volume h) {
     MER_USE_DEVICE(ctx);
     auto ie = ctx->envmaps.find(h);
-    if (ie != ctx->envmaps.end()) {              // an envmap (mer_envmap_upload)
-        if (ie->second.dev) (void) hipFree(ie->second.dev);
-        ctx->envmaps.erase(ie);
-        return 0;
-    }
+    if (ie != ctx->envmaps.end()) { ctx->envmaps.erase(ie); return 0; }             // an envmap (mer_envmap_upload)
     auto it = ctx->volumes.find(h);
     if (it == ctx->volumes.end()) return fail(ctx, "invalid volume handle");
-    if (it->second.dense && it->second.owns_dense) (void) hipFree(it->second.dense);
-    if (it->second.cell8) (void) hipFree(it->second.cell8);
-    if (it->second.coeff) (void) hipFree(it->second.coeff);
     ctx->volumes.erase(it);
     return 0;
 }
@@ -513,10 +462,10 @@ int mer_envmap_upload(mer_context *ctx, int32_t width, int32_t height, const flo
     std::memcpy(h.data() + m.off_cols, cols.data(), cols.size() * 4);
     std::memcpy(h.data() + m.off_rows, rows.data(), rows.size() * 4);
     std::memcpy(h.data() + m.off_weights, weights.data(), weights.size() * 4);
-    HIP_CHECK(ctx, hipMalloc(&m.dev, bytes));
-    if (hipMemcpy(m.dev, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void) hipFree(m.dev); return fail(ctx, "mer_envmap_upload: copy to the device failed"); }
+    if (m.dev.alloc(ctx, bytes)) return 1;
+    if (hipMemcpy(m.dev.p, h.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(ctx, "mer_envmap_upload: copy to the device failed");
     const int hd = ctx->next_handle++;
-    ctx->envmaps[hd] = m;
+    ctx->envmaps[hd] = std::move(m);
     *out = hd;
     return 0;
 }
@@ -531,8 +480,10 @@ int mer_film_channels(mer_context *ctx, const mer_scene_desc *scene, int32_t *ch
 }
 int mer_film_alloc_n(mer_context *ctx, int32_t width, int32_t height, int32_t channels, float **film_dev) {
     MER_USE_DEVICE(ctx);
-    HIP_CHECK(ctx, hipMalloc((void **) film_dev, (size_t) width * height * channels * sizeof(float)));
-    HIP_CHECK(ctx, hipMemsetAsync(*film_dev, 0, (size_t) width * height * channels * sizeof(float), ctx->stream));
+    DeviceBuffer film;               // the caller's from here on (mer_film_free)
+    if (film.alloc(ctx, (size_t) width * height * channels * sizeof(float))) return 1;
+    HIP_CHECK(ctx, hipMemsetAsync(film.p, 0, (size_t) width * height * channels * sizeof(float), ctx->stream));
+    *film_dev = (float *) film.release();
     return 0;
 }
 int mer_film_zero_n(mer_context *ctx, float *film_dev, int32_t width, int32_t height, int32_t channels) {
@@ -552,8 +503,8 @@ int mer_film_download(mer_context *ctx, const float *film_dev, int32_t width, in
     MER_USE_DEVICE(ctx);
     return mer_film_download_n(ctx, film_dev, width, height, 5, film_host);
 }
-int mer_film_free(mer_context *ctx, float *film_dev) { HIP_CHECK(ctx, hipFree(film_dev)); return 0; }
-int mer_device_free(mer_context *ctx, void *p) { HIP_CHECK(ctx, hipFree(p)); return 0; }
+int mer_film_free(mer_context *ctx, float *film_dev) { return DeviceBuffer::free_raw(ctx, film_dev); }
+int mer_device_free(mer_context *ctx, void *p) { return DeviceBuffer::free_raw(ctx, p); }
 
 int mer_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev) {
     MER_USE_DEVICE(ctx);
@@ -569,12 +520,12 @@ int mer_render_paths(mer_context *ctx, const mer_scene_desc *scene, int32_t samp
     if (!ctx || !scene || !out_rgb) return 1;
     if (scene->integrator == MER_INTEGRATOR_PTRACER) return fail(ctx, "mer_render_paths: per-path radiance is a camera-path quantity (integrator = volpath); a light path splats onto many pixels");
     const size_t n = (size_t) scene->width * scene->height * 3;
-    DevBuf buf(ctx);
-    if (buf.alloc(n * 4)) return 1;
+    DeviceBuffer buf;
+    if (buf.alloc(ctx, n * 4)) return 1;
     HIP_CHECK(ctx, hipMemsetAsync(buf.p, 0, n * 4, ctx->stream));
     mer_shard sh = {sample_index, 1, 1, 0, 1};
     if (launch_render(ctx, scene, &sh, seed, buf.as<float>(), buf.as<float>(), n, n)) return 1;
-    return buf.download(out_rgb, n * 4);
+    return buf.download(ctx, out_rgb, n * 4);
 }
 
 int mer_synchronize(mer_context *ctx) { HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream)); return 0; }
@@ -600,7 +551,7 @@ int mer_counters_read(mer_context *ctx, uint64_t out[MER_C_COUNT]) {
     MER_USE_DEVICE(ctx);
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> all((size_t) MER_C_COUNT * MER_COUNTER_REPLICAS);
-    HIP_CHECK(ctx, hipMemcpy(all.data(), ctx->counters, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(ctx, hipMemcpy(all.data(), ctx->counters.p, sizeof(uint64_t) * all.size(), hipMemcpyDeviceToHost));
     for (int k = 0; k < MER_C_COUNT; k++) {
         out[k] = 0;
         for (int r = 0; r < MER_COUNTER_REPLICAS; r++) out[k] += all[(size_t) r * MER_C_COUNT + k];
@@ -609,7 +560,7 @@ int mer_counters_read(mer_context *ctx, uint64_t out[MER_C_COUNT]) {
 }
 int mer_counters_reset(mer_context *ctx) {
     MER_USE_DEVICE(ctx);
-    HIP_CHECK(ctx, hipMemsetAsync(ctx->counters, 0, sizeof(uint64_t) * MER_C_COUNT * MER_COUNTER_REPLICAS, ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(ctx->counters.p, 0, sizeof(uint64_t) * MER_C_COUNT * MER_COUNTER_REPLICAS, ctx->stream));
     return 0;
 }
 
@@ -620,13 +571,13 @@ int mer_lookup_trilinear(mer_context *ctx, mer_volume h, const float *pts, int64
     if (it == ctx->volumes.end()) return fail(ctx, "invalid volume handle");
     if (it->second.desc.channels != 1) return fail(ctx, "lookupFloat(): volume does not support float lookups");
     DGrid g; fill_dgrid(ctx, it->second, g);
-    DevBuf dp(ctx), dv(ctx), di(ctx);
-    if (dp.upload(pts, n * 12) || dv.alloc(n * 4) || di.alloc(n * 16)) return 1;
+    DeviceBuffer dp, dv, di;
+    if (dp.upload(ctx, pts, n * 12) || dv.alloc(ctx, n * 4) || di.alloc(ctx, n * 16)) return 1;
     hipLaunchKernelGGL(lookup_trilinear_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, g, dp.as<float>(), n, dv.as<float>(),
                        out_idx ? di.as<int32_t>() : (int32_t *) nullptr);
     HIP_CHECK(ctx, hipGetLastError());
-    if (dv.download(out_val, n * 4)) return 1;
-    if (out_idx && di.download(out_idx, n * 16)) return 1;
+    if (dv.download(ctx, out_val, n * 4)) return 1;
+    if (out_idx && di.download(ctx, out_idx, n * 16)) return 1;
     return 0;
 }
 int mer_lookup_trilinear_rgb(mer_context *ctx, mer_volume h, const float *pts, int64_t n, float *out_rgb) {
@@ -634,13 +585,12 @@ int mer_lookup_trilinear_rgb(mer_context *ctx, mer_volume h, const float *pts, i
     auto it = ctx->volumes.find(h);
     if (it == ctx->volumes.end()) return fail(ctx, "invalid volume handle");
     if (it->second.desc.channels != 3) return fail(ctx, "lookupSpectrum(): volume does not support spectrum lookups");
-    Volume tmp = it->second; tmp.cell8 = nullptr;
-    DGrid g; fill_dgrid(ctx, tmp, g);
-    DevBuf dp(ctx), dv(ctx);
-    if (dp.upload(pts, n * 12) || dv.alloc(n * 12)) return 1;
+    DGrid g; fill_dgrid(ctx, it->second, g, false);
+    DeviceBuffer dp, dv;
+    if (dp.upload(ctx, pts, n * 12) || dv.alloc(ctx, n * 12)) return 1;
     hipLaunchKernelGGL(lookup_rgb_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, g, dp.as<float>(), n, dv.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return dv.download(out_rgb, n * 12);
+    return dv.download(ctx, out_rgb, n * 12);
 }
 int mer_rif_value_grad(mer_context *ctx, mer_volume h, int32_t interp, const float *pts, int64_t n, float *out_val, float *out_grad) {
     MER_USE_DEVICE(ctx);
@@ -650,12 +600,12 @@ int mer_rif_value_grad(mer_context *ctx, mer_volume h, int32_t interp, const flo
     if (interp != MER_RIF_TRILINEAR && interp != MER_RIF_BSPLINE3) return fail(ctx, "unknown rif_interp");
     if (interp == MER_RIF_BSPLINE3 && !it->second.coeff) return fail(ctx, "volume has no spline coefficients");
     DGrid g; fill_dgrid(ctx, it->second, g);
-    DevBuf dp(ctx), dv(ctx), dg(ctx);
-    if (dp.upload(pts, n * 12) || dv.alloc(n * 4) || dg.alloc(n * 12)) return 1;
+    DeviceBuffer dp, dv, dg;
+    if (dp.upload(ctx, pts, n * 12) || dv.alloc(ctx, n * 4) || dg.alloc(ctx, n * 12)) return 1;
     hipLaunchKernelGGL(rif_value_grad_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, g, interp, dp.as<float>(), n, dv.as<float>(), dg.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (dv.download(out_val, n * 4)) return 1;
-    return dg.download(out_grad, n * 12);
+    if (dv.download(ctx, out_val, n * 4)) return 1;
+    return dg.download(ctx, out_grad, n * 12);
 }
 
 int mer_acoustic_value_grad(mer_context *ctx, const mer_scene_desc *scene, const float *pts, int64_t n, float *out_val, float *out_grad) {
@@ -664,12 +614,12 @@ int mer_acoustic_value_grad(mer_context *ctx, const mer_scene_desc *scene, const
     Params P;
     mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.albedo_mode = MER_ALBEDO_CONST;
     if (make_params(ctx, &sc, P)) return 1;
-    DevBuf dp(ctx), dv(ctx), dg(ctx);
-    if (dp.upload(pts, n * 12) || dv.alloc(n * 4) || dg.alloc(n * 12)) return 1;
+    DeviceBuffer dp, dv, dg;
+    if (dp.upload(ctx, pts, n * 12) || dv.alloc(ctx, n * 4) || dg.alloc(ctx, n * 12)) return 1;
     hipLaunchKernelGGL(acoustic_value_grad_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.rif, dp.as<float>(), n, dv.as<float>(), dg.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (dv.download(out_val, n * 4)) return 1;
-    return dg.download(out_grad, n * 12);
+    if (dv.download(ctx, out_val, n * 4)) return 1;
+    return dg.download(ctx, out_grad, n * 12);
 }
 
 int mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0, const float *d0, const float *dist, int64_t n,
@@ -678,9 +628,9 @@ int mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0,
     Params P;
     if (make_params(ctx, scene, P)) return 1;
     if (scene->rif_mode == MER_RIF_CONST) return fail(ctx, "mer_er_trace needs a RIF volume");
-    DevBuf a(ctx), b(ctx), c(ctx), op(ctx), ov(ctx), od(ctx), oo(ctx), ok(ctx);
-    if (a.upload(p0, n * 12) || b.upload(d0, n * 12) || c.upload(dist, n * 4) || op.alloc(n * 12) || ov.alloc(n * 12) ||
-        od.alloc(n * 4) || oo.alloc(n * 4) || ok.alloc(n * 4)) return 1;
+    DeviceBuffer a, b, c, op, ov, od, oo, ok;
+    if (a.upload(ctx, p0, n * 12) || b.upload(ctx, d0, n * 12) || c.upload(ctx, dist, n * 4) || op.alloc(ctx, n * 12) || ov.alloc(ctx, n * 12) ||
+        od.alloc(ctx, n * 4) || oo.alloc(ctx, n * 4) || ok.alloc(ctx, n * 4)) return 1;
     const int rifk = rif_fetch_kind(ctx, scene);
     match_constant(FetchKinds(), rifk, [&](auto rif) {
         return match_constant(Steppers(), scene->stepper, [&](auto stepper) {
@@ -690,8 +640,8 @@ int mer_er_trace(mer_context *ctx, const mer_scene_desc *scene, const float *p0,
         });
     });
     HIP_CHECK(ctx, hipGetLastError());
-    if (op.download(out_p, n * 12) || ov.download(out_v, n * 12) || od.download(out_dist_surf, n * 4) || oo.download(out_opt, n * 4) ||
-        ok.download(out_success, n * 4)) return 1;
+    if (op.download(ctx, out_p, n * 12) || ov.download(ctx, out_v, n * 12) || od.download(ctx, out_dist_surf, n * 4) || oo.download(ctx, out_opt, n * 4) ||
+        ok.download(ctx, out_success, n * 4)) return 1;
     return 0;
 }
 
@@ -702,8 +652,8 @@ int mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1, 
     if (scene->rif_mode == MER_RIF_CONST) return fail(ctx, "mer_connect needs a RIF volume");
     if (scene->rif_mode == MER_RIF_ACOUSTIC) return fail(ctx, "mer_connect: the analytic acoustic RIF is connected inside mer_render only");
     P.seed = seed;
-    DevBuf a(ctx), b(ctx), r(ctx);
-    if (a.upload(p1, n * 12) || b.upload(p2, n * 12) || r.alloc(n * 48)) return 1;
+    DeviceBuffer a, b, r;
+    if (a.upload(ctx, p1, n * 12) || b.upload(ctx, p2, n * 12) || r.alloc(ctx, n * 48)) return 1;
     const int rifk = rif_fetch_kind(ctx, scene);
     bool launched = false;
 #define MER_CONNECT_CASE(R, B) if (!launched && rifk == R && (scene->boundary == MER_BOUNDARY_SDF) == (B == 1)) { launched = true;   \
@@ -720,7 +670,7 @@ int mer_connect(mer_context *ctx, const mer_scene_desc *scene, const float *p1, 
         } else return fail(ctx, "mer_connect: unsupported RIF layout for this boundary");
     }
     HIP_CHECK(ctx, hipGetLastError());
-    return r.download(out, n * 48);
+    return r.download(ctx, out, n * 48);
 }
 
 int mer_sample_distance(mer_context *ctx, const mer_scene_desc *scene, const float *o, const float *d, const float *maxt, int64_t n,
@@ -729,8 +679,8 @@ int mer_sample_distance(mer_context *ctx, const mer_scene_desc *scene, const flo
     Params P;
     if (make_params(ctx, scene, P)) return 1;
     P.seed = seed;
-    DevBuf a(ctx), b(ctx), c(ctx), r(ctx);
-    if (a.upload(o, n * 12) || b.upload(d, n * 12) || c.upload(maxt, n * 4) || r.alloc(n * 80)) return 1;
+    DeviceBuffer a, b, c, r;
+    if (a.upload(ctx, o, n * 12) || b.upload(ctx, d, n * 12) || c.upload(ctx, maxt, n * 4) || r.alloc(ctx, n * 80)) return 1;
     int rc = dispatch_modes(ctx, scene, [&](auto curved, auto rif, auto stepper, auto sigma, auto bnd) -> int {
         hipLaunchKernelGGL((sample_distance_kernel<decltype(curved)::value, decltype(rif)::value, decltype(stepper)::value, decltype(sigma)::value>),
                            dim3(nblocks(n, 64)), dim3(64), 0, ctx->stream, P, a.as<float>(), b.as<float>(), c.as<float>(), n, r.as<float>());
@@ -738,7 +688,7 @@ int mer_sample_distance(mer_context *ctx, const mer_scene_desc *scene, const flo
         return 0;
     });
     if (rc) return rc;
-    return r.download(rec, n * 80);
+    return r.download(ctx, rec, n * 80);
 }
 
 int mer_eval_transmittance(mer_context *ctx, const mer_scene_desc *scene, const float *o, const float *d, const float *maxt, int64_t n,
@@ -747,8 +697,8 @@ int mer_eval_transmittance(mer_context *ctx, const mer_scene_desc *scene, const 
     Params P;
     if (make_params(ctx, scene, P)) return 1;
     P.seed = seed;
-    DevBuf a(ctx), b(ctx), c(ctx), r(ctx);
-    if (a.upload(o, n * 12) || b.upload(d, n * 12) || c.upload(maxt, n * 4) || r.alloc(n * 12)) return 1;
+    DeviceBuffer a, b, c, r;
+    if (a.upload(ctx, o, n * 12) || b.upload(ctx, d, n * 12) || c.upload(ctx, maxt, n * 4) || r.alloc(ctx, n * 12)) return 1;
     int rc = dispatch_modes(ctx, scene, [&](auto curved, auto rif, auto stepper, auto sigma, auto bnd) -> int {
         hipLaunchKernelGGL((eval_transmittance_kernel<decltype(curved)::value, decltype(rif)::value, decltype(stepper)::value, decltype(sigma)::value>),
                            dim3(nblocks(n, 64)), dim3(64), 0, ctx->stream, P, a.as<float>(), b.as<float>(), c.as<float>(), n, r.as<float>());
@@ -756,26 +706,26 @@ int mer_eval_transmittance(mer_context *ctx, const mer_scene_desc *scene, const 
         return 0;
     });
     if (rc) return rc;
-    return r.download(out_tr, n * 12);
+    return r.download(ctx, out_tr, n * 12);
 }
 
 int mer_phase_sample(mer_context *ctx, int32_t phase, float g, const float *wi, const float *u2, int64_t n, float *wo, float *pdf) {
     MER_USE_DEVICE(ctx);
     if (phase == MER_PHASE_HG && (g >= 1 || g <= -1)) return fail(ctx, "The asymmetry parameter must lie in the interval (-1, 1)!");
-    DevBuf a(ctx), b(ctx), c(ctx), e(ctx);
-    if (a.upload(wi, n * 12) || b.upload(u2, n * 8) || c.alloc(n * 12) || e.alloc(n * 4)) return 1;
+    DeviceBuffer a, b, c, e;
+    if (a.upload(ctx, wi, n * 12) || b.upload(ctx, u2, n * 8) || c.alloc(ctx, n * 12) || e.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(phase_sample_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, phase, g, a.as<float>(), b.as<float>(), n, c.as<float>(), e.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (c.download(wo, n * 12)) return 1;
-    return e.download(pdf, n * 4);
+    if (c.download(ctx, wo, n * 12)) return 1;
+    return e.download(ctx, pdf, n * 4);
 }
 int mer_phase_eval(mer_context *ctx, int32_t phase, float g, const float *wi, const float *wo, int64_t n, float *val) {
     MER_USE_DEVICE(ctx);
-    DevBuf a(ctx), b(ctx), c(ctx);
-    if (a.upload(wi, n * 12) || b.upload(wo, n * 12) || c.alloc(n * 4)) return 1;
+    DeviceBuffer a, b, c;
+    if (a.upload(ctx, wi, n * 12) || b.upload(ctx, wo, n * 12) || c.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(phase_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, phase, g, a.as<float>(), b.as<float>(), n, c.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return c.download(val, n * 4);
+    return c.download(ctx, val, n * 4);
 }
 int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, int64_t n, float *out) {
     MER_USE_DEVICE(ctx);
@@ -789,11 +739,11 @@ int mer_emitter_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k,
     if (make_params(ctx, scene, P, true)) return 1;
     if (n <= 0) return 0;
     const float *I = scene->emitters[k].intensity;
-    DevBuf a(ctx), r(ctx);
-    if (a.upload(ref, n * 12) || r.alloc(n * 32)) return 1;
-    hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, P.has_spot ? &ctx->etab->spots[0] : (const DSpot *) nullptr, slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
+    DeviceBuffer a, r;
+    if (a.upload(ctx, ref, n * 12) || r.alloc(ctx, n * 32)) return 1;
+    hipLaunchKernelGGL(emitter_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.points, P.has_spot ? &ctx->etab.as<EmitterTable>()->spots[0] : (const DSpot *) nullptr, slot, I[0], I[1], I[2], a.as<float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return r.download(out, n * 32);
+    return r.download(ctx, out, n * 32);
 }
 static bool is_area_type(int type) { return type == MER_EMITTER_AREA || type == MER_EMITTER_AREA_DISK || type == MER_EMITTER_AREA_SPHERE; }
 int mer_area_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, const float *ref, const float *u2, int64_t n, float *out) {
@@ -806,11 +756,11 @@ int mer_area_direct(mer_context *ctx, const mer_scene_desc *scene, int32_t k, co
     Params P;
     if (make_params(ctx, scene, P, true)) return 1;
     if (n <= 0) return 0;
-    DevBuf a(ctx), b(ctx), r(ctx);
-    if (a.upload(ref, n * 12) || b.upload(u2, n * 8) || r.alloc(n * 48)) return 1;
+    DeviceBuffer a, b, r;
+    if (a.upload(ctx, ref, n * 12) || b.upload(ctx, u2, n * 8) || r.alloc(ctx, n * 48)) return 1;
     hipLaunchKernelGGL(area_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P.rects, slot, a.as<float>(), b.as<float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return r.download(out, n * 48);
+    return r.download(ctx, out, n * 48);
 }
 int mer_area_hit(mer_context *ctx, const mer_scene_desc *scene, const float *o, const float *d, const float *ref, int64_t n, float *out) {
     MER_USE_DEVICE(ctx);
@@ -821,17 +771,17 @@ int mer_area_hit(mer_context *ctx, const mer_scene_desc *scene, const float *o, 
     if (n <= 0) return 0;
     int32_t list_index[MER_MAX_EMITTERS] = {0};
     for (int j = 0, slot = 0; j < scene->n_emitters; ++j) if (is_area_type(scene->emitters[j].type)) list_index[slot++] = j;
-    DevBuf a(ctx), b(ctx), c(ctx), x(ctx), r(ctx);
-    if (a.upload(o, n * 12) || b.upload(d, n * 12) || c.upload(ref, n * 12) || x.upload(list_index, sizeof(list_index)) || r.alloc(n * 32)) return 1;
+    DeviceBuffer a, b, c, x, r;
+    if (a.upload(ctx, o, n * 12) || b.upload(ctx, d, n * 12) || c.upload(ctx, ref, n * 12) || x.upload(ctx, list_index, sizeof(list_index)) || r.alloc(ctx, n * 32)) return 1;
     hipLaunchKernelGGL(area_hit_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, x.as<int32_t>(), a.as<float>(), b.as<float>(), c.as<float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return r.download(out, n * 32);
+    return r.download(ctx, out, n * 32);
 }
 // the scene's envmap record in device memory (the emitter table's), or NULL
 static const DEnvMap *envmap_of(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
     if (make_params(ctx, scene, P, true)) return nullptr;
     if (!P.has_envmap) { fail(ctx, std::string(who) + ": the scene's emitter list has no envmap entry"); return nullptr; }
-    return &ctx->etab->env;
+    return &ctx->etab.as<EmitterTable>()->env;
 }
 int mer_envmap_eval(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_rgb, float *out_pdf) {
     MER_USE_DEVICE(ctx);
@@ -839,11 +789,11 @@ int mer_envmap_eval(mer_context *ctx, const mer_scene_desc *scene, const float *
     const DEnvMap *E = envmap_of(ctx, scene, P, "mer_envmap_eval");
     if (!E) return 1;
     if (n <= 0) return 0;
-    DevBuf a(ctx), v(ctx), q(ctx);
-    if (a.upload(dirs, n * 12) || v.alloc(n * 12) || q.alloc(n * 4)) return 1;
+    DeviceBuffer a, v, q;
+    if (a.upload(ctx, dirs, n * 12) || v.alloc(ctx, n * 12) || q.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(envmap_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, E, a.as<float>(), n, v.as<float>(), q.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return v.download(out_rgb, n * 12) || q.download(out_pdf, n * 4);
+    return v.download(ctx, out_rgb, n * 12) || q.download(ctx, out_pdf, n * 4);
 }
 int mer_envmap_sample(mer_context *ctx, const mer_scene_desc *scene, const float *u2, int64_t n, float *out_dir, float *out_value_over_pdf, float *out_pdf) {
     MER_USE_DEVICE(ctx);
@@ -851,92 +801,94 @@ int mer_envmap_sample(mer_context *ctx, const mer_scene_desc *scene, const float
     const DEnvMap *E = envmap_of(ctx, scene, P, "mer_envmap_sample");
     if (!E) return 1;
     if (n <= 0) return 0;
-    DevBuf a(ctx), d(ctx), v(ctx), q(ctx);
-    if (a.upload(u2, n * 8) || d.alloc(n * 12) || v.alloc(n * 12) || q.alloc(n * 4)) return 1;
+    DeviceBuffer a, d, v, q;
+    if (a.upload(ctx, u2, n * 8) || d.alloc(ctx, n * 12) || v.alloc(ctx, n * 12) || q.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(envmap_sample_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, E, a.as<float>(), n, d.as<float>(), v.as<float>(), q.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return d.download(out_dir, n * 12) || v.download(out_value_over_pdf, n * 12) || q.download(out_pdf, n * 4);
+    return d.download(ctx, out_dir, n * 12) || v.download(ctx, out_value_over_pdf, n * 12) || q.download(ctx, out_pdf, n * 4);
 }
 int mer_rough_dielectric_eval(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *wo, int64_t n,
                               float *out_val, float *out_pdf) {
     MER_USE_DEVICE(ctx);
     if (check_rough(ctx, scene)) return 1;
-    DevBuf a(ctx), b(ctx), c(ctx), e(ctx), f(ctx);
-    if (a.upload(eta, n * 4) || b.upload(wi, n * 12) || c.upload(wo, n * 12) || e.alloc(n * 4) || f.alloc(n * 4)) return 1;
+    DeviceBuffer a, b, c, e, f;
+    if (a.upload(ctx, eta, n * 4) || b.upload(ctx, wi, n * 12) || c.upload(ctx, wo, n * 12) || e.alloc(ctx, n * 4) || f.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(rough_eval_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, scene->rough_distribution, scene->rough_alpha,
                        scene->rough_sample_visible, a.as<float>(), b.as<float>(), c.as<float>(), n, e.as<float>(), f.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (e.download(out_val, n * 4)) return 1;
-    return f.download(out_pdf, n * 4);
+    if (e.download(ctx, out_val, n * 4)) return 1;
+    return f.download(ctx, out_pdf, n * 4);
 }
 int mer_rough_dielectric_sample(mer_context *ctx, const mer_scene_desc *scene, const float *eta, const float *wi, const float *u3, int64_t n,
                                 float *wo, float *weight, float *pdf) {
     MER_USE_DEVICE(ctx);
     if (check_rough(ctx, scene)) return 1;
-    DevBuf a(ctx), b(ctx), c(ctx), e(ctx), f(ctx), g(ctx);
-    if (a.upload(eta, n * 4) || b.upload(wi, n * 12) || c.upload(u3, n * 12) || e.alloc(n * 12) || f.alloc(n * 4) || g.alloc(n * 4)) return 1;
+    DeviceBuffer a, b, c, e, f, g;
+    if (a.upload(ctx, eta, n * 4) || b.upload(ctx, wi, n * 12) || c.upload(ctx, u3, n * 12) || e.alloc(ctx, n * 12) || f.alloc(ctx, n * 4) || g.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(rough_sample_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, scene->rough_distribution, scene->rough_alpha,
                        scene->rough_sample_visible, a.as<float>(), b.as<float>(), c.as<float>(), n, e.as<float>(), f.as<float>(), g.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (e.download(wo, n * 12) || f.download(weight, n * 4)) return 1;
-    return g.download(pdf, n * 4);
+    if (e.download(ctx, wo, n * 12) || f.download(ctx, weight, n * 4)) return 1;
+    return g.download(ctx, pdf, n * 4);
 }
 int mer_camera_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, int64_t n, float *o, float *d) {
     MER_USE_DEVICE(ctx);
     Params P;
-    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST;
+    mer_scene_desc sc = sensor_fields_only(*scene);
     if (make_params(ctx, &sc, P)) return 1;
-    DevBuf a(ctx), b(ctx), c(ctx);
-    if (a.upload(pos2, n * 8) || b.alloc(n * 12) || c.alloc(n * 12)) return 1;
+    DeviceBuffer a, b, c;
+    if (a.upload(ctx, pos2, n * 8) || b.alloc(ctx, n * 12) || c.alloc(ctx, n * 12)) return 1;
     hipLaunchKernelGGL(camera_rays_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<float>(), n, b.as<float>(), c.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (b.download(o, n * 12)) return 1;
-    return c.download(d, n * 12);
+    if (b.download(ctx, o, n * 12)) return 1;
+    return c.download(ctx, d, n * 12);
 }
 int mer_sensor_rays(mer_context *ctx, const mer_scene_desc *scene, const float *pos2, const float *aperture2, int64_t n, float *o, float *d,
                     float *mint, float *maxt) {
     MER_USE_DEVICE(ctx);
     Params P;
-    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST;
+    mer_scene_desc sc = sensor_fields_only(*scene);
     if (make_params(ctx, &sc, P)) return 1;
     const bool lens = sc.sensor == MER_SENSOR_THINLENS || sc.sensor == MER_SENSOR_TELECENTRIC;
     if (lens && !aperture2) return fail(ctx, "mer_sensor_rays: a thinlens / telecentric sensor needs the aperture samples");
-    DevBuf a(ctx), u(ctx), b(ctx), c(ctx), e(ctx), f(ctx);
-    if (a.upload(pos2, n * 8) || b.alloc(n * 12) || c.alloc(n * 12) || e.alloc(n * 4) || f.alloc(n * 4)) return 1;
-    if (lens && u.upload(aperture2, n * 8)) return 1;
+    DeviceBuffer a, u, b, c, e, f;
+    if (a.upload(ctx, pos2, n * 8) || b.alloc(ctx, n * 12) || c.alloc(ctx, n * 12) || e.alloc(ctx, n * 4) || f.alloc(ctx, n * 4)) return 1;
+    if (lens && u.upload(ctx, aperture2, n * 8)) return 1;
     hipLaunchKernelGGL(sensor_rays_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<float>(), lens ? u.as<float>() : (const float *) nullptr, n,
                        b.as<float>(), c.as<float>(), e.as<float>(), f.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    if (b.download(o, n * 12) || c.download(d, n * 12) || e.download(mint, n * 4)) return 1;
-    return f.download(maxt, n * 4);
+    if (b.download(ctx, o, n * 12) || c.download(ctx, d, n * 12) || e.download(ctx, mint, n * 4)) return 1;
+    return f.download(ctx, maxt, n * 4);
 }
 int mer_correlation(mer_context *ctx, const mer_scene_desc *scene, const float *path_length, int64_t n, float *out) {
     MER_USE_DEVICE(ctx);
     Params P;
-    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST;
+    mer_scene_desc sc = sensor_fields_only(*scene);
     if (make_params(ctx, &sc, P)) return 1;
     if (sc.modulation == MER_MODULATION_NONE) return fail(ctx, "Cannot call correlation function when the modulation type is not defined");   // pathlengthsampler.cpp:71-73
-    DevBuf a(ctx), b(ctx);
-    if (a.upload(path_length, n * 4) || b.alloc(n * 4)) return 1;
+    DeviceBuffer a, b;
+    if (a.upload(ctx, path_length, n * 4) || b.alloc(ctx, n * 4)) return 1;
     hipLaunchKernelGGL(correlation_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<float>(), n, b.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return b.download(out, n * 4);
+    return b.download(ctx, out, n * 4);
 }
 int mer_rng_floats(mer_context *ctx, uint64_t seed, uint32_t pixel, uint32_t sample, int32_t n, float *out) {
     MER_USE_DEVICE(ctx);
-    DevBuf a(ctx);
-    if (a.alloc((size_t) n * 4)) return 1;
+    DeviceBuffer a;
+    if (a.alloc(ctx, (size_t) n * 4)) return 1;
     hipLaunchKernelGGL(rng_kernel, dim3(1), dim3(64), 0, ctx->stream, seed, pixel, sample, n, a.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    return a.download(out, (size_t) n * 4);
+    return a.download(ctx, out, (size_t) n * 4);
 }
 int mer_synth_field_dev(mer_context *ctx, int32_t kind, int32_t N, float **data_dev) {
     MER_USE_DEVICE(ctx);
     if (kind < 0 || kind > 2 || N < 2) return fail(ctx, "mer_synth_field_dev: bad arguments");
-    HIP_CHECK(ctx, hipMalloc((void **) data_dev, (size_t) N * N * N * 4));
-    hipLaunchKernelGGL(synth_field_kernel, dim3(8192), dim3(256), 0, ctx->stream, kind, N, *data_dev);
+    DeviceBuffer field;              // the caller's on success (mer_device_free)
+    if (field.alloc(ctx, (size_t) N * N * N * 4)) return 1;
+    hipLaunchKernelGGL(synth_field_kernel, dim3(8192), dim3(256), 0, ctx->stream, kind, N, field.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *data_dev = (float *) field.release();
     return 0;
 }
 

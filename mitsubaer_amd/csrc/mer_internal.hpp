@@ -12,22 +12,50 @@
 #include <map>
 #include <limits>
 
+struct mer_context;
+
 namespace mer {
+
+// The one owner of device memory: a pointer and its capacity in bytes, freed by the destructor (on whatever device is current: every
+// entry point, mer_context_destroy included, selects the context's device first).  Move-only.  alloc / reserve / upload / download
+// return the usual int with the context's error set (defined below HIP_CHECK); no other code allocates or frees.
+struct DeviceBuffer {
+    void *p = nullptr; size_t bytes = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { if (this != &o) { reset(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p) (void) hipFree(p); p = nullptr; bytes = 0; }
+    void *release() { void *q = p; p = nullptr; bytes = 0; return q; }          // to a caller of the C-ABI, who frees it with free_raw
+    static int free_raw(mer_context *ctx, void *raw);
+    int alloc(mer_context *ctx, size_t n);                   // a fresh buffer of n bytes (at least 4), whatever was held before
+    int reserve(mer_context *ctx, size_t n) { return p && bytes >= n ? 0 : alloc(ctx, n); }      // grows, never shrinks; contents are not kept
+    int upload(mer_context *ctx, const void *host, size_t n);      // alloc + copy on the context stream
+    int download(mer_context *ctx, void *host, size_t n) const;    // copy on the context stream + synchronise
+    template <typename T> T *as() const { return (T *) p; }
+    explicit operator bool() const { return p != nullptr; }
+};
+struct PinnedBuffer {              // its pinned-host twin (Pipe::host_live): allocated once, never moved
+    void *p = nullptr;
+    PinnedBuffer() = default;
+    PinnedBuffer(const PinnedBuffer &) = delete;
+    ~PinnedBuffer() { if (p) (void) hipHostFree(p); }
+    int alloc(mer_context *ctx, size_t n);
+};
 
 struct Volume {
     mer_grid_desc desc;
-    void  *dense = nullptr;     // device, dense layout
-    float *cell8 = nullptr;     // device, CELL8 / BRICK records (optional)
-    float *coeff = nullptr;     // device, B-spline coefficients (optional)
+    DeviceBuffer dense;         // dense layout
+    DeviceBuffer cell8;         // CELL8 / BRICK records (optional)
+    DeviceBuffer coeff;         // B-spline coefficients (optional)
     int layout = MER_LAYOUT_DENSE;
-    bool owns_dense = true;
     size_t bytes_dense = 0;
 };
 
 // emitter `envmap` (mer_envmap_upload): one device buffer -- texels [h][w] (4 x fp16), then the float tables cdf_cols [h][w + 1], cdf_rows [h + 1],
 // row_weights [h] at the given byte offsets -- and the normalisation.  Its handle shares the volumes' numbering.
 struct EnvMap {
-    void *dev = nullptr;
+    DeviceBuffer dev;
     int32_t w = 0, h = 0;
     float norm = 0;
     size_t off_cols = 0, off_rows = 0, off_weights = 0;
@@ -46,28 +74,34 @@ struct Recorder {
     mer_fluence_desc box{};
     mer_detector_desc det{};
     int32_t frames = 0;                          // 0: a steady-state fluence grid, a sensitivity grid
-    double *dev = nullptr;
+    DeviceBuffer dev;
     uint64_t n_keys = 0;
     int32_t n_totals = 0;                        // as allocated: 8 or 12 (timed) for fluence, 16 for the others
     bool timed() const { return kind == REC_TIMED; }
     bool track() const { return kind == REC_TRACK; }
     uint64_t n_cells() const { return (uint64_t) box.res[0] * (uint64_t) box.res[1] * (uint64_t) box.res[2]; }
     int32_t faces() const { return det.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
-    double *totals() const { return dev + n_keys * 3; }
+    double *sums() const { return dev.as<double>(); }
+    double *totals() const { return sums() + n_keys * 3; }
     size_t bytes() const { return (n_keys * 3 + (uint64_t) n_totals) * sizeof(double); }
 };
 
 #define MER_MAX_PIPES 4
 struct Pipe {
     hipStream_t stream = nullptr, own_stream = nullptr;      // pipeline 0 runs on the context stream
-    uint32_t *slots = nullptr; uint32_t nslots = 0; uint32_t *live = nullptr; uint32_t *host_live = nullptr;
-    SegQueue eq{}, mq[2]{}, sq[2]{}, cq[2]{};
-    uint32_t *cstate = nullptr; uint32_t cstate_slots = 0;        // parked solver states of K_connect (allocated on first use)
-    unsigned long long *hitq = nullptr, *hitq_ctr = nullptr; unsigned long long hitq_cap = 0;
+    // the pool (prepare_pool, mer_render.hip): nslots counts RECORDS (path slots + side-walk slots); the lists hold record ids and are sized by it
+    DeviceBuffer slots; uint32_t nslots = 0; DeviceBuffer live; PinnedBuffer host_live;
+    // the seven work lists in one order -- eq, mq[0], mq[1], sq[0], sq[1], cq[0], cq[1] -- as the kernels see them (raw pointers, copied into Params)
+    // and the owners of their arrays beside them
+    enum { NQ = 7, EQ = 0, MQ = 1, SQ = 3, CQ = 5 };
+    SegQueue q[NQ]{};
+    DeviceBuffer q_items[NQ], q_counts[NQ], q_keys[NQ];           // keys: the march lists only, with the first render that sorts them
+    DeviceBuffer cstate;                                          // parked solver states of K_connect, one per record (allocated on first use)
+    DeviceBuffer hitq, hitq_ctr; unsigned long long hitq_cap = 0;
     hipEvent_t readback[2] = {nullptr, nullptr}, finished = nullptr;     // two batches in flight per pipeline
     std::vector<hipEvent_t> pass_events;          // 3 per pass: before K_event, between, after K_march
-    uint8_t *side_state = nullptr; uint32_t side_state_slots = 0;   // busy bytes of the side-walk slots, 8 per path slot (allocated with the first render that spawns)
-    uint32_t *msort = nullptr; uint32_t msort_cap = 0;            // spatial sort of the march list: sorted ids, gathered ids, keys (cap each), histogram, cursors, count
+    DeviceBuffer side_state;                                      // busy bytes of the side-walk slots, 8 per path slot (allocated with the first render that spawns)
+    DeviceBuffer msort;                                           // spatial sort of the march list: sorted ids (one per record), histogram, cursors, count
 };
 
 // Tuning / A-B switches of a context (mer_context_set_option).  Defaults are the measured optima of DESIGN.md section 4.
@@ -105,13 +139,14 @@ struct mer_context {
     std::map<int, mer::Volume> volumes;
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
     std::map<int, mer::Recorder> recorders;      // fluence grids, exitance maps, sensitivity grids (handles from next_handle)
-    uint32_t *detect_list = nullptr; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 4 arrays of detect_cap words
+    mer::DeviceBuffer detect_list; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 4 arrays of detect_cap words
     int next_handle = 1;
-    unsigned long long *counters = nullptr;      // MER_C_COUNT x replicas + work counter
-    float *ftable = nullptr; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
+    mer::DeviceBuffer counters;                  // MER_C_COUNT x replicas + work counter
+    mer::DeviceBuffer ftable; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds
     // the emitter table on the device (points, rectangles, spot cones, the envmap record: mer_device.hpp) and the value it holds, once uploaded
-    mer::EmitterTable *etab = nullptr; mer::EmitterTable etab_host; bool etab_valid = false;
-    unsigned long long *chk = nullptr;           // MER_BOUNDS_CHECK build: violation record (count, kind, index, limit)
+    mer::DeviceBuffer etab; mer::EmitterTable etab_host; bool etab_valid = false;
+    mer::DeviceBuffer chk_buf;                   // MER_BOUNDS_CHECK build: violation record (count, kind, index, limit) ...
+    unsigned long long *chk = nullptr;           // ... as every kernel argument carries it (null in the plain build)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     hipDeviceProp_t prop;
@@ -133,15 +168,38 @@ struct mer_context {
 
 namespace mer {
 
+inline int DeviceBuffer::free_raw(mer_context *ctx, void *raw) { HIP_CHECK(ctx, hipFree(raw)); return 0; }
+inline int DeviceBuffer::alloc(mer_context *ctx, size_t n) {
+    reset();
+    HIP_CHECK(ctx, hipMalloc(&p, n ? n : 4));
+    bytes = n;
+    return 0;
+}
+inline int DeviceBuffer::upload(mer_context *ctx, const void *host, size_t n) {
+    if (alloc(ctx, n)) return 1;
+    if (n) HIP_CHECK(ctx, hipMemcpyAsync(p, host, n, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
+inline int DeviceBuffer::download(mer_context *ctx, void *host, size_t n) const {
+    if (n) HIP_CHECK(ctx, hipMemcpyAsync(host, p, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+inline int PinnedBuffer::alloc(mer_context *ctx, size_t n) { HIP_CHECK(ctx, hipHostMalloc(&p, n)); return 0; }
+
 static inline int fail(mer_context *ctx, const std::string &msg) { ctx->error = msg; return 1; }
 static inline unsigned nblocks(int64_t n, int bs = 256) { return (unsigned) std::max<int64_t>(1, (n + bs - 1) / bs); }
+
+// the scene of a leaf entry point that reads the sensor fields only: no volume is looked up
+static inline mer_scene_desc sensor_fields_only(mer_scene_desc sc) { sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST; return sc; }
 
 // mer_scene.hip: scene flattening (host only)
 // linear part of a row-major 3x4 float matrix in double; determinant and inverse (returns the determinant) of a 3x3 matrix by cofactors
 static inline void linear3(const float m[12], double M[3][3]) { for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[i][j] = m[4 * i + j]; }
 double det3(const double M[3][3]);
 double inverse3(const double M[3][3], double inv[3][3]);
-void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g);
+// records = false: the dense data even where the volume has a record layout (spectrum look-ups, the albedo)
+void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g, bool records = true);
 // point_outside (optional): a point emitter of the scene lies outside the cube / sphere medium shape (launch_render picks the connect kernel by it)
 int make_params(mer_context *ctx, const mer_scene_desc *sc, Params &P, bool allow_sdf = false, bool *point_outside = nullptr);
 int film_frames(mer_context *ctx, const mer_scene_desc *sc, int &frames);
@@ -170,6 +228,8 @@ bool kernels_bspline(int stepper, int sigma, bool extra, KernelSet &k);
 bool kernels_sdf_curved(int rifk, int stepper, int sigma, KernelSet &k);
 bool kernels_sdf_curved_records(int rifk, int stepper, int sigma, KernelSet &k);      // BRICK27 (both load kinds), CELL8 with global loads
 int tile_skew_for(int tiles_x, int tile_count, int tile_deal);
+// the shard's check ("invalid shard") and the work fields of P: sample range, tile deal, total_work
+int set_work(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, Params &P);
 int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
                   uint64_t n_film, uint64_t n_path_out);
 
@@ -180,10 +240,10 @@ int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shar
 // family's kernels, launch and entry points; what they share is mer_lightpath_host.hpp
 
 // mer_sdf_build.hip: signed-distance grid of a triangle mesh.  tri12_host: 12 floats per triangle (3 vertices, xyz + one unused float each), already
-// validated; on success *sdf_dev / *w_dev are device arrays of one float per node (x fastest) that the caller frees.
+// validated; on success sdf / winding hold one float per node (x fastest).
 struct SdfGridArgs { int32_t res[3]; float lo[3], step[3]; uint64_t n_nodes; unsigned long long *chk; };
 #define MER_SDF_DEFAULT_CHUNK 4096                         // triangles per launch when the caller passes 0
 #define MER_SDF_NODES_PER_LAUNCH ((uint64_t) 1 << 24)      // nodes per launch (256^3): with the default chunk 6.9e10 pairs per launch
-int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host, int64_t n_tri, int32_t max_tri_per_launch, float **sdf_dev, float **w_dev);
+int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host, int64_t n_tri, int32_t max_tri_per_launch, DeviceBuffer &sdf, DeviceBuffer &winding);
 
 }  // namespace mer

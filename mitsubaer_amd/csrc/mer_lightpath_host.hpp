@@ -33,11 +33,9 @@ template <class F> static typename F::Kernel pick_light_kernel(const mer_scene_d
 // ---- One render from light paths.  The launcher comes in two steps: open_light_paths makes P = make_params(ctx, scene, P, false) among the
 // refusals every recorder's launch shares, in their one order, and the launch follows once the caller has refused what is its own (the
 // track-length grid's analog requirement) and filled its kernel arguments.  The light tracer itself (launch_ptracer) has other refusals around
-// the same check of the shard and the emitters:
-static inline int check_light_paths(mer_context *ctx, const Params &P, const mer_shard *shard) {
-    if (!shard || shard->spp_count < 0 || shard->spp_stride <= 0 || shard->tile_count <= 0 || shard->tile_rank < 0 ||
-        shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
-        return fail(ctx, "invalid shard");
+// the same check of the shard (set_work, which also lays the shard's work ids out in P) and the emitters:
+static inline int check_light_paths(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, Params &P) {
+    if (set_work(ctx, scene, shard, P)) return 1;
     if (P.n_point <= 0) return fail(ctx, "ptracer: the scene has no emitter (list entries of kind point, spot or collimated)");
     return 0;
 }
@@ -47,23 +45,16 @@ static inline int open_light_paths(mer_context *ctx, const mer_scene_desc *scene
     if (scene->integrator != MER_INTEGRATOR_PTRACER) return fail(ctx, not_ptracer);
     if (make_params(ctx, scene, P, false)) return 1;
     if (other_boundary && scene->boundary != R.det.boundary) return fail(ctx, other_boundary);
-    return check_light_paths(ctx, P, shard);
+    return check_light_paths(ctx, scene, shard, P);
 }
 // The light paths of a shard are the (pixel, sample index) pairs K_gen would enumerate: the work ids are laid out as launch_render lays them
-// out (decode_work) and launched PT_PATHS_PER_LAUNCH (curved rays: PT_PATHS_PER_LAUNCH_CURVED) at a time on the context stream as
+// out (set_work, by check_light_paths above) and launched PT_PATHS_PER_LAUNCH (curved rays: PT_PATHS_PER_LAUNCH_CURVED) at a time on the context stream as
 // kernel(P, extra ..., first, count).  Returns synchronised, as the wavefront loop does.  film = nullptr: the sensor fields only enumerate the paths.
 // The loop itself: per_chunk(first, count) launches what one chunk of work ids needs and returns nonzero (with the context's message set) to stop.
 template <class PerChunk>
-static int for_light_path_chunks(mer_context *ctx, const mer_scene_desc *scene, Params &P, const mer_shard *shard, uint64_t seed, float *film_dev,
+static int for_light_path_chunks(mer_context *ctx, const mer_scene_desc *scene, Params &P, uint64_t seed, float *film_dev,
                                  uint64_t n_film, PerChunk per_chunk) {
     P.seed = seed;
-    P.spp_begin = shard->spp_begin; P.spp_count = shard->spp_count; P.spp_stride = shard->spp_stride;
-    P.tile_rank = shard->tile_rank; P.tile_count = shard->tile_count;
-    P.tiles_x = (scene->width + MER_TILE - 1) / MER_TILE; P.tiles_y = (scene->height + MER_TILE - 1) / MER_TILE;
-    P.tile_skew = tile_skew_for(P.tiles_x, shard->tile_count, (int) ctx->opt.tile_deal);
-    const int ntiles = P.tiles_x * P.tiles_y;
-    P.ntiles_mine = (ntiles - shard->tile_rank + shard->tile_count - 1) / shard->tile_count;
-    P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) shard->spp_count;
     P.film = film_dev; P.path_out = nullptr; P.n_film = n_film; P.n_path_out = 0;
     HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (P.total_work == 0) return 0;
@@ -81,10 +72,10 @@ static int for_light_path_chunks(mer_context *ctx, const mer_scene_desc *scene, 
 }
 // one kernel per chunk, as kernel(P, extra ..., first, count)
 template <class Kernel, class... Extra>
-static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Params &P, const mer_shard *shard, uint64_t seed, float *film_dev,
+static int launch_light_paths(mer_context *ctx, const mer_scene_desc *scene, Params &P, uint64_t seed, float *film_dev,
                               uint64_t n_film, Kernel kernel, const Extra &... extra) {
     if (!kernel) return fail(ctx, "unsupported rif_mode / stepper combination");
-    return for_light_path_chunks(ctx, scene, P, shard, seed, film_dev, n_film, [&](uint64_t first, uint32_t count) {
+    return for_light_path_chunks(ctx, scene, P, seed, film_dev, n_film, [&](uint64_t first, uint32_t count) {
         hipLaunchKernelGGL(kernel, dim3((count + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, ctx->stream, P, extra..., first, count);
         HIP_CHECK(ctx, hipGetLastError());
         return 0;
@@ -139,26 +130,23 @@ static inline Recorder *find_recorder(mer_context *ctx, int h, int family, const
 }
 // the zeroed buffer of a checked description (family, kind, n_keys and n_totals set) and its handle
 static inline int alloc_sums(mer_context *ctx, Recorder &v, const std::string &clearing_failed, int *out) {
-    HIP_CHECK(ctx, hipMalloc((void **) &v.dev, v.bytes()));
-    if (hipMemsetAsync(v.dev, 0, v.bytes(), ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        (void) hipFree(v.dev);
+    if (v.dev.alloc(ctx, v.bytes())) return 1;
+    if (hipMemsetAsync(v.dev.p, 0, v.bytes(), ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         return fail(ctx, clearing_failed);
-    }
     const int h = ctx->next_handle++;
-    ctx->recorders[h] = v;
+    ctx->recorders[h] = std::move(v);
     *out = h;
     return 0;
 }
 static inline int clear_sums(mer_context *ctx, const Recorder *v) {
     if (!v) return 1;
-    HIP_CHECK(ctx, hipMemsetAsync(v->dev, 0, v->bytes(), ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(v->dev.p, 0, v->bytes(), ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 static inline int destroy_sums(mer_context *ctx, int h, const Recorder *v) {
     if (!v) return 1;
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void) hipFree(v->dev);
     ctx->recorders.erase(h);
     return 0;
 }
@@ -166,7 +154,7 @@ static inline int destroy_sums(mer_context *ctx, int h, const Recorder *v) {
 static inline int read_sums(mer_context *ctx, const Recorder &v, double *sums, double *totals, const char *who) {
     if (!totals) return fail(ctx, std::string(who) + ": invalid arguments");
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    if (sums) HIP_CHECK(ctx, hipMemcpy(sums, v.dev, v.n_keys * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (sums) HIP_CHECK(ctx, hipMemcpy(sums, v.sums(), v.n_keys * 3 * sizeof(double), hipMemcpyDeviceToHost));
     HIP_CHECK(ctx, hipMemcpy(totals, v.totals(), (size_t) v.n_totals * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -174,7 +162,7 @@ static inline int read_sums(mer_context *ctx, const Recorder &v, double *sums, d
 // (Grid = FluenceGrid, mer_fluence.hpp, which only the translation units of those kernels include)
 template <class Grid> static Grid fluence_grid(const mer_context *ctx, const Recorder &R) {
     Grid G;
-    G.sums = R.dev; G.totals = R.totals(); G.chk = ctx->chk; G.n_cells = R.n_cells();
+    G.sums = R.sums(); G.totals = R.totals(); G.chk = ctx->chk; G.n_cells = R.n_cells();
     G.frames = R.timed() ? R.frames : 0; G.t_min = R.timed() ? R.det.t_min : 0; G.t_bin = R.timed() ? R.det.t_bin : 0;
     for (int a = 0; a < 3; a++) { G.res[a] = R.box.res[a]; G.bmin[a] = R.box.bmin[a]; G.bmax[a] = R.box.bmax[a]; }
     return G;

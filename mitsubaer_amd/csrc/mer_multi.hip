@@ -65,8 +65,8 @@ struct mer_multi {
     Rccl rccl;
     std::vector<ncclComm_t> comms;            // made on first use, for exactly this device list
     // per-context film + the staging buffer of the peer-copy reduction (on the first device); they grow, never shrink
-    std::vector<float *> film; size_t film_floats = 0;
-    float *staging = nullptr; size_t staging_floats = 0;
+    std::vector<mer::DeviceBuffer> film;
+    mer::DeviceBuffer staging;
     int last_reduce = MER_REDUCE_NONE; std::vector<float> last_render_ms; float last_reduce_ms = 0;
     uint64_t last_counters[MER_C_COUNT] = {};
 };
@@ -100,7 +100,7 @@ int mer_multi_create(const int32_t *device_ids, int32_t n, mer_multi **out) {
         int can = 0;
         if (hipDeviceCanAccessPeer(&can, m->devices[0], m->devices[i]) == hipSuccess && can) { (void) hipSetDevice(m->devices[0]); (void) hipDeviceEnablePeerAccess(m->devices[i], 0); (void) hipGetLastError(); }
     }
-    m->film.assign(n, nullptr); m->last_render_ms.assign(n, 0.0f);
+    m->film.resize(n); m->last_render_ms.assign(n, 0.0f);
     *out = m;
     return 0;
 }
@@ -110,8 +110,8 @@ void mer_multi_destroy(mer_multi *m) {
     if (m->rccl.handle) for (ncclComm_t c : m->comms) if (c) (void) m->rccl.CommDestroy(c);
     for (size_t i = 0; i < m->ctx.size(); i++) {
         (void) hipSetDevice(m->devices[i]);
-        if (i < m->film.size() && m->film[i]) (void) hipFree(m->film[i]);
-        if (i == 0 && m->staging) (void) hipFree(m->staging);
+        if (i < m->film.size()) m->film[i].reset();
+        if (i == 0) m->staging.reset();
         if (m->ctx[i]) { (void) mer_context_set_stream(m->ctx[i], nullptr); mer_context_destroy(m->ctx[i]); }
         if (i < m->streams.size() && m->streams[i]) (void) hipStreamDestroy(m->streams[i]);
     }
@@ -172,14 +172,9 @@ int mer_multi_render(mer_multi *m, const mer_scene_desc *scene, int32_t shard_mo
     int32_t ch = 5;
     if (mer_film_channels(m->ctx[0], scene, &ch)) return mfail(m, mer_last_error(m->ctx[0]));
     const size_t floats = (size_t) scene->width * scene->height * (size_t) ch;
-    if (floats > m->film_floats) {
-        for (int i = 0; i < n; i++) {
-            MULTI_HIP(m, hipSetDevice(m->devices[i]));
-            if (m->film[i]) (void) hipFree(m->film[i]);
-            m->film[i] = nullptr;
-            MULTI_HIP(m, hipMalloc((void **) &m->film[i], floats * sizeof(float)));
-        }
-        m->film_floats = floats;
+    for (int i = 0; i < n; i++) {
+        MULTI_HIP(m, hipSetDevice(m->devices[i]));
+        if (m->film[i].reserve(m->ctx[i], floats * sizeof(float))) return mfail(m, mer_last_error(m->ctx[i]));
     }
     // ---- render: one host thread per context (each blocks in its own wavefront loop)
     std::vector<int> rc(n, 0);
@@ -191,8 +186,8 @@ int mer_multi_render(mer_multi *m, const mer_scene_desc *scene, int32_t shard_mo
             mer_shard sh;
             if (shard_mode == MER_SHARD_SAMPLES) { sh.spp_begin = spp_begin + i; sh.spp_count = std::max(0, (spp_count - i + n - 1) / n); sh.spp_stride = n; sh.tile_rank = 0; sh.tile_count = 1; }
             else { sh.spp_begin = spp_begin; sh.spp_count = spp_count; sh.spp_stride = 1; sh.tile_rank = i; sh.tile_count = n; }
-            rc[i] = (hipSetDevice(m->devices[i]) != hipSuccess) || mer_counters_reset(c) || mer_film_zero_n(c, m->film[i], scene->width, scene->height, ch) ||
-                    mer_render(c, scene, &sh, seed, m->film[i]) || mer_synchronize(c);
+            rc[i] = (hipSetDevice(m->devices[i]) != hipSuccess) || mer_counters_reset(c) || mer_film_zero_n(c, m->film[i].as<float>(), scene->width, scene->height, ch) ||
+                    mer_render(c, scene, &sh, seed, m->film[i].as<float>()) || mer_synchronize(c);
             m->last_render_ms[i] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         });
     }
@@ -219,7 +214,7 @@ int mer_multi_render(mer_multi *m, const mer_scene_desc *scene, int32_t shard_mo
         ncclResult_t r = R.GroupStart();
         for (int i = 0; i < n && r == ncclSuccess; i++) {
             MULTI_HIP(m, hipSetDevice(m->devices[i]));
-            r = R.Reduce(m->film[i], m->film[i], floats, ncclFloat, ncclSum, 0, m->comms[i], m->streams[i]);
+            r = R.Reduce(m->film[i].p, m->film[i].p, floats, ncclFloat, ncclSum, 0, m->comms[i], m->streams[i]);
         }
         const ncclResult_t r2 = R.GroupEnd();
         if (r != ncclSuccess || r2 != ncclSuccess) return mfail(m, std::string("ncclReduce failed: ") + R.GetErrorString(r != ncclSuccess ? r : r2));
@@ -229,22 +224,18 @@ int mer_multi_render(mer_multi *m, const mer_scene_desc *scene, int32_t shard_mo
         return mfail(m, "mer_multi_render: RCCL requested but unavailable: " + (m->distinct ? m->rccl.why : std::string("a device is listed twice")));      // rccl = 2 demands it
     } else if (n > 1) {
         MULTI_HIP(m, hipSetDevice(m->devices[0]));
-        if (m->staging_floats < floats) {
-            if (m->staging) (void) hipFree(m->staging);
-            m->staging = nullptr;
-            MULTI_HIP(m, hipMalloc((void **) &m->staging, floats * sizeof(float)));
-            m->staging_floats = floats;
-        }
+        if (m->staging.reserve(m->ctx[0], floats * sizeof(float))) return mfail(m, mer_last_error(m->ctx[0]));
+        float *staging = m->staging.as<float>();
         for (int i = 1; i < n; i++) {         // context order: the summation order does not depend on which render finished first
-            if (m->devices[i] == m->devices[0]) MULTI_HIP(m, hipMemcpyAsync(m->staging, m->film[i], floats * sizeof(float), hipMemcpyDeviceToDevice, m->streams[0]));
-            else MULTI_HIP(m, hipMemcpyPeerAsync(m->staging, m->devices[0], m->film[i], m->devices[i], floats * sizeof(float), m->streams[0]));
-            hipLaunchKernelGGL(film_add_kernel, dim3((unsigned) ((floats / 4 + 255) / 256 + 1)), dim3(256), 0, m->streams[0], m->film[0], m->staging, floats);
+            if (m->devices[i] == m->devices[0]) MULTI_HIP(m, hipMemcpyAsync(staging, m->film[i].p, floats * sizeof(float), hipMemcpyDeviceToDevice, m->streams[0]));
+            else MULTI_HIP(m, hipMemcpyPeerAsync(staging, m->devices[0], m->film[i].p, m->devices[i], floats * sizeof(float), m->streams[0]));
+            hipLaunchKernelGGL(film_add_kernel, dim3((unsigned) ((floats / 4 + 255) / 256 + 1)), dim3(256), 0, m->streams[0], m->film[0].as<float>(), staging, floats);
         }
         MULTI_HIP(m, hipGetLastError());
         MULTI_HIP(m, hipStreamSynchronize(m->streams[0]));
         m->last_reduce = MER_REDUCE_PEER_COPY;
     }
-    if (mer_film_download_n(m->ctx[0], m->film[0], scene->width, scene->height, ch, film_host)) return mfail(m, mer_last_error(m->ctx[0]));
+    if (mer_film_download_n(m->ctx[0], m->film[0].as<float>(), scene->width, scene->height, ch, film_host)) return mfail(m, mer_last_error(m->ctx[0]));
     m->last_reduce_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int k = 0; k < MER_C_COUNT; k++) m->last_counters[k] = 0;
     for (int i = 0; i < n; i++) {

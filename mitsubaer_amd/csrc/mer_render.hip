@@ -112,15 +112,12 @@ __global__ void __launch_bounds__(MER_BLOCK) msort_scatter_kernel(const Params P
         if (key[k] != 0xffffffffu) P.msorted[MER_CHK(P.chk, CHK_QUEUE_ITEM, h[key[k]] + rank[k], P.nslots_all)] = item[k];
 }
 
-int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
-                  uint64_t n_film, uint64_t n_path_out) {
-    Params P; bool point_outside = false;
-    if (make_params(ctx, scene, P, true, &point_outside)) return 1;
+// The work of a shard as the kernels enumerate it (decode_work): the shard's one check, then the sample range, the tile deal and the number of
+// work ids.  launch_render and the light-path launches (check_light_paths, mer_lightpath_host.hpp) lay their work out here.
+int set_work(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, Params &P) {
     if (!shard || shard->spp_count < 0 || shard->spp_stride <= 0 || shard->tile_count <= 0 || shard->tile_rank < 0 ||
         shard->tile_rank >= shard->tile_count || shard->spp_begin < 0)
         return fail(ctx, "invalid shard");
-    const Options &opt = ctx->opt;
-    P.seed = seed;
     P.spp_begin = shard->spp_begin; P.spp_count = shard->spp_count; P.spp_stride = shard->spp_stride;
     P.tile_rank = shard->tile_rank; P.tile_count = shard->tile_count;
     P.tiles_x = (scene->width + MER_TILE - 1) / MER_TILE; P.tiles_y = (scene->height + MER_TILE - 1) / MER_TILE;
@@ -128,18 +125,41 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     const int ntiles = P.tiles_x * P.tiles_y;
     P.ntiles_mine = (ntiles - shard->tile_rank + shard->tile_count - 1) / shard->tile_count;
     P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) shard->spp_count;
-    P.film = film_dev; P.path_out = path_out_dev; P.n_film = n_film; P.n_path_out = n_path_out;
-    HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (P.total_work == 0) return 0;
+    return 0;
+}
 
+// What a render decides before it touches the device: the kernels it launches, the stages a pass has, and every size the pools are made to.
+struct RenderPlan {
+    KernelSet ks{};
+    bool extra = false, connect_stage = false, spawn = false;
+    uint32_t slot_mult = 1;              // records per path slot: the slot itself and its side-walk slots
+    int msort_bits = 0, npipes = 1, ksteps0 = 0, connect_launches = 0;
+    uint32_t want = 0;                   // path slots per pipeline
+    unsigned gen_blocks_max = 1;
+    unsigned long long ring = 1;         // ids of a pipeline's hit ring
+    // event-queue segments: a segment of class c receives the lanes of the waves w = s (mod segments per class) of EVERY producer launch of
+    // the row -- K_march plus connect_launches K_connect launches, each of which re-packs its pending lanes into its first waves
+    uint64_t eq_segcap(uint32_t cap) const { return std::min<uint64_t>((uint64_t) cap, (uint64_t) ((connect_stage ? connect_launches : 0) + 2) * (cap / (MER_NSEG / MER_EV_CLASSES))) + 256u; }
+    // ids per segment of work list k (Pipe::q) in a pool of cap records
+    uint32_t segcap(int k, uint32_t cap) const {
+        if (k == Pipe::EQ) return (uint32_t) eq_segcap(cap);                        // every lane may be of one event class
+        if (k == Pipe::MQ || k == Pipe::MQ + 1) return 2u * (cap / (MER_NSEG / MER_MQ_CLASSES)) + 256u;   // ... or of one march class
+        if (k == Pipe::CQ || k == Pipe::CQ + 1) return cap + 256u;   // every slot may be pending, in one class
+        return 2u * (cap / MER_NSEG) + 256u;          // two producer kernels may feed one segment
+    }
+};
+
+// fills the plan: no HIP call.  per_path: the render writes per-path output
+static int plan_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, const Params &P, bool point_outside, bool per_path, RenderPlan &pl) {
+    const Options &opt = ctx->opt;
     const bool has_point = P.n_point > 0;            // the legacy point / area fields or the emitter list (make_params)
     const bool curved = scene->rif_mode != MER_RIF_CONST;
     // EXTRA kernels carry the point emitter, the envmap, the modulated film, the dielectric boundary and the sensors beside the pinhole; the signed-distance boundary exists in
     // the EXTRA kernels only
     const bool has_area = P.n_rect > 0;
-    const bool extra = scene->boundary == MER_BOUNDARY_SDF || has_point || has_area || P.has_envmap || scene->modulation != MER_MODULATION_NONE || scene->boundary_bsdf != MER_BSDF_NULL
+    const bool extra = pl.extra = scene->boundary == MER_BOUNDARY_SDF || has_point || has_area || P.has_envmap || scene->modulation != MER_MODULATION_NONE || scene->boundary_bsdf != MER_BSDF_NULL
                        || scene->sensor != MER_SENSOR_PERSPECTIVE;       // the other three sensor kinds start their paths in the EXTRA kernels (primary_ray)
-    KernelSet ks{};
+    KernelSet &ks = pl.ks;
     if (!pick_kernels(ctx, scene, extra, ks)) {
         if (scene->boundary == MER_BOUNDARY_SDF && curved) return fail(ctx, "signed-distance boundary: no kernel for this RIF layout (MER_LAYOUT_BRICK125 is not built with it)");
         return fail(ctx, "unsupported rif_mode / stepper combination");
@@ -153,7 +173,7 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     const bool inline_walks = opt.inline_walks && ks.event_inline && !curved && scene->method != MER_METHOD_SIMPSON;
     if (inline_walks) ks.event = ks.event_inline;
     if (scene->boundary_bsdf == MER_BSDF_HROUGHDIELECTRIC) ks.event = inline_walks ? ks.event_inline_rough : ks.event_rough;   // its own instances (mer_wavefront.hpp)
-    const bool connect_stage = has_point && curved && scene->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC;   // a rough boundary: the surface vertex samples the emitter
+    const bool connect_stage = pl.connect_stage = has_point && curved && scene->boundary_bsdf != MER_BSDF_HROUGHDIELECTRIC;   // a rough boundary: the surface vertex samples the emitter
     // any point emitter outside the shape is reached through the boundary: the kernel that carries the refraction code (it connects to emitters
     // inside the shape as well; signed-distance shapes: the plain kernel carries it too, the side is tested per connection)
     if (connect_stage && point_outside) ks.connect = ks.connect_cross;
@@ -162,132 +182,130 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     // the path slots -- when the render is a steady-state film with an environment to reach (per-path output keeps every walk in the path's own lane:
     // one value per path, written once, bit-reproducible)
     const bool has_env = scene->env_radiance[0] != 0 || scene->env_radiance[1] != 0 || scene->env_radiance[2] != 0;
-    const bool spawn = opt.spawn_walks && curved && !extra && has_env && !path_out_dev && scene->decomposition == MER_DECOMPOSITION_NONE;
-    const uint32_t slot_mult = spawn ? 1u + 2u * MER_SIDE_PER_KIND : 1u;
+    const bool spawn = pl.spawn = opt.spawn_walks && curved && !extra && has_env && !per_path && scene->decomposition == MER_DECOMPOSITION_NONE;
+    pl.slot_mult = spawn ? 1u + 2u * MER_SIDE_PER_KIND : 1u;
     // spatial sort of the march lists (msort_* kernels): plain curved kernels on a gridded RIF inside a box or sphere
-    const int msort_bits = (curved && !extra && scene->boundary != MER_BOUNDARY_SDF && P.rif.res[0] > 1 && P.rif.wmax[0] > P.rif.wmin[0]) ? (int) opt.march_sort : 0;
+    pl.msort_bits = (curved && !extra && scene->boundary != MER_BOUNDARY_SDF && P.rif.res[0] > 1 && P.rif.wmax[0] > P.rif.wmin[0]) ? (int) opt.march_sort : 0;
     int npipes = (int) opt.pipes;
     if (shard->spp_count < npipes) npipes = std::max(1, shard->spp_count);
     uint32_t want = opt.nslots > 0 ? (uint32_t) opt.nslots : (uint32_t) ctx->prop.multiProcessorCount * 2048u * 4u;   // 4 x the resident lanes of the chip, over all pipelines
     // a small render (a tile shard of a strong-scaled job, a preview): with fewer than ~8 paths per slot the slots are never refilled and the
     // lists only get sparser; a quarter of the slots keeps the wavefront denser while it drains (+3 ... 5 % at 8 ... 32 spp, ab_adaptive_k.txt)
     if (opt.nslots == 0 && opt.small_render_slots && P.total_work / 8 < want) want = (uint32_t) std::max<uint64_t>(want / 4, P.total_work / 8);
-    want = (want / (uint32_t) npipes + MER_BLOCK - 1) / MER_BLOCK * MER_BLOCK;       // per pipeline
-    const int ksteps0 = (int) opt.ksteps;
+    pl.want = want = (want / (uint32_t) npipes + MER_BLOCK - 1) / MER_BLOCK * MER_BLOCK;       // per pipeline
+    pl.npipes = npipes; pl.ksteps0 = (int) opt.ksteps;
+    // K_connect runs one solver unit (one traced ray) per pending connection per launch: several launches per pass
+    pl.connect_launches = (int) opt.connect_launches;
+    // K_gen: one launch = gen_blocks x 4 waves x 64 x gen_iters work ids
+    const unsigned gen_blocks_max = pl.gen_blocks_max = std::max(1u, std::min(want / MER_BLOCK, 1024u));
+    const unsigned long long ids_per_launch = (unsigned long long) gen_blocks_max * (MER_BLOCK / 64) * 64ull * (unsigned long long) P.gen_iters;
+    // The hit ring holds what K_gen's throttle lets wait (cap / 2: a wave produces while at most that many ids are waiting) plus,
+    // in the worst case, every id of ONE launch (all its waves read the tail before any of them pushes, and every camera sample
+    // may hit the medium): capacity >= 2 x max(slots, ids per launch), or unread ids would be overwritten.
+    unsigned long long ring = 1; while (ring < 2ull * std::max<unsigned long long>(want, ids_per_launch)) ring <<= 1;
+    pl.ring = ring;
+    return 0;
+}
+
+// Pipeline q of a render: its stream and events, its pool grown to the plan's sizes, R.P wired to it, and what a render must find cleared.
+static int prepare_pool(mer_context *ctx, const RenderPlan &pl, const Params &P, const mer_shard *shard, int q, Run &R) {
+    Pipe &pp = ctx->pipes[q];
+    const uint32_t want = pl.want, slot_mult = pl.slot_mult;
+    if (q == 0) pp.stream = ctx->stream;
+    else if (!pp.own_stream) { HIP_CHECK(ctx, hipStreamCreateWithFlags(&pp.own_stream, hipStreamNonBlocking)); }
+    if (q > 0) { pp.stream = pp.own_stream; HIP_CHECK(ctx, hipStreamWaitEvent(pp.stream, ctx->ev0, 0)); }   // after what the caller queued (film zeroing ...)
+    // pp.nslots counts RECORDS (path slots + side-walk slots); the lists hold record ids and are sized by it.  Slots, lists and ring grow together,
+    // so that every segcap is the one its list was reserved for (a list may be longer than its segcap asks: reserve never shrinks)
+    if (pp.nslots < want * slot_mult || pp.hitq_cap < pl.ring || (pp.nslots && pp.q[Pipe::EQ].segcap < pl.eq_segcap(pp.nslots))) {                 // capacity: grows, never shrinks
+        const uint32_t cap = std::max(want * slot_mult, pp.nslots);
+        pp.nslots = 0;
+        if (pp.slots.reserve(ctx, (size_t) cap * MER_SLOT_WORDS * sizeof(uint32_t))) return 1;
+        for (int k = 0; k < Pipe::NQ; k++) {
+            SegQueue &sq = pp.q[k];
+            sq.segcap = pl.segcap(k, cap);
+            if (pp.q_items[k].reserve(ctx, (size_t) sq.segcap * MER_NSEG * sizeof(uint32_t)) ||
+                pp.q_counts[k].reserve(ctx, (size_t) MER_LIVE_SLOTS * MER_NSEG * sizeof(uint32_t))) return 1;
+            sq.items = pp.q_items[k].as<uint32_t>(); sq.counts = pp.q_counts[k].as<uint32_t>(); sq.chk = ctx->chk;
+        }
+        pp.hitq_cap = std::max(pl.ring, pp.hitq_cap);
+        if (pp.hitq.reserve(ctx, (size_t) pp.hitq_cap * sizeof(unsigned long long))) return 1;
+        pp.nslots = cap;
+    }
+    if (pp.live.reserve(ctx, MER_LIVE_SLOTS * sizeof(uint32_t)) || (!pp.host_live.p && pp.host_live.alloc(ctx, 8 * sizeof(uint32_t))) ||
+        pp.hitq_ctr.reserve(ctx, 64 * sizeof(unsigned long long))) return 1;       // hitq_ctr: [0] tail, [32] head, [48] this pipeline's work counter
+    for (hipEvent_t *e : {&pp.readback[0], &pp.readback[1], &pp.finished}) if (!*e) HIP_CHECK(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    // pipeline q's part of the shard: sample indices spp_begin + (q + k npipes) spp_stride
+    R.P = P;
+    R.P.spp_begin = shard->spp_begin + q * shard->spp_stride; R.P.spp_stride = shard->spp_stride * pl.npipes;
+    R.P.spp_count = (shard->spp_count - q + pl.npipes - 1) / pl.npipes;
+    R.P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) R.P.spp_count;
+    R.nslots = want;
+    const uint64_t need_slots = (R.P.total_work + MER_BLOCK - 1) / MER_BLOCK * MER_BLOCK;
+    if (need_slots < R.nslots) R.nslots = (uint32_t) need_slots;
+    uint32_t *slots = pp.slots.as<uint32_t>();
+    R.P.slots = slots; R.P.nslots = R.nslots; R.P.nslots_all = R.nslots * slot_mult; R.P.spawn = pl.spawn ? 1 : 0; R.P.live = pp.live.as<uint32_t>();
+    R.P.eq = pp.q[Pipe::EQ];
+    for (int k = 0; k < 2; k++) { R.P.mq[k] = pp.q[Pipe::MQ + k]; R.P.sq[k] = pp.q[Pipe::SQ + k]; R.P.cq[k] = pp.q[Pipe::CQ + k]; }
+    // parked solver states of K_connect (never together with spawned walks: a point emitter selects the EXTRA kernels)
+    if (pl.connect_stage && pp.cstate.reserve(ctx, (size_t) pp.nslots * MER_CSTATE_WORDS * sizeof(uint32_t))) return 1;
+    R.P.cstate = pp.cstate.as<uint32_t>();
+    if (pl.spawn && pp.side_state.reserve(ctx, (size_t) want * 8u)) return 1;           // busy bytes of the side-walk slots: 8 per path slot
+    R.P.side_state = pl.spawn ? pp.side_state.as<uint8_t>() : nullptr;
+    R.P.msort = 0; R.P.mq[0].keys = nullptr; R.P.mq[1].keys = nullptr;
+    if (pl.msort_bits) {              // spatial sort of the march list: a cell per list entry (written with the entry), the sorted list, histogram, cursors, count
+        if (pp.msort.reserve(ctx, ((size_t) pp.nslots + 2 * MER_SORT_MAXBINS + 16) * sizeof(uint32_t))) return 1;
+        for (int k = 0; k < 2; k++) {
+            DeviceBuffer &keys = pp.q_keys[Pipe::MQ + k];
+            if (keys.reserve(ctx, (size_t) R.P.mq[k].segcap * MER_NSEG * sizeof(uint16_t))) return 1;
+            R.P.mq[k].keys = keys.as<uint16_t>();
+        }
+        R.P.msort = std::min(pl.msort_bits, P.mq_sort ? 3 : 4); R.P.msort_major = (int) ctx->opt.march_sort_major;
+        R.P.msorted = pp.msort.as<uint32_t>();
+        R.P.msort_hist = R.P.msorted + pp.nslots; R.P.msort_cursor = R.P.msort_hist + MER_SORT_MAXBINS; R.P.msort_count = R.P.msort_cursor + MER_SORT_MAXBINS;
+        for (int k = 0; k < 3; k++) { R.P.msort_o[k] = P.rif.wmin[k]; const float e = P.rif.wmax[k] - P.rif.wmin[k]; R.P.msort_s[k] = e > 0 ? (float) (1 << R.P.msort) / e : 0.0f; }
+        HIP_CHECK(ctx, hipMemsetAsync(R.P.msort_hist, 0, (2 * MER_SORT_MAXBINS + 16) * sizeof(uint32_t), pp.stream));
+    }
+    R.P.hitq = pp.hitq.as<unsigned long long>(); R.P.hitq_cap = pp.hitq_cap; R.P.hitq_ctr = pp.hitq_ctr.as<unsigned long long>(); R.P.work_counter = R.P.hitq_ctr + 48;
+    R.P.ksteps = pl.ksteps0; R.P.cq_row = 0;
+    R.done = R.P.total_work == 0;
+    if (R.done) return 0;
+    R.blocks = R.nslots * slot_mult / MER_BLOCK;                 // the lists may hold every record
+    R.alive_bound = R.nslots; R.child_bound = R.nslots * (slot_mult - 1u);
+    R.gen_blocks = std::max(1u, std::min(R.nslots / MER_BLOCK, pl.gen_blocks_max));
+    HIP_CHECK(ctx, hipMemsetAsync(slots, 0, (size_t) R.nslots * MER_SLOT_WORDS * sizeof(uint32_t), pp.stream));
+    // side-walk records: only their state word must read "idle" (the region may hold stale records of a render with another slot count)
+    if (pl.spawn) hipLaunchKernelGGL(clear_side_flags_kernel, dim3(nblocks((int64_t) R.nslots * (slot_mult - 1u))), dim3(256), 0, pp.stream, slots, R.nslots, R.nslots * slot_mult);
+    if (pl.spawn) HIP_CHECK(ctx, hipMemsetAsync(pp.side_state.p, 0, (size_t) R.nslots * 8u, pp.stream));      // ... and K_event's copy of that state (the busy bytes)
+    HIP_CHECK(ctx, hipMemsetAsync(pp.live.p, 0, MER_LIVE_SLOTS * sizeof(uint32_t), pp.stream));
+    for (DeviceBuffer &counts : pp.q_counts)
+        HIP_CHECK(ctx, hipMemsetAsync(counts.p, 0, (size_t) MER_LIVE_SLOTS * MER_NSEG * sizeof(uint32_t), pp.stream));
+    HIP_CHECK(ctx, hipMemsetAsync(pp.hitq_ctr.p, 0, 64 * sizeof(unsigned long long), pp.stream));
+    return 0;
+}
+
+int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, float *film_dev, float *path_out_dev,
+                  uint64_t n_film, uint64_t n_path_out) {
+    Params P; bool point_outside = false;
+    if (make_params(ctx, scene, P, true, &point_outside)) return 1;
+    if (set_work(ctx, scene, shard, P)) return 1;
+    const Options &opt = ctx->opt;
+    P.seed = seed;
+    P.film = film_dev; P.path_out = path_out_dev; P.n_film = n_film; P.n_path_out = n_path_out;
+    HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (P.total_work == 0) return 0;
     // sorting the march lists by exit time scatters the lanes of a wave over the volume: a gain while the RIF sits near the caches
     // (256^3: +8 %, 512^3: +3 %), a loss once every fetch goes to HBM (1024^3: -4 %)
     P.mq_sort = opt.mq_sort >= 0 ? (opt.mq_sort != 0) : ((int64_t) P.rif.res[0] * P.rif.res[1] * P.rif.res[2] <= ((int64_t) 1 << 28) ? 1 : 0);
     P.gen_iters = 8; P.gen_all = opt.gen_all ? 1 : 0;
-    // K_connect runs one solver unit (one traced ray) per pending connection per launch: several launches per pass
-    const int connect_launches = (int) opt.connect_launches;
-    // K_gen: one launch = gen_blocks x 4 waves x 64 x gen_iters work ids
-    const unsigned gen_blocks_max = std::max(1u, std::min(want / MER_BLOCK, 1024u));
-    const unsigned long long ids_per_launch = (unsigned long long) gen_blocks_max * (MER_BLOCK / 64) * 64ull * (unsigned long long) P.gen_iters;
+    RenderPlan pl;
+    if (plan_render(ctx, scene, shard, P, point_outside, path_out_dev != nullptr, pl)) return 1;
+    const KernelSet &ks = pl.ks; const bool connect_stage = pl.connect_stage; const uint32_t slot_mult = pl.slot_mult;
+    const int npipes = pl.npipes, ksteps0 = pl.ksteps0, connect_launches = pl.connect_launches;
 
     Run runs[MER_MAX_PIPES];
     const auto t_start = std::chrono::steady_clock::now();
     HIP_CHECK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int q = 0; q < npipes; q++) {
-        Pipe &pp = ctx->pipes[q]; Run &R = runs[q];
-        if (q == 0) pp.stream = ctx->stream;
-        else if (!pp.own_stream) { HIP_CHECK(ctx, hipStreamCreateWithFlags(&pp.own_stream, hipStreamNonBlocking)); }
-        if (q > 0) { pp.stream = pp.own_stream; HIP_CHECK(ctx, hipStreamWaitEvent(pp.stream, ctx->ev0, 0)); }   // after what the caller queued (film zeroing ...)
-        // The hit ring holds what K_gen's throttle lets wait (cap / 2: a wave produces while at most that many ids are waiting) plus,
-        // in the worst case, every id of ONE launch (all its waves read the tail before any of them pushes, and every camera sample
-        // may hit the medium): capacity >= 2 x max(slots, ids per launch), or unread ids would be overwritten.
-        unsigned long long ring = 1; while (ring < 2ull * std::max<unsigned long long>(want, ids_per_launch)) ring <<= 1;
-        // event-queue segments: a segment of class c receives the lanes of the waves w = s (mod segments per class) of EVERY producer launch of
-        // the row -- K_march plus connect_launches K_connect launches, each of which re-packs its pending lanes into its first waves
-        auto eq_segcap = [&](uint32_t cap) { return std::min<uint64_t>((uint64_t) cap, (uint64_t) ((connect_stage ? connect_launches : 0) + 2) * (cap / (MER_NSEG / MER_EV_CLASSES))) + 256u; };
-        // pp.nslots counts RECORDS (path slots + side-walk slots); the lists hold record ids and are sized by it
-        if (pp.nslots < want * slot_mult || pp.hitq_cap < ring || (pp.nslots && pp.eq.segcap < eq_segcap(pp.nslots))) {                 // capacity: grows, never shrinks
-            const uint32_t cap = std::max(want * slot_mult, pp.nslots);
-            if (pp.slots) (void) hipFree(pp.slots);
-            if (pp.hitq) (void) hipFree(pp.hitq);
-            pp.slots = nullptr; pp.hitq = nullptr; pp.nslots = 0;
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.slots, (size_t) cap * MER_SLOT_WORDS * sizeof(uint32_t)));
-            for (SegQueue *sq : {&pp.eq, &pp.mq[0], &pp.mq[1], &pp.sq[0], &pp.sq[1], &pp.cq[0], &pp.cq[1]}) {
-                if (sq->items) (void) hipFree(sq->items);
-                if (sq->keys) (void) hipFree(sq->keys);
-                sq->items = nullptr; sq->keys = nullptr;
-                sq->segcap = 2u * (cap / MER_NSEG) + 256u;          // two producer kernels may feed one segment
-                if (sq == &pp.eq) sq->segcap = (uint32_t) eq_segcap(cap);                        // every lane may be of one event class
-                if (sq == &pp.mq[0] || sq == &pp.mq[1]) sq->segcap = 2u * (cap / (MER_NSEG / MER_MQ_CLASSES)) + 256u;   // ... or of one march class
-                if (sq == &pp.cq[0] || sq == &pp.cq[1]) sq->segcap = cap + 256u;   // every slot may be pending, in one class
-                HIP_CHECK(ctx, hipMalloc((void **) &sq->items, (size_t) sq->segcap * MER_NSEG * sizeof(uint32_t)));
-                if (!sq->counts) HIP_CHECK(ctx, hipMalloc((void **) &sq->counts, (size_t) MER_LIVE_SLOTS * MER_NSEG * sizeof(uint32_t)));
-                sq->chk = ctx->chk;
-            }
-            pp.hitq_cap = std::max(ring, pp.hitq_cap);
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.hitq, (size_t) pp.hitq_cap * sizeof(unsigned long long)));
-            pp.nslots = cap;
-        }
-        if (!pp.live) {
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.live, MER_LIVE_SLOTS * sizeof(uint32_t)));
-            HIP_CHECK(ctx, hipHostMalloc((void **) &pp.host_live, 8 * sizeof(uint32_t)));
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.hitq_ctr, 64 * sizeof(unsigned long long)));       // [0] tail, [32] head, [48] this pipeline's work counter
-            HIP_CHECK(ctx, hipEventCreateWithFlags(&pp.readback[0], hipEventDisableTiming));
-            HIP_CHECK(ctx, hipEventCreateWithFlags(&pp.readback[1], hipEventDisableTiming));
-            HIP_CHECK(ctx, hipEventCreateWithFlags(&pp.finished, hipEventDisableTiming));
-        }
-        // pipeline q's part of the shard: sample indices spp_begin + (q + k npipes) spp_stride
-        R.P = P;
-        R.P.spp_begin = shard->spp_begin + q * shard->spp_stride; R.P.spp_stride = shard->spp_stride * npipes;
-        R.P.spp_count = (shard->spp_count - q + npipes - 1) / npipes;
-        R.P.total_work = (uint64_t) P.ntiles_mine * MER_TILE * MER_TILE * (uint64_t) R.P.spp_count;
-        R.nslots = want;
-        const uint64_t need_slots = (R.P.total_work + MER_BLOCK - 1) / MER_BLOCK * MER_BLOCK;
-        if (need_slots < R.nslots) R.nslots = (uint32_t) need_slots;
-        R.P.slots = pp.slots; R.P.nslots = R.nslots; R.P.nslots_all = R.nslots * slot_mult; R.P.spawn = spawn ? 1 : 0; R.P.live = pp.live; R.P.eq = pp.eq; R.P.mq[0] = pp.mq[0]; R.P.mq[1] = pp.mq[1];
-        R.P.sq[0] = pp.sq[0]; R.P.sq[1] = pp.sq[1]; R.P.cq[0] = pp.cq[0]; R.P.cq[1] = pp.cq[1];
-        if (connect_stage && pp.cstate_slots < pp.nslots) {      // (never together with spawned walks: a point emitter selects the EXTRA kernels)
-            if (pp.cstate) (void) hipFree(pp.cstate);
-            pp.cstate = nullptr; pp.cstate_slots = 0;
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.cstate, (size_t) pp.nslots * MER_CSTATE_WORDS * sizeof(uint32_t)));
-            pp.cstate_slots = pp.nslots;
-        }
-        R.P.cstate = pp.cstate;
-        if (spawn && pp.side_state_slots < R.nslots) {           // busy bytes of the side-walk slots: 8 per path slot
-            if (pp.side_state) (void) hipFree(pp.side_state);
-            pp.side_state = nullptr; pp.side_state_slots = 0;
-            HIP_CHECK(ctx, hipMalloc((void **) &pp.side_state, (size_t) std::max(want, R.nslots) * 8u));
-            pp.side_state_slots = std::max(want, R.nslots);
-        }
-        R.P.side_state = spawn ? pp.side_state : nullptr;
-        R.P.msort = 0; R.P.mq[0].keys = nullptr; R.P.mq[1].keys = nullptr;
-        if (msort_bits) {              // spatial sort of the march list: a cell per list entry (written with the entry), the sorted list, histogram, cursors, count
-            if (pp.msort_cap < pp.nslots) {
-                if (pp.msort) (void) hipFree(pp.msort);
-                pp.msort = nullptr; pp.msort_cap = 0;
-                HIP_CHECK(ctx, hipMalloc((void **) &pp.msort, ((size_t) pp.nslots + 2 * MER_SORT_MAXBINS + 16) * sizeof(uint32_t)));
-                pp.msort_cap = pp.nslots;
-            }
-            for (int k = 0; k < 2; k++) {
-                if (!pp.mq[k].keys) HIP_CHECK(ctx, hipMalloc((void **) &pp.mq[k].keys, (size_t) pp.mq[k].segcap * MER_NSEG * sizeof(uint16_t)));
-                R.P.mq[k].keys = pp.mq[k].keys;
-            }
-            R.P.msort = std::min(msort_bits, P.mq_sort ? 3 : 4); R.P.msort_major = (int) opt.march_sort_major;
-            R.P.msorted = pp.msort;
-            R.P.msort_hist = pp.msort + pp.msort_cap; R.P.msort_cursor = R.P.msort_hist + MER_SORT_MAXBINS; R.P.msort_count = R.P.msort_cursor + MER_SORT_MAXBINS;
-            for (int k = 0; k < 3; k++) { R.P.msort_o[k] = P.rif.wmin[k]; const float e = P.rif.wmax[k] - P.rif.wmin[k]; R.P.msort_s[k] = e > 0 ? (float) (1 << R.P.msort) / e : 0.0f; }
-            HIP_CHECK(ctx, hipMemsetAsync(R.P.msort_hist, 0, (2 * MER_SORT_MAXBINS + 16) * sizeof(uint32_t), pp.stream));
-        }
-        R.P.hitq = pp.hitq; R.P.hitq_cap = pp.hitq_cap; R.P.hitq_ctr = pp.hitq_ctr; R.P.work_counter = pp.hitq_ctr + 48;
-        R.P.ksteps = ksteps0; R.P.cq_row = 0;
-        R.done = R.P.total_work == 0;
-        if (R.done) continue;
-        R.blocks = R.nslots * slot_mult / MER_BLOCK;                 // the lists may hold every record
-        R.alive_bound = R.nslots; R.child_bound = R.nslots * (slot_mult - 1u);
-        R.gen_blocks = std::max(1u, std::min(R.nslots / MER_BLOCK, gen_blocks_max));
-        HIP_CHECK(ctx, hipMemsetAsync(pp.slots, 0, (size_t) R.nslots * MER_SLOT_WORDS * sizeof(uint32_t), pp.stream));
-        // side-walk records: only their state word must read "idle" (the region may hold stale records of a render with another slot count)
-        if (spawn) hipLaunchKernelGGL(clear_side_flags_kernel, dim3(nblocks((int64_t) R.nslots * (slot_mult - 1u))), dim3(256), 0, pp.stream, pp.slots, R.nslots, R.nslots * slot_mult);
-        if (spawn) HIP_CHECK(ctx, hipMemsetAsync(pp.side_state, 0, (size_t) R.nslots * 8u, pp.stream));      // ... and K_event's copy of that state (the busy bytes)
-        HIP_CHECK(ctx, hipMemsetAsync(pp.live, 0, MER_LIVE_SLOTS * sizeof(uint32_t), pp.stream));
-        for (SegQueue *sq : {&pp.eq, &pp.mq[0], &pp.mq[1], &pp.sq[0], &pp.sq[1], &pp.cq[0], &pp.cq[1]})
-            HIP_CHECK(ctx, hipMemsetAsync(sq->counts, 0, (size_t) MER_LIVE_SLOTS * MER_NSEG * sizeof(uint32_t), pp.stream));
-        HIP_CHECK(ctx, hipMemsetAsync(pp.hitq_ctr, 0, 64 * sizeof(unsigned long long), pp.stream));
-    }
+    for (int q = 0; q < npipes; q++) if (prepare_pool(ctx, pl, P, shard, q, runs[q])) return 1;
 
     const uint32_t check_every = (uint32_t) opt.check_every;      // passes per batch (one read-back of the finished-slot count each)
     const bool pass_events = opt.pass_events != 0;          // per-kernel timing of every pass (mer_last_render_stats)
@@ -301,6 +319,7 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
     const bool side_walks_return = scene->sigma_mode == MER_SIGMA_GRID && scene->tr_estimator == MER_TR_WOODCOCK2;
     auto enqueue_batch = [&](int q, int rb) -> int {
         Pipe &pp = ctx->pipes[q]; Run &R = runs[q];
+        uint32_t *host_live = (uint32_t *) pp.host_live.p;
         unsigned march_blocks = R.blocks, event_blocks = R.blocks;
         if (opt.grid_fit) {
             const uint64_t records = std::min<uint64_t>((uint64_t) R.nslots * slot_mult, (uint64_t) R.alive_bound * slot_mult + R.child_bound);
@@ -331,8 +350,8 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
             R.pass++;
         }
         HIP_CHECK(ctx, hipGetLastError());
-        HIP_CHECK(ctx, hipMemcpyAsync(pp.host_live + 4 * rb, pp.live, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, pp.stream));     // finished path slots, side walks in flight
-        HIP_CHECK(ctx, hipMemcpyAsync(pp.host_live + 4 * rb + 2, R.P.work_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, pp.stream));
+        HIP_CHECK(ctx, hipMemcpyAsync(host_live + 4 * rb, pp.live.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, pp.stream));     // finished path slots, side walks in flight
+        HIP_CHECK(ctx, hipMemcpyAsync(host_live + 4 * rb + 2, R.P.work_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, pp.stream));
         HIP_CHECK(ctx, hipEventRecord(pp.readback[rb], pp.stream));
         return 0;
     };
@@ -349,17 +368,18 @@ int launch_render(mer_context *ctx, const mer_scene_desc *scene, const mer_shard
         bool any = false;
         for (int q = 0; q < npipes; q++) {
             Pipe &pp = ctx->pipes[q]; Run &R = runs[q];
+            const uint32_t *host_live = (uint32_t *) pp.host_live.p;
             if (R.done) continue;
             any = true;
             const int rb = R.cur; R.cur ^= 1;
             if (hipEventSynchronize(pp.readback[rb]) != hipSuccess) { ctx->error = "hipEventSynchronize(readback) failed"; return abort_render(); }
-            const uint32_t finished_slots = pp.host_live[4 * rb];
+            const uint32_t finished_slots = host_live[4 * rb];
             if (opt.verbose >= 2)        // drain timeline: host time, pipeline, passes issued, slots finished, work ids handed out
                 fprintf(stderr, "[mer] t=%8.3f ms pipe %d passes %u finished %u / %u work %llu / %llu K=%d\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(),
-                        q, R.pass, finished_slots, R.nslots, *(unsigned long long *) (pp.host_live + 4 * rb + 2), (unsigned long long) R.P.total_work, R.P.ksteps);
-            if (finished_slots >= R.nslots && pp.host_live[4 * rb + 1] == 0u) { R.done = true; continue; }      // every path done and no side walk in flight
-            R.alive_bound = R.nslots - std::min(finished_slots, R.nslots); R.child_bound = pp.host_live[4 * rb + 1];
-            R.work_left = *(unsigned long long *) (pp.host_live + 4 * rb + 2) < R.P.total_work;
+                        q, R.pass, finished_slots, R.nslots, *(unsigned long long *) (host_live + 4 * rb + 2), (unsigned long long) R.P.total_work, R.P.ksteps);
+            if (finished_slots >= R.nslots && host_live[4 * rb + 1] == 0u) { R.done = true; continue; }      // every path done and no side walk in flight
+            R.alive_bound = R.nslots - std::min(finished_slots, R.nslots); R.child_bound = host_live[4 * rb + 1];
+            R.work_left = *(unsigned long long *) (host_live + 4 * rb + 2) < R.P.total_work;
             // Pass length in the tail.  The tail of a render is the serial latency of its deepest paths, and a path advances by ONE walk (free
             // flight, NEE or look-up: ~65 steps) per pass however long the pass may be, so a pass should end when most lanes have parked.
             // Rounds 1-2 LENGTHENED the passes as lanes ran out (fewer launches); with K x 32 every pass lasts as long as the longest walk in

@@ -15,10 +15,10 @@ static int launch_exitance(mer_context *ctx, const mer_scene_desc *scene, const 
     if (open_light_paths(ctx, scene, shard, E, P, "mer_render_exitance: the scene's integrator must be ptracer (the map is recorded from light paths)",
                          "mer_render_exitance: the scene's boundary differs from the map's (a cube map has 6 faces, a sphere map 1)")) return 1;
     ExitanceMap M;
-    M.sums = E.dev; M.totals = E.totals(); M.chk = ctx->chk;
+    M.sums = E.sums(); M.totals = E.totals(); M.chk = ctx->chk;
     M.res_u = E.det.res[0]; M.res_v = E.det.res[1]; M.faces = E.faces(); M.frames = E.frames;
     M.t_min = E.det.t_min; M.t_bin = E.det.t_bin; M.cos_min = E.det.cos_min;
-    return launch_light_paths(ctx, scene, P, shard, seed, nullptr, 0, pick_light_kernel<ExitanceFamily>(scene), M);
+    return launch_light_paths(ctx, scene, P, seed, nullptr, 0, pick_light_kernel<ExitanceFamily>(scene), M);
 }
 
 }  // namespace mer

@@ -53,7 +53,7 @@ static int launch_fluence(mer_context *ctx, const mer_scene_desc *scene, const m
             return fail(ctx, at + "strategy balance with a channel-dependent sigma_t samples a mixture of exponentials");
     }
     const FluenceKernel kernel = F.track() ? pick_fluence_track(scene) : F.timed() ? pick_light_kernel<FluenceFamily<true>>(scene) : pick_light_kernel<FluenceFamily<false>>(scene);
-    return launch_light_paths(ctx, scene, P, shard, seed, nullptr, 0, kernel, fluence_grid<FluenceGrid>(ctx, F));
+    return launch_light_paths(ctx, scene, P, seed, nullptr, 0, kernel, fluence_grid<FluenceGrid>(ctx, F));
 }
 
 }  // namespace mer

@@ -14,8 +14,8 @@ int launch_ptracer(mer_context *ctx, const mer_scene_desc *scene, const mer_shar
     Params P;
     if (make_params(ctx, scene, P, false)) return 1;
     if (scene->integrator != MER_INTEGRATOR_PTRACER) return fail(ctx, "launch_ptracer: the scene's integrator is not ptracer");
-    if (check_light_paths(ctx, P, shard)) return 1;
-    return launch_light_paths(ctx, scene, P, shard, seed, film_dev, n_film, pick_light_kernel<PtracerFamily>(scene));
+    if (check_light_paths(ctx, scene, shard, P)) return 1;
+    return launch_light_paths(ctx, scene, P, seed, film_dev, n_film, pick_light_kernel<PtracerFamily>(scene));
 }
 
 // the kernels of the two leaf entry points (here, not in mer_ptracer.hpp: a second translation unit includes that header)
@@ -39,7 +39,7 @@ __global__ void sensor_position_kernel(const Params P, const float *dirs, int64_
 static int sensor_params(mer_context *ctx, const mer_scene_desc *scene, Params &P, const char *who) {
     if (!scene) return fail(ctx, std::string(who) + ": no scene");
     if (scene->sensor != MER_SENSOR_PERSPECTIVE) return fail(ctx, std::string(who) + ": the perspective sensor only");
-    mer_scene_desc sc = *scene; sc.sigma_mode = MER_SIGMA_HOMOGENEOUS; sc.rif_mode = MER_RIF_CONST; sc.albedo_mode = MER_ALBEDO_CONST;
+    mer_scene_desc sc = sensor_fields_only(*scene);
     // the light tracer's checks of the sensor (a rigid cam_to_world) apply whatever the scene's integrator is; its emitters are not read
     mer_emitter none{}; none.type = MER_EMITTER_POINT; none.sampling_weight = 1.0f;
     sc.integrator = MER_INTEGRATOR_PTRACER; sc.integrator_reserved = 0;
@@ -53,11 +53,6 @@ static int sensor_params(mer_context *ctx, const mer_scene_desc *scene, Params &
 
 using namespace mer;
 
-struct PtDevBuf {
-    void *p = nullptr;
-    ~PtDevBuf() { if (p) (void) hipFree(p); }
-};
-
 extern "C" {
 
 int mer_sensor_direct(mer_context *ctx, const mer_scene_desc *scene, const float *ref, int64_t n, float *out) {
@@ -67,14 +62,12 @@ int mer_sensor_direct(mer_context *ctx, const mer_scene_desc *scene, const float
     if (sensor_params(ctx, scene, P, "mer_sensor_direct")) return 1;
     if (n < 0 || (n > 0 && (!ref || !out))) return fail(ctx, "mer_sensor_direct: invalid arguments");
     if (n == 0) return 0;
-    PtDevBuf a, r;
-    HIP_CHECK(ctx, hipMalloc(&a.p, (size_t) n * 12)); HIP_CHECK(ctx, hipMalloc(&r.p, (size_t) n * 32));
+    DeviceBuffer a, r;
+    if (a.alloc(ctx, (size_t) n * 12) || r.alloc(ctx, (size_t) n * 32)) return 1;
     HIP_CHECK(ctx, hipMemcpyAsync(a.p, ref, (size_t) n * 12, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(sensor_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, (const float *) a.p, n, (float *) r.p);
+    hipLaunchKernelGGL(sensor_direct_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<const float>(), n, r.as<float>());
     HIP_CHECK(ctx, hipGetLastError());
-    HIP_CHECK(ctx, hipMemcpyAsync(out, r.p, (size_t) n * 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return r.download(ctx, out, (size_t) n * 32);
 }
 
 int mer_sensor_position(mer_context *ctx, const mer_scene_desc *scene, const float *dirs, int64_t n, float *out_uv, int32_t *out_ok) {
@@ -84,15 +77,13 @@ int mer_sensor_position(mer_context *ctx, const mer_scene_desc *scene, const flo
     if (sensor_params(ctx, scene, P, "mer_sensor_position")) return 1;
     if (n < 0 || (n > 0 && (!dirs || !out_uv || !out_ok))) return fail(ctx, "mer_sensor_position: invalid arguments");
     if (n == 0) return 0;
-    PtDevBuf a, r, k;
-    HIP_CHECK(ctx, hipMalloc(&a.p, (size_t) n * 12)); HIP_CHECK(ctx, hipMalloc(&r.p, (size_t) n * 8)); HIP_CHECK(ctx, hipMalloc(&k.p, (size_t) n * 4));
+    DeviceBuffer a, r, k;
+    if (a.alloc(ctx, (size_t) n * 12) || r.alloc(ctx, (size_t) n * 8) || k.alloc(ctx, (size_t) n * 4)) return 1;
     HIP_CHECK(ctx, hipMemcpyAsync(a.p, dirs, (size_t) n * 12, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(sensor_position_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, (const float *) a.p, n, (float *) r.p, (int32_t *) k.p);
+    hipLaunchKernelGGL(sensor_position_kernel, dim3(nblocks(n)), dim3(256), 0, ctx->stream, P, a.as<const float>(), n, r.as<float>(), k.as<int32_t>());
     HIP_CHECK(ctx, hipGetLastError());
     HIP_CHECK(ctx, hipMemcpyAsync(out_uv, r.p, (size_t) n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(ctx, hipMemcpyAsync(out_ok, k.p, (size_t) n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return k.download(ctx, out_ok, (size_t) n * 4);
 }
 
 }

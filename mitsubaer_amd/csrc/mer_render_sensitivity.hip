@@ -31,12 +31,11 @@ static int check_sensitivity_desc(mer_context *ctx, const mer_sensitivity_desc *
 static int detect_list(mer_context *ctx, uint32_t cap, DetectList &L) {
     if (ctx->detect_cap < cap) {
         HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->detect_list) (void) hipFree(ctx->detect_list);
-        ctx->detect_list = nullptr; ctx->detect_cap = 0;
-        HIP_CHECK(ctx, hipMalloc((void **) &ctx->detect_list, (DETECT_HEAD + (size_t) cap * 4) * sizeof(uint32_t)));
+        ctx->detect_cap = 0;
+        if (ctx->detect_list.reserve(ctx, (DETECT_HEAD + (size_t) cap * 4) * sizeof(uint32_t))) return 1;
         ctx->detect_cap = cap;
     }
-    L.count = ctx->detect_list;
+    L.count = ctx->detect_list.as<uint32_t>();
     L.cap = ctx->detect_cap; L.chk = ctx->chk;
     return 0;
 }
@@ -57,7 +56,7 @@ static int launch_sensitivity(mer_context *ctx, const mer_scene_desc *scene, con
     D.face = t.face; D.iu0 = t.iu0; D.iu1 = t.iu1; D.iv0 = t.iv0; D.iv1 = t.iv1;
     const FluenceGrid G = fluence_grid<FluenceGrid>(ctx, J);
     double *totals = J.totals();
-    return for_light_path_chunks(ctx, scene, P, shard, seed, nullptr, 0, [&](uint64_t first, uint32_t count) {
+    return for_light_path_chunks(ctx, scene, P, seed, nullptr, 0, [&](uint64_t first, uint32_t count) {
         if (count > L.cap) return fail(ctx, "mer_render_sensitivity: a launch chunk exceeds the detected-path list");
         // the count this chunk's second pass is sized by is read back after this chunk's first pass, into a variable that starts at 0
         uint32_t detected = 0;

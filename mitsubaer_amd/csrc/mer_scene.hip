@@ -26,14 +26,15 @@ double inverse3(const double M[3][3], double inv[3][3]) {
 // what the kernels fetch a volume's values from: the layout they see, the brick geometry, the bytes of that buffer (dense data, CELL8
 // cells or BRICK records) and the extent buffer loads use (0 = global loads: 4 GiB or more, or option buffer_loads = 0)
 struct RecordInfo { int layout, bshift, recw, nbx, nby; uint64_t bytes; uint32_t buf_bytes; };
-static RecordInfo record_info(const mer_context *ctx, const Volume &v) {
+static RecordInfo record_info(const mer_context *ctx, const Volume &v, bool records = true) {
     RecordInfo r;
-    r.layout = v.cell8 ? v.layout : MER_LAYOUT_DENSE;
-    const bool brick = v.cell8 && (v.layout == MER_LAYOUT_BRICK27 || v.layout == MER_LAYOUT_BRICK125);
+    records = records && v.cell8;
+    r.layout = records ? v.layout : MER_LAYOUT_DENSE;
+    const bool brick = records && (v.layout == MER_LAYOUT_BRICK27 || v.layout == MER_LAYOUT_BRICK125);
     r.bshift = v.layout == MER_LAYOUT_BRICK125 ? 2 : 1; r.recw = v.layout == MER_LAYOUT_BRICK125 ? 128 : 32;
     const int bc = 1 << r.bshift;                                       // ceil((res-1)/bc) bricks per axis
     r.nbx = (v.desc.res[0] - 2) / bc + 1; r.nby = (v.desc.res[1] - 2) / bc + 1;
-    r.bytes = !v.cell8 ? (uint64_t) v.bytes_dense
+    r.bytes = !records ? (uint64_t) v.bytes_dense
             : brick ? (uint64_t) r.nbx * r.nby * ((v.desc.res[2] - 2) / bc + 1) * (uint64_t) r.recw * 4ull
             : (uint64_t) (v.desc.res[0] - 1) * (v.desc.res[1] - 1) * (v.desc.res[2] - 1) * 32ull;
     r.buf_bytes = r.bytes < 0xFFFFFFFFull && ctx->opt.buffer_loads ? (uint32_t) r.bytes : 0u;
@@ -42,14 +43,15 @@ static RecordInfo record_info(const mer_context *ctx, const Volume &v) {
 
 // worldToGrid = scale((res-1)/extents) * translate(-min) * toWorld^-1 with toWorld = identity
 // (GridDataSource::configure, src/volume/gridvolume.cpp:188-195).  Float arithmetic as in the reference.
-void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g) {
+void fill_dgrid(const mer_context *ctx, const Volume &v, DGrid &g, bool records) {
     std::memset(&g, 0, sizeof(g));
-    g.data = v.dense; g.cell8 = v.cell8; g.coeff = v.coeff;
+    records = records && v.cell8;
+    g.data = v.dense.p; g.cell8 = records ? v.cell8.as<float>() : nullptr; g.coeff = v.coeff.as<float>();
     g.channels = v.desc.channels; g.dtype = v.desc.dtype;
-    const RecordInfo r = record_info(ctx, v);
+    const RecordInfo r = record_info(ctx, v, records);
     g.layout = r.layout; g.bshift = r.bshift; g.bw = (1 << g.bshift) + 1; g.recw = r.recw; g.nbx = r.nbx; g.nby = r.nby;
     g.buf_bytes = r.buf_bytes;
-    g.n_record = v.cell8 ? r.bytes / 4 : 0;
+    g.n_record = records ? r.bytes / 4 : 0;
     g.n_dense = (uint64_t) v.desc.res[0] * v.desc.res[1] * v.desc.res[2] * (uint64_t) v.desc.channels;
     g.chk = ctx->chk;
     // worldToVolume: the desc's matrix, all zeros = identity
@@ -387,7 +389,7 @@ static const char *envmap_derive(mer_context *ctx, const mer_emitter &e, DEnvMap
         }
     if (!(inverse3(M, inv) > 0)) return "envmap emitter: the linear part of 'toWorld' must be a rotation (within 1e-5)";
     const EnvMap &m = it->second;
-    const unsigned char *b = (const unsigned char *) m.dev;
+    const unsigned char *b = m.dev.as<const unsigned char>();
     E = DEnvMap{};
     E.texels = (const uint2 *) b; E.cdf_cols = (const float *) (b + m.off_cols); E.cdf_rows = (const float *) (b + m.off_rows);
     E.row_weights = (const float *) (b + m.off_weights);
@@ -577,8 +579,7 @@ static int albedo_grid(mer_context *ctx, const mer_scene_desc &sc, Params &P) {
         auto it = ctx->volumes.find(sc.albedo_grid);
         if (it == ctx->volumes.end()) return fail(ctx, "No albedo specified!");                                     // heterogeneous.cpp:231-232
         if (it->second.desc.channels != 3) return fail(ctx, "albedo volume must support spectrum lookups");
-        Volume tmp = it->second; tmp.cell8 = nullptr;
-        fill_dgrid(ctx, tmp, P.albedo);
+        fill_dgrid(ctx, it->second, P.albedo, false);
     }
     return 0;
 }
@@ -709,12 +710,12 @@ static int reconstruction_filter(mer_context *ctx, const mer_scene_desc &sc, Par
     // the table goes to device memory once per (kind, parameter); no kernel of this context is in flight here (renders and leaf calls return synchronised)
     float fv[33];
     filter_table(sc.rfilter, sc.rfilter_param, fv, P.fradius, P.fscale);
-    if (!ctx->ftable) HIP_CHECK(ctx, hipMalloc((void **) &ctx->ftable, sizeof(fv)));
+    if (ctx->ftable.reserve(ctx, sizeof(fv))) return 1;
     if (ctx->ftable_kind != sc.rfilter || ctx->ftable_param != sc.rfilter_param) {
-        HIP_CHECK(ctx, hipMemcpy(ctx->ftable, fv, sizeof(fv), hipMemcpyHostToDevice));
+        HIP_CHECK(ctx, hipMemcpy(ctx->ftable.p, fv, sizeof(fv), hipMemcpyHostToDevice));
         ctx->ftable_kind = sc.rfilter; ctx->ftable_param = sc.rfilter_param;
     }
-    P.ftable = ctx->ftable;
+    P.ftable = ctx->ftable.as<float>();
     if (P.fradius > 7.0f) return fail(ctx, "reconstruction filter radius too large");
     return 0;
 }
@@ -785,21 +786,22 @@ static int constant_environment(mer_context *ctx, const mer_scene_desc &sc, Para
 // The emitter table goes to device memory when it changes; no kernel of this context is in flight here (renders and leaf calls return
 // synchronised).
 static int emitter_upload(mer_context *ctx, const mer_scene_desc &sc, Params &P, const Emitters &em) {
-    if (!ctx->etab) HIP_CHECK(ctx, hipMalloc((void **) &ctx->etab, sizeof(EmitterTable)));
+    if (ctx->etab.reserve(ctx, sizeof(EmitterTable))) return 1;
     if (!ctx->etab_valid || std::memcmp(&ctx->etab_host, &em.tab, sizeof(EmitterTable)) != 0) {
-        HIP_CHECK(ctx, hipMemcpy(ctx->etab, &em.tab, sizeof(EmitterTable), hipMemcpyHostToDevice));
+        HIP_CHECK(ctx, hipMemcpy(ctx->etab.p, &em.tab, sizeof(EmitterTable), hipMemcpyHostToDevice));
         ctx->etab_host = em.tab; ctx->etab_valid = true;
     }
     P.n_point = em.n_point; P.n_rect = em.n_rect;
-    P.points = ctx->etab->points; P.rects = ctx->etab->rects;
+    EmitterTable *etab = ctx->etab.as<EmitterTable>();
+    P.points = etab->points; P.rects = etab->rects;
     P.has_spot = em.any_spot ? 1 : 0;              // the kernels find the cones (spot_table)
     P.has_envmap = em.has_env ? 1 : 0;             // and the envmap's record (envmap_rec) behind the rectangles: EmitterTable
     return 0;
 }
 
 static int context_pointers(mer_context *ctx, const mer_scene_desc &sc, Params &P) {
-    P.counters = ctx->counters;
-    P.work_counter = ctx->counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
+    P.counters = ctx->counters.as<unsigned long long>();
+    P.work_counter = P.counters + MER_C_COUNT * MER_COUNTER_REPLICAS;
     P.chk = ctx->chk;
     P.dbg_pixel = (int32_t) ctx->opt.debug_pixel;
     return 0;

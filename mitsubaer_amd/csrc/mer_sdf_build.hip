@@ -77,7 +77,7 @@ __global__ __launch_bounds__(MER_SDF_BLOCK) void sdf_finish_kernel(SdfGridArgs g
     ws[at] = w;
 }
 
-int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host, int64_t n_tri, int32_t max_tri_per_launch, float **sdf_dev, float **w_dev) {
+int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host, int64_t n_tri, int32_t max_tri_per_launch, DeviceBuffer &sdf, DeviceBuffer &winding) {
     SdfGridArgs g;
     g.n_nodes = (uint64_t) d->res[0] * (uint64_t) d->res[1] * (uint64_t) d->res[2];
     for (int a = 0; a < 3; a++) {
@@ -86,31 +86,23 @@ int sdf_build(mer_context *ctx, const mer_grid_desc *d, const float *tri12_host,
     }
     g.chk = ctx->chk;
     const uint32_t chunk = max_tri_per_launch > 0 ? (uint32_t) max_tri_per_launch : (uint32_t) MER_SDF_DEFAULT_CHUNK;
-    float4 *tri = nullptr; float *d2s = nullptr, *ws = nullptr;
-    auto release = [&]() { if (tri) (void) hipFree(tri); if (d2s) (void) hipFree(d2s); if (ws) (void) hipFree(ws); };
-    auto run = [&]() -> int {
-        HIP_CHECK(ctx, hipMalloc((void **) &tri, (size_t) n_tri * 48));
-        HIP_CHECK(ctx, hipMalloc((void **) &d2s, g.n_nodes * 4));
-        HIP_CHECK(ctx, hipMalloc((void **) &ws, g.n_nodes * 4));
-        HIP_CHECK(ctx, hipMemcpyAsync(tri, tri12_host, (size_t) n_tri * 48, hipMemcpyHostToDevice, ctx->stream));
-        // triangle chunks outermost: a node range meets its chunks in index order
-        for (uint32_t t0 = 0; t0 < (uint32_t) n_tri; t0 += chunk) {
-            const uint32_t t1 = (uint32_t) std::min<int64_t>(n_tri, (int64_t) t0 + chunk);
-            for (uint64_t n0 = 0; n0 < g.n_nodes; n0 += MER_SDF_NODES_PER_LAUNCH) {
-                const uint64_t n1 = std::min<uint64_t>(g.n_nodes, n0 + MER_SDF_NODES_PER_LAUNCH);
-                const dim3 grid(nblocks((int64_t) (n1 - n0), MER_SDF_BLOCK));
-                hipLaunchKernelGGL(sdf_accum_kernel, grid, dim3(MER_SDF_BLOCK), 0, ctx->stream, g, (const float4 *) tri, (uint32_t) n_tri, t0, t1, n0, n1, d2s, ws);
-                HIP_CHECK(ctx, hipGetLastError());
-            }
+    DeviceBuffer tri;
+    if (tri.alloc(ctx, (size_t) n_tri * 48) || sdf.alloc(ctx, g.n_nodes * 4) || winding.alloc(ctx, g.n_nodes * 4)) return 1;
+    float *d2s = sdf.as<float>(), *ws = winding.as<float>();
+    HIP_CHECK(ctx, hipMemcpyAsync(tri.p, tri12_host, (size_t) n_tri * 48, hipMemcpyHostToDevice, ctx->stream));
+    // triangle chunks outermost: a node range meets its chunks in index order
+    for (uint32_t t0 = 0; t0 < (uint32_t) n_tri; t0 += chunk) {
+        const uint32_t t1 = (uint32_t) std::min<int64_t>(n_tri, (int64_t) t0 + chunk);
+        for (uint64_t n0 = 0; n0 < g.n_nodes; n0 += MER_SDF_NODES_PER_LAUNCH) {
+            const uint64_t n1 = std::min<uint64_t>(g.n_nodes, n0 + MER_SDF_NODES_PER_LAUNCH);
+            const dim3 grid(nblocks((int64_t) (n1 - n0), MER_SDF_BLOCK));
+            hipLaunchKernelGGL(sdf_accum_kernel, grid, dim3(MER_SDF_BLOCK), 0, ctx->stream, g, tri.as<const float4>(), (uint32_t) n_tri, t0, t1, n0, n1, d2s, ws);
+            HIP_CHECK(ctx, hipGetLastError());
         }
-        hipLaunchKernelGGL(sdf_finish_kernel, dim3(nblocks((int64_t) g.n_nodes, MER_SDF_BLOCK)), dim3(MER_SDF_BLOCK), 0, ctx->stream, g, d2s, ws);
-        HIP_CHECK(ctx, hipGetLastError());
-        HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        return 0;
-    };
-    if (run()) { release(); return 1; }
-    (void) hipFree(tri);
-    *sdf_dev = d2s; *w_dev = ws;
+    }
+    hipLaunchKernelGGL(sdf_finish_kernel, dim3(nblocks((int64_t) g.n_nodes, MER_SDF_BLOCK)), dim3(MER_SDF_BLOCK), 0, ctx->stream, g, d2s, ws);
+    HIP_CHECK(ctx, hipGetLastError());
+    HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));          // before `tri` goes
     return 0;
 }
 
