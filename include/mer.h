@@ -281,6 +281,15 @@ typedef struct { int32_t boundary, res[2], face, iu0, iu1, iv0, iv1; float cos_m
 /* a sensitivity grid (mer_sensitivity_create): the voxel grid of a fluence grid (res, bmin, bmax: half-open cells) and the detector */
 typedef int32_t mer_sensitivity;                              /* handle, > 0, from the context's handle counter */
 typedef struct { int32_t res[3]; float bmin[3], bmax[3]; mer_detector_desc det; } mer_sensitivity_desc;
+/* an array of detectors and gates over one window (mer_sensitivity_array_create) */
+typedef struct {
+    int32_t res[3]; float bmin[3], bmax[3];
+    mer_detector_desc det;     /* raster, face, window, cone, t_min, t_bin: as for mer_sensitivity_create */
+    int32_t bin_u, bin_v;      /* one detector = bin_u x bin_v raster cells of the window */
+    int32_t gates;             /* >= 1; gate g takes floorf((l - t_min) / t_bin) == g */
+    int32_t scatter;           /* 0 | 1: also record the scattering grid K */
+    int32_t reserved[2];       /* 0 */
+} mer_sensitivity_array_desc;
 
 enum {
     MER_C_PATHS = 0, MER_C_STEPS, MER_C_RIF_EVALS, MER_C_TENTATIVE, MER_C_REAL,
@@ -601,9 +610,40 @@ int  mer_exitance_read(mer_context *ctx, mer_exitance e, double *sums /* [frames
         chunk of the light tracer's launches it reads the number of detected paths back and launches the second pass over exactly that
         many (none when it is 0); the list of one chunk's paths lives in the context and is freed with it.  mer_sensitivity_read: sums
         may be NULL (totals only).  mer_context_destroy frees the grids alive.
-        Not built: several detectors per call, sensitivities to scattering or to the index field, time-resolved Jacobians beyond the one
-        gate, several GPUs in one call. ---- */
+        Detector arrays, gates and the scattering grid (mer_sensitivity_array_create).  A time-domain measurement is one source, a raster
+        of detectors and a row of gates; a path leaves through one raster cell at one path length, so it belongs to at most one
+        measurement and the two passes fill every grid at once.  One detector is bin_u x bin_v raster cells of the window: ndu =
+        (iu1 - iu0) / bin_u, ndv = (iv1 - iv0) / bin_v; gate g takes the exits with floorf((l - t_min) / t_bin) == g, 0 <= g < gates
+        (gates == 1 and t_bin == 0: no gate); cone, gate expression and raster cell are those above.  An exit in raster cell (iu, iv)
+        and gate g is measurement m = (g * ndv + (iv - iv0) / bin_v) * ndu + (iu - iu0) / bin_u of M = gates * ndv * ndu.  The handle is a
+        mer_sensitivity: mer_render_sensitivity, _clear and _destroy take it as they are; mer_sensitivity_create(desc) means bin = the
+        whole window, gates = 1, scatter = 0.
+            J[m]  the absorption grid of measurement m, as above, over the paths of m (key m * n_cells + cell).
+            K[m]  scatter = 1: the scattering grid (key (M + m) * n_cells + cell): every real collision a detected path scatters from
+                  deposits the path's weight at the detector, w, into the cell that holds the collision point (mer_render_fluence's
+                  cell): K_c = sum over the detected paths of w * N_c, N_c = the path's scattering collisions in cell c.
+        In all (1 + scatter) * M * n_cells <= 2^27 keys.
+        mer_sensitivity_read_array: sums double[1 + scatter][gates][ndv][ndu][nz][ny][nx][3] (or NULL), meas double[gates][ndv][ndu][8]
+        (or NULL) and the totals.  meas[m]: [0..2] the detected weight of m, [3] its detected paths (first pass); [4..6] the sum over
+        its paths of w * the path's number of scattering collisions, counted before any box test (second pass; 0 when scatter = 0);
+        [7] 0.  totals[0..12] keep their meaning, summed over all measurements; totals[13..15]: scatter = 1: w per collision outside
+        the box, so that sum(K) + totals[13..15] = sum over m of meas[m][4..6] per channel; 0 otherwise.  mer_sensitivity_shape: gates,
+        ndv, ndu, scatter.  Both take handles made either way; mer_sensitivity_read refuses, by name, a handle with M > 1 or scatter = 1.
+        Interpretation of K.  In a medium with homogeneous sigma_s, per channel and for every distance-sampling strategy, with S_m the
+        detected signal of measurement m per emitted path: dS_m / d sigma_s = (sum(K[m]) / sigma_s - sum(J[m])) / paths, and per cell
+        dS_m / d sigma_s(c) = (K_c / sigma_s - J_c) / paths.  The reason: a path's contribution carries one factor sigma_s per
+        scattering vertex and exp(-sigma_s L) along its length, and the sampling density is held fixed.  With a gridded sigma_t or
+        albedo K is delivered raw (w per collision) and its interpretation is left to the caller.
+        mer_sensitivity_array_create refuses, each with its own message under its own prefix and *out = 0: everything
+        mer_sensitivity_create refuses, in the same words; bin_u or bin_v < 1 or not dividing the window; gates < 1; gates > 1 with
+        t_bin == 0; scatter other than 0 or 1; reserved != 0; more than 2^27 keys.
+        Not built: sensitivities to the index field, several GPUs in one call. ---- */
 int  mer_sensitivity_create(mer_context *ctx, const mer_sensitivity_desc *desc, mer_sensitivity *out);
+int  mer_sensitivity_array_create(mer_context *ctx, const mer_sensitivity_array_desc *desc, mer_sensitivity *out);
+int  mer_sensitivity_shape(mer_context *ctx, mer_sensitivity s, int32_t shape[4] /* gates, ndv, ndu, scatter */);
+int  mer_sensitivity_read_array(mer_context *ctx, mer_sensitivity s,
+                                double *sums /* [1 + scatter][gates][ndv][ndu][nz][ny][nx][3] or NULL */,
+                                double *meas /* [gates][ndv][ndu][8] or NULL */, double totals[16]);
 int  mer_sensitivity_clear(mer_context *ctx, mer_sensitivity s);
 int  mer_sensitivity_destroy(mer_context *ctx, mer_sensitivity s);
 int  mer_render_sensitivity(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_sensitivity s);

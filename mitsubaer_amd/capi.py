@@ -32,6 +32,7 @@ SYMBOLS = [
     "mer_fluence_time_create", "mer_fluence_time_read", "mer_fluence_track_create",
     "mer_exitance_create", "mer_exitance_clear", "mer_exitance_destroy", "mer_render_exitance", "mer_exitance_read",
     "mer_sensitivity_create", "mer_sensitivity_clear", "mer_sensitivity_destroy", "mer_render_sensitivity", "mer_sensitivity_read",
+    "mer_sensitivity_array_create", "mer_sensitivity_shape", "mer_sensitivity_read_array",
 ]
 SHARD_SAMPLES, SHARD_TILES = 0, 1
 REDUCE_NONE, REDUCE_RCCL, REDUCE_PEER_COPY = 0, 1, 2
@@ -523,7 +524,10 @@ def sensitivity_desc(res, bmin, bmax, detector):
 
 def validate_sensitivity(desc):
     """The refusals of mer_sensitivity_create, with its messages: MerError.  No GPU needed."""
-    at = "mer_sensitivity_create: "
+    _validate_sensitivity(desc, "mer_sensitivity_create: ")
+
+
+def _validate_sensitivity(desc, at):
     _validate_box(desc, at)
     t = desc.det
     _validate_raster(t, at, "detector res", 1)
@@ -533,6 +537,57 @@ def validate_sensitivity(desc):
         raise MerError(at + "the window must lie inside the raster (0 <= iu0, iu1 <= res[0], 0 <= iv0, iv1 <= res[1])")
     if not (t.iu0 < t.iu1 and t.iv0 < t.iv1):
         raise MerError(at + "the window is empty (iu0 < iu1 and iv0 < iv1 are required)")
+
+
+class SensitivityArrayDesc(C.Structure):
+    """mer_sensitivity_array_desc: the box and the detector of a SensitivityDesc; one detector is bin_u x bin_v raster cells of the window,
+    gate g the exits with floorf((l - t_min) / t_bin) == g for 0 <= g < gates; scatter = 1 also records the scattering grids K"""
+    _fields_ = [("res", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("det", DetectorDesc),
+                ("bin_u", C.c_int32), ("bin_v", C.c_int32), ("gates", C.c_int32), ("scatter", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# mer_sensitivity_read_array's totals: SENSITIVITY_TOTALS, then [13..15]; its meas[m]: [0..2], [3], [4..6], [7]
+SENSITIVITY_ARRAY_TOTALS = SENSITIVITY_TOTALS + ("collisions_dropped",)
+SENSITIVITY_MEAS = ("detected_weight", "detected", "weight_collisions")
+
+
+def sensitivity_array_desc(res, bmin, bmax, detector, bins, gates=1, scatter=False):
+    """bins = (bin_u, bin_v); None: one detector, the whole window"""
+    d = SensitivityArrayDesc()
+    d.res[:] = [int(v) for v in res]
+    d.bmin[:] = [float(v) for v in bmin]
+    d.bmax[:] = [float(v) for v in bmax]
+    C.memmove(C.byref(d.det), C.byref(detector), C.sizeof(DetectorDesc))
+    d.bin_u, d.bin_v = [int(v) for v in (bins if bins is not None else (d.det.iu1 - d.det.iu0, d.det.iv1 - d.det.iv0))]
+    d.gates, d.scatter = int(gates), int(scatter)
+    d.reserved[:] = [0, 0]
+    return d
+
+
+def sensitivity_array_shape(d):
+    """(1 + scatter, gates, ndv, ndu) of a valid SensitivityArrayDesc"""
+    return (1 + d.scatter, d.gates, (d.det.iv1 - d.det.iv0) // d.bin_v, (d.det.iu1 - d.det.iu0) // d.bin_u)
+
+
+def validate_sensitivity_array(desc):
+    """The refusals of mer_sensitivity_array_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_sensitivity_array_create: "
+    _validate_sensitivity(desc, at)
+    t = desc.det
+    if desc.bin_u < 1 or desc.bin_v < 1:
+        raise MerError(at + "bin_u and bin_v must be at least 1")
+    if (t.iu1 - t.iu0) % desc.bin_u or (t.iv1 - t.iv0) % desc.bin_v:
+        raise MerError(at + "bin_u and bin_v must divide the window (iu1 - iu0 and iv1 - iv0)")
+    if desc.gates < 1:
+        raise MerError(at + "gates must be at least 1")
+    if desc.gates > 1 and t.t_bin == 0:
+        raise MerError(at + "several gates need t_bin > 0")
+    if desc.scatter not in (0, 1):
+        raise MerError(at + "scatter must be 0 or 1")
+    if desc.reserved[0] != 0 or desc.reserved[1] != 0:
+        raise MerError(at + "reserved must be 0")
+    if int(np.prod(sensitivity_array_shape(desc), dtype=np.int64)) * desc.res[0] * desc.res[1] * desc.res[2] > 1 << 27:
+        raise MerError(at + "more than 2^27 cells x measurements x (1 + scatter)")
 
 
 def _box_shape(d):
@@ -554,6 +609,9 @@ _RECORDERS = {
     "exitance": _Recorder("exitance", "mer_exitance_create", exitance_desc, validate_exitance, "mer_exitance_read", 16,
                           lambda d: (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0]), None),
     "sensitivity": _Recorder("sensitivity", "mer_sensitivity_create", sensitivity_desc, validate_sensitivity, "mer_sensitivity_read", 16, _box_shape, None),
+    # read through Context.sensitivity_read_array (which takes the handles of both rows) and, with one measurement and no K, Context.sensitivity_read
+    "sensitivity_array": _Recorder("sensitivity", "mer_sensitivity_array_create", sensitivity_array_desc, validate_sensitivity_array, "mer_sensitivity_read_array", 16,
+                                   lambda d: sensitivity_array_shape(d) + _box_shape(d), None),
 }
 
 
@@ -1059,7 +1117,65 @@ class Context:
 
     def sensitivity_read(self, handle, sums=True):
         """-> (raw sums float64 [nz][ny][nx][3], or None with sums = False; totals float64 [16]: capi.SENSITIVITY_TOTALS)"""
-        return self._recorder_read("sensitivity", handle, sums)
+        mine, shape = self._recorders.get(handle, (None, None))
+        if mine != "sensitivity_array":
+            return self._recorder_read("sensitivity", handle, sums)
+        # a handle of sensitivity_array_create: the library takes it with one measurement and no K, and refuses it by name otherwise
+        totals = np.zeros(16, np.float64)
+        single = shape[:4] == (1, 1, 1, 1)
+        out = np.zeros(shape[4:] + (3,), np.float64) if sums and single else None
+        self._check(self.lib.mer_sensitivity_read(self.h, C.c_int32(handle), _fp(out) if out is not None else None, _fp(totals)))
+        return out, totals
+
+    # ---- detector arrays, gates and the scattering grid (mer_sensitivity_array_create) ----------
+    def sensitivity_array_create(self, res, bmin, bmax, detector, bins=None, gates=1, scatter=False):
+        """-> handle of the zeroed grids of an array of detectors: one detector is bins = (bin_u, bin_v) raster cells of the detector's window
+        (None: all of it), gate g takes the exits with floor((l - t_min) / t_bin) == g for 0 <= g < gates; scatter: the scattering grids K too.
+        sensitivity_clear, sensitivity_destroy and render_sensitivity take it like a sensitivity_create handle."""
+        return self._recorder_create("sensitivity_array", res, bmin, bmax, detector, bins, gates, scatter)
+
+    def sensitivity_shape(self, handle):
+        """-> (gates, ndv, ndu, scatter) of a handle of sensitivity_create or sensitivity_array_create"""
+        shape = (C.c_int32 * 4)()
+        self._check(self.lib.mer_sensitivity_shape(self.h, C.c_int32(handle), shape))
+        return tuple(int(v) for v in shape)
+
+    def sensitivity_read_array(self, handle, sums=True):
+        """-> (raw sums float64 [1 + scatter][gates][ndv][ndu][nz][ny][nx][3], or None with sums = False; meas float64 [gates][ndv][ndu][8]:
+        detected weight x 3, detected paths, w x scattering collisions x 3, 0; totals float64 [16]: capi.SENSITIVITY_ARRAY_TOTALS)"""
+        mine, shape = self._recorders.get(handle, (None, None))
+        if mine not in ("sensitivity", "sensitivity_array"):
+            raise MerError("mer_sensitivity_read_array: unknown sensitivity handle")
+        if mine == "sensitivity":
+            shape = (1, 1, 1, 1) + shape
+        out = np.zeros(shape + (3,), np.float64) if sums else None
+        meas = np.zeros(shape[1:4] + (8,), np.float64)
+        totals = np.zeros(16, np.float64)
+        self._check(self.lib.mer_sensitivity_read_array(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(meas), _fp(totals)))
+        return out, meas, totals
+
+    def sensitivity_array(self, scene, res, detector, bins, gates, spp_count, scatter=False, seed=0, bmin=None, bmax=None, spp_begin=0):
+        """The sensitivity maps of an array of detectors and gates in one render (integrator = ptracer): (J / paths float64
+        [gates][ndv][ndu][nz][ny][nx][3], K / paths of the same shape or None without scatter, meas float64 [gates][ndv][ndu][8], info).
+        detector: capi.detector_desc or a dict of its arguments without the boundary; its (t_min, t_bin) is gate 0.  In a medium with
+        homogeneous sigma_s the derivative of the detected signal of measurement m by sigma_s is sum(K[m]) / sigma_s - sum(J[m]) per
+        channel (per cell: K_c / sigma_s - J_c); with a gridded sigma_t or albedo K is raw: w per scattering collision.  info: the totals
+        by name (as Context.sensitivity, plus collisions_dropped [3]), the raw sums [1 + scatter][...] and the box."""
+        if isinstance(detector, dict):
+            detector = detector_desc(scene.boundary, **detector)
+        bmin, bmax = self._fluence_box(scene, bmin, bmax)
+        h = self.sensitivity_array_create(res, bmin, bmax, detector, bins, gates, scatter)
+        try:
+            self.render_sensitivity(scene, h, spp_begin, spp_count, seed)
+            sums, meas, t = self.sensitivity_read_array(h)
+        finally:
+            self.sensitivity_destroy(h)
+        d = fluence_desc(res, bmin, bmax)
+        info = {"paths": t[0], "detected_weight": t[1:4].copy(), "dropped": t[4:7].copy(), "ended": t[7], "detected": t[8],
+                "weight_length": t[9:12].copy(), "disagreements": t[12], "collisions_dropped": t[13:16].copy(), "sums": sums, "totals": t,
+                "bmin": np.array(d.bmin[:], np.float64), "bmax": np.array(d.bmax[:], np.float64)}
+        scaled = sums / t[0] if t[0] > 0 else np.zeros_like(sums)
+        return scaled[0], (scaled[1] if scatter else None), meas, info
 
     def sensitivity(self, scene, res, detector, spp_count, seed=0, bmin=None, bmax=None, spp_begin=0):
         """One sensitivity map of the scene (integrator = ptracer) for a detector on the boundary of its medium shape (capi.detector_desc,

@@ -66,7 +66,8 @@ struct EnvMap {
 // the family decides which entry points know a handle (the other two families refuse it as unknown), the kind which kernel a fluence handle renders with.
 //   fluence      sums [frames][nz][ny][nx][3] over `box`, 8 totals; timed: frames > 0 bins of det.t_bin from det.t_min on, 12 totals; track: K_fluence_track
 //   exitance     sums [frames][faces][res_v][res_u][3], 16 totals: det holds the boundary, raster, window and cone
-//   sensitivity  sums [nz][ny][nx][3] over `box`, 16 totals: det is the detector
+//   sensitivity  sums [1 + scatter][gates][ndv][ndu][nz][ny][nx][3] over `box`, 16 totals, then n_meas = gates x ndv x ndu measurements of 8 float64:
+//                det is the raster, window, cone and first gate; one detector is bin_u x bin_v cells of the window (mer_sensitivity_create: all of it)
 enum { REC_FLUENCE = 0, REC_EXITANCE = 1, REC_SENSITIVITY = 2 };      // Recorder::family
 enum { REC_COLLISION = 0, REC_TRACK = 1, REC_TIMED = 2 };             // Recorder::kind (fluence; the other families have the first only)
 struct Recorder {
@@ -77,13 +78,16 @@ struct Recorder {
     DeviceBuffer dev;
     uint64_t n_keys = 0;
     int32_t n_totals = 0;                        // as allocated: 8 or 12 (timed) for fluence, 16 for the others
+    int32_t bin_u = 0, bin_v = 0, gates = 1, scatter = 0;      // sensitivity
+    uint64_t n_meas = 0;                         // sensitivity: the measurements, 8 float64 each behind the totals
     bool timed() const { return kind == REC_TIMED; }
     bool track() const { return kind == REC_TRACK; }
     uint64_t n_cells() const { return (uint64_t) box.res[0] * (uint64_t) box.res[1] * (uint64_t) box.res[2]; }
     int32_t faces() const { return det.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
     double *sums() const { return dev.as<double>(); }
     double *totals() const { return sums() + n_keys * 3; }
-    size_t bytes() const { return (n_keys * 3 + (uint64_t) n_totals) * sizeof(double); }
+    double *meas() const { return totals() + n_totals; }
+    size_t bytes() const { return (n_keys * 3 + (uint64_t) n_totals + n_meas * 8) * sizeof(double); }
 };
 
 #define MER_MAX_PIPES 4
@@ -139,7 +143,7 @@ struct mer_context {
     std::map<int, mer::Volume> volumes;
     std::map<int, mer::EnvMap> envmaps;          // mer_envmap_upload (handles from next_handle, as the volumes')
     std::map<int, mer::Recorder> recorders;      // fluence grids, exitance maps, sensitivity grids (handles from next_handle)
-    mer::DeviceBuffer detect_list; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 4 arrays of detect_cap words
+    mer::DeviceBuffer detect_list; uint32_t detect_cap = 0;   // the detected-path list of mer_render_sensitivity (allocated on first use): 64 words whose first is the count, then 5 arrays of detect_cap words
     int next_handle = 1;
     mer::DeviceBuffer counters;                  // MER_C_COUNT x replicas + work counter
     mer::DeviceBuffer ftable; int ftable_kind = -1; float ftable_param = 0;   // reconstruction-filter table on the device (33 floats) and what it holds

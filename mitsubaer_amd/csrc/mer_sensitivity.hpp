@@ -9,6 +9,9 @@
 //             wave-uniform skeleton of K_fluence_track (mer_fluence_track.hpp) and deposits w x length for the piece of every free flight
 //             inside each cell, cut as the track-length grid cuts them.  At the replayed exit it compares the w it recomputed with the
 //             recorded one, bit for bit, and counts the disagreements: 0 says the two passes walked the same paths.
+// An array of detectors and gates (mer_sensitivity_array_create) costs the same two passes: a path leaves through one raster cell at one
+// path length, so it belongs to at most one measurement m.  K_detect records m with the path, K_replay offsets its keys by it and, with
+// `scatter`, also deposits w at every scattering collision: the scattering grids K.
 #pragma once
 #include "mer_exitance.hpp"         // ExitanceMap, exitance_cell
 #include "mer_fluence_track.hpp"    // FluenceGrid, fluence_cell, TrackDDA
@@ -16,9 +19,10 @@
 namespace mer {
 
 // the detected-path list of a context: SoA, so that the lanes of a wave write (and K_replay's read) adjacent words.  id = the work id less
-// the launch's `first`.  cap = the paths of one launch chunk: the list cannot overflow.  One pointer, DETECT_HEAD words whose first is the
-// count, then the four arrays of cap words; the kernels form the arrays' addresses themselves: with a pointer per array, and a whole
-// ExitanceMap in the detector, four K_detect instances had 36 bytes of scratch (SGPR pressure from the kernel arguments).
+// the launch's `first`, m = the measurement (detector of the array x gate) the path belongs to.  cap = the paths of one launch chunk: the
+// list cannot overflow.  One pointer, DETECT_HEAD words whose first is the count, then the five arrays of cap words; the kernels form the
+// arrays' addresses themselves: with a pointer per array, and a whole ExitanceMap in the detector, four K_detect instances had 36 bytes of
+// scratch (SGPR pressure from the kernel arguments).
 #define DETECT_HEAD 64
 struct DetectList {
     uint32_t *count;
@@ -26,13 +30,45 @@ struct DetectList {
     unsigned long long *chk;
     __device__ __forceinline__ uint32_t *id() const { return count + DETECT_HEAD; }
     __device__ __forceinline__ float *w(int c) const { return (float *) (count + DETECT_HEAD + (size_t) (c + 1) * cap); }
+    __device__ __forceinline__ uint32_t *m() const { return count + DETECT_HEAD + (size_t) 4 * cap; }
 };
 
-// the detector of a mer_sensitivity handle: the raster, the window, the cone and the gate
+// the detectors of a mer_sensitivity handle: the raster, the window, the cone and the gates; one detector is bin_u x bin_v raster cells of
+// the window (bins = bin_u | bin_v << 16; mer_sensitivity_create: the whole window), gate g the paths with floorf((l - t_min) / t_bin) == g
 struct Detector {
     int32_t res_u, res_v, face, iu0, iu1, iv0, iv1;
     float cos_min, t_min, t_bin;
+    uint32_t bins;
+    int32_t gates;
 };
+
+// MEAS_WORDS float64 per measurement behind the totals of a sensitivity Recorder (mer.h, mer_sensitivity_read_array): [0..2] the detected
+// weight and [3] the detected paths (K_detect), [4..6] w x the path's scattering collisions (K_replay), [7] 0
+#define MEAS_WORDS 8
+#define SENS_TOTALS 16
+
+// Every lane of the wave calls this together, as wave_deposit (mer_lightpath.hpp), whose merging of equal keys this is: the lanes with
+// dep add (va, vb, vc, n) into meas[m][off ... off + 3]; one group of atomics per distinct m of the wave.
+__device__ __forceinline__ void wave_measure(double *meas, unsigned long long *chk, uint32_t n_meas, bool dep, uint32_t m, int off, double va, double vb, double vc, double n) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(dep);
+    while (todo) {
+        const int leader = __ffsll((long long) todo) - 1;
+        const uint32_t lm = (uint32_t) __shfl((int) m, leader, 64);
+        const bool same = dep && m == lm;
+        const unsigned long long g = __ballot(same);
+        double a = same ? va : 0.0, b = same ? vb : 0.0, c = same ? vc : 0.0, d = same ? n : 0.0;
+        if (g & (g - 1ULL)) { a = wave_sum_f64(a); b = wave_sum_f64(b); c = wave_sum_f64(c); d = wave_sum_f64(d); }
+        if (lane == leader) {
+            double *dst = meas + MER_CHK(chk, CHK_SENSITIVITY, (uint64_t) lm, n_meas) * MEAS_WORDS + off;
+            if (a != 0.0) atomicAdd(dst, a);
+            if (b != 0.0) atomicAdd(dst + 1, b);
+            if (c != 0.0) atomicAdd(dst + 2, c);
+            if (d != 0.0) atomicAdd(dst + 3, d);
+        }
+        todo &= ~g;
+    }
+}
 
 // What the exit-recording walk leaves in a lane
 struct ExitRecord {
@@ -98,7 +134,8 @@ __device__ __forceinline__ void exit_walk(const Params &P, LaneCounters &C, uint
     R.escaped = escaped; R.xe = xe; R.de = de; R.dexit = dexit; R.ended = ended; R.plen = plen;
 }
 
-// K_detect.  totals (mer.h): [0] paths, [1..3] the detected weight, [7] ended, [8] the detected paths.
+// K_detect.  totals (mer.h): [0] paths, [1..3] the detected weight, [7] ended, [8] the detected paths; the measurements follow the
+// totals: meas = totals + SENS_TOTALS.
 template <bool CURVED, int RIF, int STEPPER, int SIGMA>
 __global__ void __launch_bounds__(PT_BLOCK) detect_kernel(const Params P, const Detector D, const DetectList L, double *totals, uint64_t first, uint32_t count) {
     const mer_scene_desc &S = P.sc;
@@ -108,14 +145,23 @@ __global__ void __launch_bounds__(PT_BLOCK) detect_kernel(const Params P, const 
 
     // ---- the detector: cone (tested first), gate, window.  Every lane of the wave gets here.
     bool det = false;
+    uint32_t mi = 0;                                         // the measurement: (gate * ndv + dv) * ndu + du
     if (R.dexit >= 0.0f) {
         det = !(D.cos_min > 0.0f && dot(R.de, shape_normal(S, R.xe)) < D.cos_min);
-        if (det && D.t_bin > 0.0f) det = floorf((R.plen - D.t_min) / D.t_bin) == 0.0f;
+        if (det && D.t_bin > 0.0f) {
+            const float b = floorf((R.plen - D.t_min) / D.t_bin);
+            det = b >= 0.0f && b < (float) D.gates;
+            if (det) mi = (uint32_t) b;
+        }
         if (det) {
             ExitanceMap M; M.res_u = D.res_u; M.res_v = D.res_v;         // all that exitance_cell reads of a map
             const uint32_t cell = exitance_cell(S, M, R.xe), row = cell / (uint32_t) D.res_u;
             const int32_t iu = (int32_t) (cell - row * (uint32_t) D.res_u), iv = (int32_t) (row % (uint32_t) D.res_v), face = (int32_t) (row / (uint32_t) D.res_v);
             det = face == D.face && iu >= D.iu0 && iu < D.iu1 && iv >= D.iv0 && iv < D.iv1;
+            if (det) {
+                const uint32_t bu = D.bins & 0xffffu, bv = D.bins >> 16;
+                mi = (mi * ((uint32_t) (D.iv1 - D.iv0) / bv) + (uint32_t) (iv - D.iv0) / bv) * ((uint32_t) (D.iu1 - D.iu0) / bu) + (uint32_t) (iu - D.iu0) / bu;
+            }
         }
     }
     const f3 w = det ? R.escaped : f3(0, 0, 0);
@@ -132,7 +178,11 @@ __global__ void __launch_bounds__(PT_BLOCK) detect_kernel(const Params P, const 
             const uint64_t at = MER_CHK(L.chk, CHK_DETECT_LIST, base + (uint32_t) __popcll(mask & ((1ULL << lane) - 1ULL)), L.cap);
             L.id()[at] = blockIdx.x * PT_BLOCK + threadIdx.x;
             L.w(0)[at] = w.x; L.w(1)[at] = w.y; L.w(2)[at] = w.z;
+            L.m()[at] = mi;
         }
+        // the measurements: one group of atomics per distinct measurement of the wave
+        wave_measure(totals + SENS_TOTALS, L.chk, (uint32_t) D.gates * ((uint32_t) (D.iv1 - D.iv0) / (D.bins >> 16)) * ((uint32_t) (D.iu1 - D.iu0) / (D.bins & 0xffffu)),
+                     det, mi, 0, (double) w.x, (double) w.y, (double) w.z, 1.0);
     }
 
     // totals and counters: one wave-aggregated flush each, as K_exitance has them
@@ -152,18 +202,30 @@ __global__ void __launch_bounds__(PT_BLOCK) detect_kernel(const Params P, const 
 // detector, whatever the distance sampling: only the integrand of the detected signal depends on sigma_a.  The walk counters are not flushed:
 // mer_counters_read reports the detect pass.  totals: [4..6] w x the length outside the box, [9..11] w x the path's length inside the shape
 // (summed per lane in float64 from the flight lengths, before any cutting), [12] the replay disagreements.
-template <bool CURVED, int RIF, int STEPPER, int SIGMA>
-__global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const FluenceGrid G, const DetectList L, uint64_t first, uint32_t n) {
+// The path's measurement m (of n_meas) offsets its keys: the absorption grid J of m has the keys m * n_cells + cell.  scatter: the
+// scattering grids K follow the n_meas absorption grids, key (n_meas + m) * n_cells + cell: every real collision the path scatters from
+// deposits w into the cell of the collision point (K_fluence's cell); totals [13..15] w per collision outside the box; meas[m][4..6] w x the
+// path's collisions, counted before the box test.
+// ARRAY = false: the one measurement without a scattering grid of mer_sensitivity_create, whose instances then compile as they did before
+// the arrays (with the measurement and the collision registers in every instance two of the 14 lost a wave per SIMD and two gained 36
+// bytes of scratch: DESIGN.md, sensitivity maps); the last two arguments are ignored.
+template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool ARRAY>
+__global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const FluenceGrid G, const DetectList L, uint64_t first, uint32_t n,
+                                                          uint32_t n_meas_arg, uint32_t scatter_arg) {
+    const uint32_t n_meas = ARRAY ? n_meas_arg : 1u, scatter = ARRAY ? scatter_arg : 0u;
     const mer_scene_desc &S = P.sc;
     LaneCounters C; C.clear();
     LightPath<CURVED, SIGMA> lp;
     const uint32_t r = blockIdx.x * PT_BLOCK + threadIdx.x;
     const bool have = r < n;
-    uint32_t j = 0; f3 w(0, 0, 0);
+    uint32_t j = 0, kbase = 0; f3 w(0, 0, 0);
     if (have) {
         const uint64_t at = MER_CHK(L.chk, CHK_DETECT_LIST, r, L.cap);
         j = L.id()[at]; w = f3(L.w(0)[at], L.w(1)[at], L.w(2)[at]);
+        if (ARRAY) kbase = L.m()[at] * (uint32_t) G.n_cells;      // at most 2^27 keys
     }
+    const uint64_t n_keys = (uint64_t) (1u + scatter) * n_meas * G.n_cells;
+    uint32_t collisions = 0, collisions_out = 0;             // scatter: the path's scattering collisions, and those outside the box
     f3 escaped(0, 0, 0);
     float dexit = -1.0f;                                     // the length of the flight that reached the boundary (LightPath::weigh_exit)
     int left = 0;                                            // the replayed path left through the boundary
@@ -223,7 +285,7 @@ __global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const 
                         pl = l * h; got = pl > 0.0f;
                     }
                     const bool flush = got && run_on && c != run_cell;
-                    wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, G.n_cells, flush, run_cell, w * run_l);
+                    wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, n_keys, flush, kbase + run_cell, w * run_l);
                     if (got) {
                         if (flush || !run_on) { run_cell = c; run_l = pl; run_on = 1; }
                         else run_l += pl;
@@ -232,18 +294,25 @@ __global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const 
             }
         } else if (flight) ev = lp.run_flight(P, C, W, ev, sigma);
         float fL = 0.0f;                                     // straight: the length flown, [0, m.t] or [0, itsT]
+        bool kdep = false; uint32_t kcell = 0;               // scatter: the collision's deposit
         if (flight) {
             if (ev == EV_REAL) {
                 MRec m;
                 if (lp.collide(P, C, W, sigma, m)) {
                     fL = m.t;
+                    if (scatter) {
+                        collisions++;
+                        kdep = fluence_cell(G, m.p, kcell);
+                        if (!kdep) collisions_out++;
+                    }
                     lp.scatter(S, lp.arrive(W, m));
                 }
             } else if (ev != EV_GATE_FAIL) { escaped = lp.T * lp.power; left = 1; fL = itsT; dexit = lp.exit_distance(W); }
         }
-        // ---- the deposits
+        // ---- the deposits: every lane of the wave makes every call of every trip (scatter is the launch's)
+        if (scatter) wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, n_keys, kdep, n_meas * (uint32_t) G.n_cells + kbase + kcell, w);
         if (CURVED) {
-            wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, G.n_cells, run_on != 0, run_cell, w * run_l);      // the flight ended: flush the run
+            wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, n_keys, run_on != 0, kbase + run_cell, w * run_l);      // the flight ended: flush the run
             run_on = 0;
         } else {
             int pend = 0;
@@ -259,7 +328,7 @@ __global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const 
                     if (!pend) outside += (double) post;
                     got = l > 0.0f;
                 }
-                wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, G.n_cells, got, c, w * l);
+                wave_deposit(G.sums, G.chk, CHK_SENSITIVITY, n_keys, got, kbase + c, w * l);
             }
         }
     }
@@ -278,6 +347,16 @@ __global__ void __launch_bounds__(PT_BLOCK) replay_kernel(const Params P, const 
             if (tot[3 + q] != 0.0) atomicAdd(G.totals + 9 + q, tot[3 + q]);
         }
         if (tot[6] != 0.0) atomicAdd(G.totals + 12, tot[6]);
+    }
+    if (scatter) {
+        const double co = (double) collisions_out;
+        const double out[3] = {wave_sum_f64((double) w.x * co), wave_sum_f64((double) w.y * co), wave_sum_f64((double) w.z * co)};
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < 3; q++) if (out[q] != 0.0) atomicAdd(G.totals + 13 + q, out[q]);
+        }
+        wave_measure(G.totals + SENS_TOTALS, G.chk, n_meas, have && collisions != 0, kbase / (uint32_t) G.n_cells, 4,
+                     (double) w.x * (double) collisions, (double) w.y * (double) collisions, (double) w.z * (double) collisions, 0.0);
     }
 }
 

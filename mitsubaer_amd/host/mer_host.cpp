@@ -1255,6 +1255,33 @@ std::vector<float> Integrator::Sensitivity::jacobian() const {
     for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
     return v;
 }
+// ... and the grids of an array of detectors and gates, J and (scatter) K, from the same two passes
+Integrator::SensitivityArray Integrator::renderSensitivityArray(const Scene &scene, int device, const int res[3], mer_detector_desc det, int binU, int binV, int gates,
+                                                                bool scatter, int spp, unsigned long long seed) const {
+    LightPathSession s(*this, scene, device, spp, "the sensitivity grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    SensitivityArray out;
+    s.boundingBox(out.bmin, out.bmax);
+    mer_sensitivity_array_desc sd;
+    for (int a = 0; a < 3; a++) { sd.res[a] = out.res[a] = res[a]; sd.bmin[a] = out.bmin[a]; sd.bmax[a] = out.bmax[a]; }
+    det.boundary = s.d.boundary; det.reserved = 0;
+    sd.det = det; sd.bin_u = binU; sd.bin_v = binV; sd.gates = gates; sd.scatter = scatter ? 1 : 0; sd.reserved[0] = sd.reserved[1] = 0;
+    mer_sensitivity j = 0;
+    int32_t shape[4];
+    if (mer_sensitivity_array_create(s.ctx, &sd, &j) || mer_sensitivity_shape(s.ctx, j, shape)) s.fail();
+    out.gates = shape[0]; out.ndv = shape[1]; out.ndu = shape[2]; out.scatter = shape[3];
+    if (mer_render_sensitivity(s.ctx, &s.d, &s.whole, seed, j)) s.fail();
+    const size_t m = (size_t) out.gates * out.ndv * out.ndu;
+    out.sums.resize((size_t) (1 + out.scatter) * m * res[0] * res[1] * res[2] * 3);
+    out.meas.resize(m * 8);
+    if (mer_sensitivity_read_array(s.ctx, j, out.sums.data(), out.meas.data(), out.totals)) s.fail();
+    return out;
+}
+std::vector<float> Integrator::SensitivityArray::jacobian() const {
+    const double inv = totals[0] > 0 ? 1.0 / totals[0] : 0.0;
+    std::vector<float> v(sums.size());
+    for (size_t i = 0; i < sums.size(); i++) v[i] = (float) (sums[i] * inv);
+    return v;
+}
 bool parseDetector(const std::string &value, mer_detector_desc &det) {
     int v[7];
     if (!parseCounts(value, 7, 0, 9999, v)) return false;

@@ -270,6 +270,19 @@ public:
     };
     /// det: the detector (mer.h); its boundary is set to the scene's.  tBin = 0: no gate
     Sensitivity renderSensitivity(const Scene &scene, int device, const int res[3], mer_detector_desc det, int spp, unsigned long long seed) const;
+    /// the sensitivity grids of an array of detectors and gates in one render (mer_sensitivity_array_create): one detector is binU x binV raster
+    /// cells of det's window, gate g the exits with floor((l - t_min) / t_bin) == g for 0 <= g < gates; scatter: the scattering grids K too
+    struct SensitivityArray {
+        int res[3]; float bmin[3], bmax[3];
+        int gates = 1, ndv = 1, ndu = 1, scatter = 0;
+        std::vector<double> sums;               ///< raw sums [1 + scatter][gates][ndv][ndu][nz][ny][nx][3]: J, then K
+        std::vector<double> meas;               ///< [gates][ndv][ndu][8]: detected weight x 3, detected paths, w x scattering collisions x 3, 0
+        double totals[16];                      ///< as Sensitivity's; [13..15]: w per collision outside the box (mer_sensitivity_read_array)
+        /// sums / paths, float32, in the shape of sums
+        std::vector<float> jacobian() const;
+    };
+    SensitivityArray renderSensitivityArray(const Scene &scene, int device, const int res[3], mer_detector_desc det, int binU, int binV, int gates, bool scatter,
+                                            int spp, unsigned long long seed) const;
 private:
     struct LightPathSession;                    ///< mer_host.cpp: the one-device session the three recorders above share
     /// the medium's grids (density, albedo, index field, signed distance) onto every context of mm, their handles into d; on failure destroys mm and throws

@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cmath>
@@ -33,6 +33,7 @@ int main(int argc, char **argv) {
     float acceptCos = 0.0f; bool acceptCosSet = false;                    // --accept-cos=C: the acceptance cone of that map
     int sensitivityRes[3] = {0, 0, 0}; bool sensitivity = false;          // --sensitivity=NX,NY,NZ: the sensitivity grid of a detector on the boundary instead of the film
     mer_detector_desc detector; std::memset(&detector, 0, sizeof(detector)); bool detectorSet = false, gateSet = false;   // --detector=..., --gate=TMIN,TBIN
+    int detectorBins[2] = {0, 0}, gates = 1; bool binsSet = false, gatesSet = false, scatter = false;   // --detector-bins=BU,BV, --gates=N, --scatter: the array form
     std::vector<int> devices; int shardMode = MER_SHARD_SAMPLES;          // several GPUs (the reference: -p <workers>, src/mitsuba/mitsuba.cpp:281)
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -77,6 +78,16 @@ int main(int argc, char **argv) {
             if (!e2 || e2 == e + 1 || *e2 || !std::isfinite(detector.t_min) || !std::isfinite(detector.t_bin) || !(detector.t_bin > 0.0f)) { std::fprintf(stderr, "--gate=TMIN,TBIN expects a finite start and a width greater than 0, in optical path length\n"); return 2; }
             gateSet = true;
         }
+        else if (a.rfind("--detector-bins=", 0) == 0) {
+            if (!merhost::parseExitanceRes(a.substr(16), detectorBins)) { std::fprintf(stderr, "--detector-bins=BU,BV expects two cell counts between 1 and 4096\n"); return 2; }
+            binsSet = true;
+        }
+        else if (a.rfind("--gates=", 0) == 0) {
+            char *e = NULL; const long n = std::strtol(a.c_str() + 8, &e, 10);
+            if (e == a.c_str() + 8 || *e || n < 1 || n > (1L << 27)) { std::fprintf(stderr, "--gates=N expects a count of at least 1\n"); return 2; }
+            gates = (int) n; gatesSet = true;
+        }
+        else if (a == "--scatter") scatter = true;
         else if (a.rfind("--accept-cos=", 0) == 0) {
             char *e = NULL; acceptCos = std::strtof(a.c_str() + 13, &e);
             if (e == a.c_str() + 13 || *e || !(acceptCos >= 0.0f && acceptCos < 1.0f)) { std::fprintf(stderr, "--accept-cos=C expects a cosine with 0 <= C < 1\n"); return 2; }
@@ -84,7 +95,7 @@ int main(int argc, char **argv) {
         }
         else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--track-length") trackLength = true;
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN]] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -109,7 +120,12 @@ int main(int argc, char **argv) {
                                                          "  face FACE of an --exitance raster of NU x NV cells; --accept-cos=C narrows it to a cone, --gate=TMIN,TBIN to the optical path lengths\n"
                                                          "  TMIN <= l < TMIN + TBIN.  The detected paths are walked a second time and deposit weight x length on a grid of NX x NY x NZ cells over\n"
                                                          "  the medium shape's bounding box; -o names a 3-channel float32 VOL of J / paths (minus the derivative of the detected signal per path by\n"
-                                                         "  a cell's sigma_a), laid out as --fluence lays its VOL out; the totals are printed.  One GPU; not with --fluence, --exitance, --gpus or --devices\n"); return 0; }
+                                                         "  a cell's sigma_a), laid out as --fluence lays its VOL out; the totals are printed.  One GPU; not with --fluence, --exitance, --gpus or --devices\n"
+                                                         "  --detector-bins=BU,BV, --gates=N, --scatter (with --sensitivity= and --detector=): an array of detectors in one render.  One detector is\n"
+                                                         "  BU x BV raster cells of the window (BU, BV must divide it; default: the whole window), gate g takes TMIN + g TBIN <= l < TMIN + (g + 1) TBIN\n"
+                                                         "  for g < N (N > 1 needs --gate=), --scatter adds the scattering grids K (the detected weight per scattering collision in a cell; with a\n"
+                                                         "  homogeneous sigma_s the derivative of a detector's signal by sigma_s is K / sigma_s - J).  -o names a float32 .npy\n"
+                                                         "  [1 + scatter][gates][ndv][ndu][nz][ny][nx][3] = sums / paths; one line per measurement is printed: gate, dv, du, detected paths and weight\n"); return 0; }
         else scenePath = a;
     }
     if (exitance && fluence) { std::fprintf(stderr, "--exitance and --fluence exclude each other: one map per run\n"); return 2; }
@@ -120,6 +136,14 @@ int main(int argc, char **argv) {
     if (sensitivity && (timeResolved || trackLength)) { std::fprintf(stderr, "--time-resolved and --track-length belong to --fluence / --exitance: a sensitivity grid has the one gate of --gate=TMIN,TBIN\n"); return 2; }
     if (sensitivity && !detectorSet) { std::fprintf(stderr, "--sensitivity needs --detector=FACE,NU,NV,IU0,IU1,IV0,IV1\n"); return 2; }
     if ((detectorSet || gateSet) && !sensitivity) { std::fprintf(stderr, "--detector and --gate need --sensitivity=NX,NY,NZ\n"); return 2; }
+    const bool array = binsSet || gatesSet || scatter;
+    if (array && !(sensitivity && detectorSet)) { std::fprintf(stderr, "--detector-bins, --gates and --scatter need --sensitivity=NX,NY,NZ and --detector=FACE,NU,NV,IU0,IU1,IV0,IV1\n"); return 2; }
+    if (gates > 1 && !gateSet) { std::fprintf(stderr, "--gates=N above 1 needs --gate=TMIN,TBIN: the first gate and the width of every gate\n"); return 2; }
+    if (binsSet && ((detector.iu1 - detector.iu0) % detectorBins[0] || (detector.iv1 - detector.iv0) % detectorBins[1])) { std::fprintf(stderr, "--detector-bins=BU,BV must divide the window of --detector (IU1 - IU0 and IV1 - IV0)\n"); return 2; }
+    if (array) {
+        if (out == "out.npy") out = "sensitivity.npy";
+        if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--detector-bins, --gates and --scatter write a .npy file ([1 + scatter][gates][ndv][ndu][nz][ny][nx][3])\n"); return 2; }
+    }
     if (acceptCosSet && !exitance && !sensitivity) { std::fprintf(stderr, "--accept-cos needs --exitance=NU,NV\n"); return 2; }
     if (exitance) {
         if (out == "out.npy") out = "exitance.npy";
@@ -145,6 +169,24 @@ int main(int argc, char **argv) {
                         x.totals[0], x.totals[1], x.totals[2], x.totals[3], x.totals[4], x.totals[5], x.totals[6], x.totals[7], x.totals[8], x.totals[9], x.totals[10],
                         x.totals[11], x.totals[12], x.totals[13], x.totals[14], x.totals[15]);
             std::printf("wrote %s (%d frames of %d faces of %dx%d cells)\n", out.c_str(), x.frames, x.faces, x.resU, x.resV);
+            return 0;
+        }
+        if (sensitivity && array) {
+            detector.cos_min = acceptCos;
+            const merhost::Integrator::SensitivityArray j = scene->integrator->renderSensitivityArray(
+                *scene, device, sensitivityRes, detector, binsSet ? detectorBins[0] : detector.iu1 - detector.iu0, binsSet ? detectorBins[1] : detector.iv1 - detector.iv0, gates, scatter, spp, seed);
+            const std::vector<float> v = j.jacobian();
+            merhost::writeNpy(out, v.data(), std::vector<int>{1 + j.scatter, j.gates, j.ndv, j.ndu, j.res[2], j.res[1], j.res[0], 3});
+            std::printf("paths %.0f  detected weight %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f  detected %.0f  weight x length %.9g %.9g %.9g  disagreements %.0f  collisions dropped %.9g %.9g %.9g\n",
+                        j.totals[0], j.totals[1], j.totals[2], j.totals[3], j.totals[4], j.totals[5], j.totals[6], j.totals[7], j.totals[8], j.totals[9], j.totals[10],
+                        j.totals[11], j.totals[12], j.totals[13], j.totals[14], j.totals[15]);
+            for (int g = 0; g < j.gates; g++)
+                for (int dv = 0; dv < j.ndv; dv++)
+                    for (int du = 0; du < j.ndu; du++) {
+                        const double *m = &j.meas[(((size_t) g * j.ndv + dv) * j.ndu + du) * 8];
+                        std::printf("measurement gate %d dv %d du %d  detected %.0f  weight %.9g %.9g %.9g\n", g, dv, du, m[3], m[0], m[1], m[2]);
+                    }
+            std::printf("wrote %s (%d x %d x %d x %d grids of %dx%dx%d cells)\n", out.c_str(), 1 + j.scatter, j.gates, j.ndv, j.ndu, j.res[0], j.res[1], j.res[2]);
             return 0;
         }
         if (sensitivity) {
