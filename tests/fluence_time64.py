@@ -1,5 +1,5 @@
 """The time-resolved fluence grid of mer_render_fluence (a handle of mer_fluence_time_create) restated in float64 with numpy: the walk of
-tests/fluence64.py, draw for draw, with a path length per particle (include/mer.h, mer_fluence_time_create, has the estimator).
+tests/fluence64.py (lightpath64.walk with the medium Grey), with the path length per particle that the recorder Grid bins by (include/mer.h, mer_fluence_time_create, has the estimator).
 
 The path length l of a deposit: the exterior leg from an emitter outside the cube to its entry point, times 1 (the index outside), plus
 every free flight up to and including the one that ends at the collision, times rif_const (straight rays in a medium of constant index).
@@ -8,67 +8,17 @@ frame lies outside 0 ... frames - 1 goes to the out-of-window total, a point out
 
 Totals (12, as mer_fluence_time_read): the 8 of fluence64, then the out-of-window weight x 3, then 0."""
 import numpy as np
-from tests.fluence64 import hg_sample, cells, bar, total_bar, _slabs          # noqa: F401  (bar and total_bar: for the tests that import this module)
+from tests.lightpath64 import CUBE, Grey, Grid, walk, bar, total_bar          # noqa: F401  (bar and total_bar: for the tests that import this module)
 
 
 def render(emitter, sigma_s, sigma_a, g, res, frames, t_min, t_bin, rif_const=1.0, bmin=(-1, -1, -1), bmax=(1, 1, 1), paths=4096, batches=16,
            seed=0, max_depth=-1, rr_depth=5, max_events=4096):
     """`batches` independent batches of `paths` paths: (sums (batches, frames, nz, ny, nx), totals (batches, 12)), raw sums as the library
     keeps them (one channel: the medium is grey; the three channels of the totals are equal)"""
-    rng = np.random.default_rng(seed)
-    st = float(sigma_s + sigma_a); albedo = float(sigma_s) / st
-    ncell = int(np.prod(res))
-    sums = np.zeros((batches, frames * ncell)); totals = np.zeros((batches, 12))
-    outside = not np.all(np.abs(emitter["o"]) <= 1)
-    for b in range(batches):
-        N = paths
-        totals[b, 0] = N
-        if emitter["kind"] == "point":
-            w = rng.random((N, 2)); z = 1 - 2 * w[:, 0]; ph = 2 * np.pi * w[:, 1]; rr = np.sqrt(np.maximum(1 - z * z, 0))
-            d = np.stack([rr * np.cos(ph), rr * np.sin(ph), z], 1)
-        else:
-            d = np.tile(emitter["d"], (N, 1))
-        x = np.tile(emitter["o"], (N, 1))
-        T = np.ones(N); L = np.zeros(N); phi = emitter["phi"]
-        depth = 1
-        escaped = 0.0; dropped = 0.0; late = 0.0
-        if outside:                                                     # to the null boundary: one depth, one roulette trip
-            tn, tf = _slabs(x, d)
-            hit = (tn <= tf) & (tn > 0)
-            escaped += phi * np.count_nonzero(~hit)
-            x, d, T, L = x[hit] + d[hit] * tn[hit, None], d[hit], T[hit], L[hit] + tn[hit] * 1.0       # the exterior leg: index 1
-            if depth >= rr_depth:
-                q = np.minimum(T, 0.95); keep = rng.random(len(T)) < q
-                x, d, T, L = x[keep], d[keep], T[keep] / q[keep], L[keep]
-            depth += 1
-        for _ in range(max_events):
-            if len(T) == 0 or not (depth <= max_depth or max_depth < 0):
-                break
-            _, tex = _slabs(x, d)
-            tfl = -np.log1p(-rng.random(len(T))) / st
-            sc = tfl < tex
-            escaped += phi * T[~sc].sum()
-            x, d, T, L = x[sc] + d[sc] * tfl[sc, None], d[sc], T[sc], L[sc] + tfl[sc] * rif_const
-            if len(T) == 0:
-                break
-            idx, inside = cells(x, res, bmin, bmax)
-            f = np.floor((L - t_min) / t_bin)
-            timely = (f >= 0) & (f < frames)
-            wdep = T * phi / st
-            m = inside & timely
-            sums[b] += np.bincount(f[m].astype(np.int64) * ncell + idx[m], wdep[m], frames * ncell)
-            dropped += wdep[~inside].sum()
-            late += wdep[inside & ~timely].sum()
-            T = T * albedo
-            live = T > 0
-            x, d, T, L = x[live], d[live], T[live], L[live]
-            d = hg_sample(g, d, rng.random((len(T), 2)))
-            if depth >= rr_depth:
-                q = np.minimum(T, 0.95); keep = rng.random(len(T)) < q
-                x, d, T, L = x[keep], d[keep], T[keep] / q[keep], L[keep]
-            depth += 1
-        totals[b, 1:4] = escaped; totals[b, 4:7] = dropped; totals[b, 8:11] = late
-    return sums.reshape((batches, frames, res[2], res[1], res[0])), totals
+    rec = Grid(batches, 1, res, bmin, bmax, frames, t_min, t_bin)
+    walk(emitter, emitter["phi"], CUBE, Grey(sigma_s, sigma_a), g, [rec], n=rif_const, paths=paths, batches=batches, seed=seed, max_depth=max_depth,
+         rr_depth=rr_depth, max_events=max_events)
+    return rec.result()[..., 0], rec.totals
 
 
 def beam_column_time(emitter, sigma_t, rif_const, res, frames, t_min, t_bin, bmin=(-1, -1, -1), bmax=(1, 1, 1)):
