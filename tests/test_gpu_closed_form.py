@@ -169,3 +169,27 @@ def test_connection_in_a_constant_index_is_the_chord(ctx):
     np.testing.assert_allclose(d, chord / L[:, None], atol=2e-4)
     for v in vols:
         v.destroy()
+
+
+# ---- curved free flights, connections and NEE against exact rays of n = 1.5 + 0.45 y: the deterministic bounds are 8 x the fp32 CPU
+# oracle's measured deviation (closed_form.FREE_FLIGHT_MEASURED / CONNECT_MEASURED), never a GPU figure
+@pytest.mark.parametrize("stepper", [P.STEP_RK4, P.STEP_VERLET], ids=["rk4", "verlet"])
+def test_curved_transmittance_against_the_exact_ray(be, stepper):
+    cf.check_curved_transmittance(be, stepper)
+
+
+@pytest.mark.parametrize("ray", [0, 1])
+@pytest.mark.parametrize("stepper", [P.STEP_RK4, P.STEP_VERLET], ids=["rk4", "verlet"])
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_curved_free_flight_against_the_exact_ray(be, stepper, ray, layout):
+    cf.check_curved_free_flight(be, stepper, ray, layout=LAYOUTS[layout], tol=8.0)
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_connection_in_a_linear_index_against_the_exact_ray(be, layout):
+    cf.check_linear_connection(be, layout=LAYOUTS[layout], tol=8.0)
+
+
+@pytest.mark.parametrize("gridded", [False, True], ids=["homogeneous", "gridded"])
+def test_point_emitter_single_scatter_through_curved_rays(be, gridded):
+    cf.check_point_single_scatter_curved(be, gridded)

@@ -472,7 +472,7 @@ def test_constant_rif_reproduces_straight_rays(ctx):
 def test_errors_are_loud(ctx):
     p = scenes.straight_scene(N=16)
     sc, vols = ctx.upload_scene(p)
-    sc.density = 999
+    sc.density = 2 ** 30            # a handle the context never issued (they count up from 1 over the whole session)
     with pytest.raises(capi.MerError, match="No density specified"):
         ctx.render_to_host(sc, 0, 1)
     sc, vols = ctx.upload_scene(p)

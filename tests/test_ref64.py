@@ -123,3 +123,76 @@ def test_camera_rays_are_the_pinhole(orc, cam):
 
 def test_emission_only_slab_per_pixel(orc):
     cf.check_emission_slab(cf.Oracle(orc))
+
+
+# ---- curved free flights, connections and NEE against exact rays of n = 1.5 + 0.45 y (CPU seconds: fp32 / fp64 alike)
+def test_linear_index_connection_is_a_ray_between_its_points():
+    """the connection reference itself: reversible (same arc and optical length, arrival = -launch of the reverse), a vertical pair is its
+    chord with optical length mean(n) x length, the arc exceeds the chord and the optical length undercuts the chord's (the landing test runs inside the function)"""
+    a, b = cf.CURVED_A, cf.CURVED_B
+    rng = np.random.RandomState(2)
+    p1 = rng.uniform(-0.7, 0.7, (256, 3)); p2 = rng.uniform(-0.7, 0.7, (256, 3))
+    p1[0] = [0.1, -0.3, 0.2]; p2[0] = [0.1, 0.5, 0.2]
+    v0, ve, arc, opt = ref64.linear_index_connection(a, b, p1, p2)
+    r0, re, rarc, ropt = ref64.linear_index_connection(a, b, p2, p1)
+    assert np.abs(arc - rarc).max() < 1e-12 and np.abs(opt - ropt).max() < 1e-12 and np.abs(ve + r0).max() < 1e-12 and np.abs(v0 + re).max() < 1e-12
+    assert np.abs(np.linalg.norm(v0, axis=1) - (a + b * p1[:, 1])).max() < 1e-12 and np.abs(np.linalg.norm(ve, axis=1) - (a + b * p2[:, 1])).max() < 1e-12
+    assert abs(arc[0] - 0.8) < 1e-12 and abs(opt[0] - (a + b * 0.1) * 0.8) < 1e-12
+    L = np.linalg.norm(p2 - p1, axis=1)
+    assert (arc - L).min() > -1e-12 and (arc - L).max() > 0.01 and np.all(opt <= (a + b * 0.5 * (p1[:, 1] + p2[:, 1])) * L + 1e-12)   # Fermat: no longer than the chord's optical length
+
+
+def test_curve_optical_depth_quadrature_error():
+    """halving the spacing: the quadrature of the gridded sigma_t along both exact rays has converged to 1e-7 at the table the checks use
+    (tau ~ 2.3 and 3.2; the Monte Carlo standard errors it is compared with are above 1e-3 of tau), and tau is increasing up to the exit"""
+    p = cf.curved_case()
+    for i in range(len(cf.CURVED_RAYS)):
+        s, tau, sx = cf._curved_tau(p, i)
+        s2, tau2, sx2 = cf._curved_tau(p, i, m=2 * (len(s) - 1) + 1)
+        s4, tau4, _ = cf._curved_tau(p, i, m=(len(s) - 1) // 2 + 1)
+        assert sx == sx2 and abs(tau[-1] - tau2[-1]) < 1e-7 and abs(tau4[-1] - tau[-1]) < 4e-7, (tau4[-1], tau[-1], tau2[-1])
+        assert np.abs(np.interp(s[::50], s2, tau2) - tau[::50]).max() < 1e-7
+        assert np.all(np.diff(tau) >= 0) and np.all(np.diff(s) > 0)
+        end, _, _ = ref64.linear_index_trajectory(cf.CURVED_A, cf.CURVED_B, [cf.CURVED_RAYS[i][0]], [cf.CURVED_RAYS[i][1]], sx)
+        assert abs(np.abs(end).max() - 1) < 1e-6                                    # the table ends on a face of the cube
+    # a constant sigma_t: tau = sigma_t x arc
+    s, tau, sx = ref64.curve_optical_depth(cf.CURVED_A, cf.CURVED_B, None, 1.0, [-0.6, 0.5, -0.3], [1.0, 0.3, 0.2], sigma_t=1.2)
+    assert np.abs(tau - 1.2 * s).max() < 1e-9
+
+
+def test_curved_single_scatter_quadrature_error():
+    """halving both spacings moves the quadrature of check_point_single_scatter_curved by less than 1e-4 of itself (the check allows 3 %),
+    and with b -> 0 it is the straight-ray quadrature of point_single_scatter times the phase function"""
+    for gridded in (False, True):
+        p = cf.curved_single_scatter_scene(gridded)
+        ref = cf.curved_single_scatter_reference(p, gridded)[0]
+        kw = dict(density=p.density, scale=p.density_scale, albedo=p.albedo[0]) if gridded else dict(sigma_t=1.2, albedo=0.75)
+        half = ref64.point_single_scatter_curved(cf.CURVED_A, cf.CURVED_B, [-1, 0, 0], [1, 0, 0], p.point_position, p.g, n=801, m=401, **kw)[0]
+        assert abs(half / ref - 1) < 1e-4, (half, ref)
+    flat = ref64.point_single_scatter_curved(1.3, 1e-5, [-1, 0, 0], [1, 0, 0], [0.1, 0.6, -0.2], 0.0, 0.75, sigma_t=1.2)[0]
+    straight = ref64.point_single_scatter([-3, 0, 0], [1, 0, 0], 2.0, 4.0, 0.3, 0.9, [0.1, 0.6, -0.2])[0]
+    assert abs(flat / straight - 1) < 1e-4, (flat, straight)
+
+
+@pytest.mark.parametrize("stepper", [P.STEP_RK4, P.STEP_VERLET], ids=["rk4", "verlet"])
+def test_curved_transmittance_against_the_exact_ray(be, stepper):
+    """1 s (RK4), 9 s (Verlet at the small step)"""
+    cf.check_curved_transmittance(be, stepper)
+
+
+@pytest.mark.parametrize("ray", [0, 1])
+@pytest.mark.parametrize("stepper", [P.STEP_RK4, P.STEP_VERLET], ids=["rk4", "verlet"])
+def test_curved_free_flight_against_the_exact_ray(be, stepper, ray):
+    """1 s (RK4), 4 s (Verlet)"""
+    cf.check_curved_free_flight(be, stepper, ray)
+
+
+def test_connection_in_a_linear_index_against_the_exact_ray(be):
+    """3 s: 512 pairs in 0.1 s, the rest is the 3 x 200 000 seeds of the expectation"""
+    cf.check_linear_connection(be)
+
+
+@pytest.mark.parametrize("gridded", [False, True], ids=["homogeneous", "gridded"])
+def test_point_emitter_single_scatter_through_curved_rays(orc, gridded):
+    """42 s / 62 s on 8 threads: sized by the weight-100 restarts; fp32 only"""
+    cf.check_point_single_scatter_curved(cf.Oracle(orc), gridded)
