@@ -273,6 +273,14 @@ typedef struct { int32_t res[3]; float bmin[3], bmax[3]; int32_t frames; float t
    frames == 1 and t_bin == 0.  cos_min: the acceptance cone about the outward normal (0 accepts every exit).  reserved must be 0. */
 typedef int32_t mer_exitance;                                 /* handle, > 0, from the context's handle counter */
 typedef struct { int32_t boundary; int32_t res[2]; int32_t frames; float t_min, t_bin, cos_min; int32_t reserved; } mer_exitance_desc;
+/* the frequency-domain recorders (mer_fluence_fd_create, mer_exitance_fd_create): the box of a fluence grid or the raster and cone of an
+   exitance map, and n_freq (1 ... MER_MAX_FREQUENCIES) wavenumbers k >= 0 in radians per unit of optical path length -- k = 2 pi f / c0 for
+   the modulation frequency f and the vacuum speed of light c0 in scene units per second; k = 0 is the steady state.  The entries of
+   wavenumber past n_freq and every reserved word must be 0.  Both structs are laid out without implicit padding (48 and 24 bytes before
+   wavenumber). */
+#define MER_MAX_FREQUENCIES 8
+typedef struct { int32_t res[3]; float bmin[3], bmax[3]; int32_t n_freq; int32_t reserved[2]; double wavenumber[MER_MAX_FREQUENCIES]; } mer_fluence_fd_desc;
+typedef struct { int32_t boundary; int32_t res[2]; float cos_min; int32_t n_freq; int32_t reserved; double wavenumber[MER_MAX_FREQUENCIES]; } mer_exitance_fd_desc;
 /* a detector on the boundary of the medium shape (mer_sensitivity_create): the raster of an exitance map of res[0] x res[1] (u x v) cells per
    face, one `face` of it (0 ... 5 for MER_BOUNDARY_AABB, 0 for MER_BOUNDARY_SPHERE) and on that face the half-open cell window
    iu0 <= iu < iu1, iv0 <= iv < iv1; the acceptance cone cos_min about the outward normal (0 accepts every exit); the gate (t_min, t_bin) in
@@ -569,6 +577,45 @@ int  mer_exitance_clear(mer_context *ctx, mer_exitance e);
 int  mer_exitance_destroy(mer_context *ctx, mer_exitance e);
 int  mer_render_exitance(mer_context *ctx, const mer_scene_desc *scene, const mer_shard *shard, uint64_t seed, mer_exitance e);
 int  mer_exitance_read(mer_context *ctx, mer_exitance e, double *sums /* [frames][faces][res_v][res_u][3] or NULL */, double totals[16]);
+
+/* ---- frequency-domain fluence grids and exitance maps: the response to an intensity-modulated source, the third standard measurement of
+        photon migration beside the steady state and the pulse.  The field at a point, and the signal at a detector, is a complex number
+        whose modulus is the amplitude and whose argument is the phase lag of the photon-density wave.  A frequency-domain grid is a further
+        kind of mer_fluence handle and a frequency-domain map a second kind of mer_exitance handle: mer_fluence_clear / mer_exitance_clear,
+        mer_fluence_destroy / mer_exitance_destroy, mer_render_fluence / mer_render_exitance and mer_context_destroy take them, and the
+        render entry points pick the kernel by the handle's kind (every other kind renders exactly as before).
+        The estimator.  The walk is mer_render_fluence's / mer_render_exitance's, draw for draw: recording draws no sampler number, fetches
+        no RIF value and advances no counter, so for one scene, shard and seed the counters, totals[0] and totals[7] equal those of the
+        steady handles.  A handle holds n_freq wavenumbers k_j.
+          grid   every real collision deposits into the cell of the collision point, per channel, with the weight w of mer_fluence_create
+                 and the optical path length l that mer_fluence_time_create bins (float32: the exterior leg at index 1, then per free
+                 flight integral n ds on a curved ray or t * rif_const on a straight one):  w cos(k_j l) into the real plane of frequency
+                 j and w sin(k_j l) into its imaginary plane.
+          map    the one exit of a path adds w (cos, sin)(k_j l) to the cell of x, with x, d, w and l exactly what mer_render_exitance
+                 records (l includes the last flight).  cos_min applies as it does there; there is no window: `late` stays 0.
+        Phase arithmetic.  phi = k_j * (double) l with k_j kept in float64; phi is reduced to [-pi, pi] in float64, rounded to float32
+        once, and cos / sin are float32: each has an absolute error of at most 2^-21 (pi 2^-24 from the rounding, 2 ulp from the
+        functions).  The pair is then scaled to unit modulus in float64 (to within 1e-12) and multiplied with w in float64, so that no
+        deposit weighs more than its w.  k = 0 gives exactly (1, 0): its real plane receives the deposits of the steady handle, and its
+        imaginary plane is never written and stays exactly 0.0.
+        Layout.  Raw float64 sums, added with float64 atomics, plane (2 j + part) for part 0 = real, 1 = imaginary:
+          grid   double[n_freq][2][nz][ny][nx][3]; complex fluence = sums / (paths * cell volume)
+          map    double[n_freq][2][faces][res_v][res_u][3]; complex exitance = sums / (paths * cell area)
+        at most 2^27 keys (cells x 2 x n_freq).  Raw sums of disjoint shards add.  amplitude = hypot(re, im), phase = atan2(im, re); the
+        modulus never exceeds the steady sum of the same paths.
+        Totals.  mer_fluence_fd_read: the 8 of mer_fluence_read, [4..6] the plain w of the points outside the box.  mer_exitance_fd_read:
+        the 16 of mer_exitance_read; [8..10] (late) stay 0, [14] counts the exits binned once, not per plane.
+        Refusals.  mer_fluence_fd_create: the box checks of mer_fluence_create; mer_exitance_fd_create: the boundary, res and cos_min
+        checks of mer_exitance_create; both, each with its own message and *out = 0: n_freq outside 1 ... MER_MAX_FREQUENCIES; a wavenumber
+        that is negative or not finite; a non-zero entry past n_freq; a non-zero reserved word; more than 2^27 keys.
+        mer_fluence_read, mer_fluence_time_read and mer_exitance_read refuse a frequency-domain handle and name the reader to use;
+        mer_fluence_fd_read and mer_exitance_fd_read refuse every other kind the same way.  sums may be NULL (totals only).
+        Scope: exactly that of mer_render_fluence / mer_render_exitance.  Not built: a frequency-domain track-length grid,
+        frequency-domain sensitivity grids, several GPUs in one call. ---- */
+int  mer_fluence_fd_create(mer_context *ctx, const mer_fluence_fd_desc *desc, mer_fluence *out);
+int  mer_fluence_fd_read(mer_context *ctx, mer_fluence f, double *sums /* [n_freq][2][nz][ny][nx][3] or NULL */, double totals[8]);
+int  mer_exitance_fd_create(mer_context *ctx, const mer_exitance_fd_desc *desc, mer_exitance *out);
+int  mer_exitance_fd_read(mer_context *ctx, mer_exitance e, double *sums /* [n_freq][2][faces][res_v][res_u][3] or NULL */, double totals[16]);
 
 /* ---- sensitivity maps: which part of the medium did the light that reached a detector travel through.  The absorption sensitivity of
         the detected signal -- the Jacobian of diffuse optical tomography, the photon-measurement density function, the "banana" between

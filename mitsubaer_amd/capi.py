@@ -3,6 +3,7 @@ loading fails loudly if the library is missing, and context creation fails witho
 import collections
 import ctypes as C
 import os
+from types import SimpleNamespace
 import numpy as np
 from . import params as P
 
@@ -31,6 +32,7 @@ SYMBOLS = [
     "mer_fluence_create", "mer_fluence_clear", "mer_fluence_destroy", "mer_render_fluence", "mer_fluence_read",
     "mer_fluence_time_create", "mer_fluence_time_read", "mer_fluence_track_create",
     "mer_exitance_create", "mer_exitance_clear", "mer_exitance_destroy", "mer_render_exitance", "mer_exitance_read",
+    "mer_fluence_fd_create", "mer_fluence_fd_read", "mer_exitance_fd_create", "mer_exitance_fd_read",
     "mer_sensitivity_create", "mer_sensitivity_clear", "mer_sensitivity_destroy", "mer_render_sensitivity", "mer_sensitivity_read",
     "mer_sensitivity_array_create", "mer_sensitivity_shape", "mer_sensitivity_read_array",
 ]
@@ -487,6 +489,78 @@ def validate_exitance(desc):
         raise MerError(at + "more than 2^27 cells x faces x frames")
 
 
+MAX_FREQUENCIES = 8           # MER_MAX_FREQUENCIES
+
+
+class FluenceFDDesc(C.Structure):
+    """mer_fluence_fd_desc: the box of a FluenceDesc and n_freq wavenumbers k >= 0 in radians per unit of optical path length (k = 2 pi f / c0;
+    0: the steady state).  No implicit padding: wavenumber starts at byte 48"""
+    _fields_ = [("res", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("n_freq", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("wavenumber", C.c_double * MAX_FREQUENCIES)]
+
+
+class ExitanceFDDesc(C.Structure):
+    """mer_exitance_fd_desc: the raster and cone of an ExitanceDesc and n_freq wavenumbers; wavenumber starts at byte 24"""
+    _fields_ = [("boundary", C.c_int32), ("res", C.c_int32 * 2), ("cos_min", C.c_float), ("n_freq", C.c_int32), ("reserved", C.c_int32),
+                ("wavenumber", C.c_double * MAX_FREQUENCIES)]
+
+
+def _set_wavenumbers(d, wavenumbers):
+    """n_freq and the wavenumber array of a frequency-domain desc; a list no desc can hold is refused here, under the name of n_freq's check"""
+    k = [float(v) for v in np.atleast_1d(np.asarray(wavenumbers, np.float64))]
+    d.n_freq = len(k)
+    d.wavenumber[:] = (k + [0.0] * MAX_FREQUENCIES)[:MAX_FREQUENCIES]
+    return d
+
+
+def fluence_fd_desc(res, bmin, bmax, wavenumbers):
+    d = FluenceFDDesc()
+    d.res[:] = [int(v) for v in res]
+    d.bmin[:] = [float(v) for v in bmin]
+    d.bmax[:] = [float(v) for v in bmax]
+    return _set_wavenumbers(d, wavenumbers)
+
+
+def exitance_fd_desc(boundary, res, wavenumbers, cos_min=0.0):
+    d = ExitanceFDDesc()
+    d.boundary = int(boundary)
+    d.res[:] = [int(v) for v in res]
+    d.cos_min = float(cos_min)
+    return _set_wavenumbers(d, wavenumbers)
+
+
+def _validate_frequencies(desc, at, reserved):
+    """the wavenumber checks the two frequency-domain recorders share, under the entry point's prefix"""
+    if desc.n_freq < 1 or desc.n_freq > MAX_FREQUENCIES:
+        raise MerError(at + "n_freq must lie in 1 ... 8")
+    for j in range(desc.n_freq):
+        if not np.isfinite(desc.wavenumber[j]) or desc.wavenumber[j] < 0:
+            raise MerError(at + "a wavenumber must be finite and at least 0")
+    for j in range(desc.n_freq, MAX_FREQUENCIES):
+        if not desc.wavenumber[j] == 0:
+            raise MerError(at + "the entries of wavenumber past n_freq must be 0")
+    if any(v != 0 for v in reserved):
+        raise MerError(at + "reserved must be 0")
+
+
+def validate_fluence_fd(desc):
+    """The refusals of mer_fluence_fd_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_fluence_fd_create: "
+    _validate_box(desc, at)
+    _validate_frequencies(desc, at, desc.reserved[:])
+    if desc.res[0] * desc.res[1] * desc.res[2] * 2 * desc.n_freq > 1 << 27:
+        raise MerError(at + "more than 2^27 cells x 2 x n_freq")
+
+
+def validate_exitance_fd(desc):
+    """The refusals of mer_exitance_fd_create, with its messages: MerError.  No GPU needed."""
+    at = "mer_exitance_fd_create: "
+    _validate_raster(SimpleNamespace(boundary=desc.boundary, res=desc.res, t_bin=0.0, t_min=0.0, cos_min=desc.cos_min, reserved=0), at, "res", 1)
+    _validate_frequencies(desc, at, [desc.reserved])
+    if 2 * desc.n_freq * exitance_faces(desc.boundary) * desc.res[0] * desc.res[1] > 1 << 27:
+        raise MerError(at + "more than 2^27 cells x faces x 2 x n_freq")
+
+
 class DetectorDesc(C.Structure):
     """mer_detector_desc: the raster of an exitance map (res = (res_u, res_v) cells per face), one face of it, the half-open cell window
     iu0 <= iu < iu1, iv0 <= iv < iv1 on that face, the acceptance cone cos_min and the gate (t_min, t_bin) in optical path length (t_bin 0: none)"""
@@ -596,18 +670,21 @@ def _box_shape(d):
 
 # The kinds of recorder a context hands out (Context._recorder_*): the family whose clear / destroy / render entry points take the handle
 # (mer_<family>_clear, mer_<family>_destroy, mer_render_<family>), the C create function, the desc builder, the validator, the read entry point
-# with its totals count, the shape of the sums (without the 3 channels) from the desc and what the family's other read says of this kind.
-# A new kind is one row here and the public methods that name it.
-_Recorder = collections.namedtuple("_Recorder", "family create desc validate read totals shape other_read")
+# with its totals count, the shape of the sums (without the 3 channels) from the desc and what the family's other reads call this kind: they
+# refuse it with "<their name>: <what>: use <read>".  A new kind is one row here and the public methods that name it.
+_Recorder = collections.namedtuple("_Recorder", "family create desc validate read totals shape what")
 _RECORDERS = {
-    "fluence": _Recorder("fluence", "mer_fluence_create", fluence_desc, validate_fluence, "mer_fluence_read", 8, _box_shape,
-                         "mer_fluence_time_read: steady-state grid: use mer_fluence_read"),
+    "fluence": _Recorder("fluence", "mer_fluence_create", fluence_desc, validate_fluence, "mer_fluence_read", 8, _box_shape, "steady-state grid"),
     "fluence_track": _Recorder("fluence", "mer_fluence_track_create", fluence_desc, validate_fluence_track, "mer_fluence_read", 8, _box_shape,
-                               "mer_fluence_time_read: steady-state grid: use mer_fluence_read"),
+                               "steady-state grid"),
     "fluence_time": _Recorder("fluence", "mer_fluence_time_create", fluence_time_desc, validate_fluence_time, "mer_fluence_time_read", 12,
-                              lambda d: (d.frames,) + _box_shape(d), "mer_fluence_read: time-resolved grid: use mer_fluence_time_read"),
+                              lambda d: (d.frames,) + _box_shape(d), "time-resolved grid"),
+    "fluence_fd": _Recorder("fluence", "mer_fluence_fd_create", fluence_fd_desc, validate_fluence_fd, "mer_fluence_fd_read", 8,
+                            lambda d: (d.n_freq, 2) + _box_shape(d), "frequency-domain grid"),
     "exitance": _Recorder("exitance", "mer_exitance_create", exitance_desc, validate_exitance, "mer_exitance_read", 16,
-                          lambda d: (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0]), None),
+                          lambda d: (d.frames, exitance_faces(d.boundary), d.res[1], d.res[0]), "steady or time-gated map"),
+    "exitance_fd": _Recorder("exitance", "mer_exitance_fd_create", exitance_fd_desc, validate_exitance_fd, "mer_exitance_fd_read", 16,
+                             lambda d: (d.n_freq, 2, exitance_faces(d.boundary), d.res[1], d.res[0]), "frequency-domain map"),
     "sensitivity": _Recorder("sensitivity", "mer_sensitivity_create", sensitivity_desc, validate_sensitivity, "mer_sensitivity_read", 16, _box_shape, None),
     # read through Context.sensitivity_read_array (which takes the handles of both rows) and, with one measurement and no K, Context.sensitivity_read
     "sensitivity_array": _Recorder("sensitivity", "mer_sensitivity_array_create", sensitivity_array_desc, validate_sensitivity_array, "mer_sensitivity_read_array", 16,
@@ -979,7 +1056,7 @@ class Context:
             if mine is None or _RECORDERS[mine].family != k.family:
                 raise MerError("%s: unknown %s handle" % (k.read, k.family))
             if _RECORDERS[mine].read != k.read:
-                raise MerError(_RECORDERS[mine].other_read)
+                raise MerError("%s: %s: use %s" % (k.read, _RECORDERS[mine].what, _RECORDERS[mine].read))
             out = np.zeros(shape + (3,), np.float64)
         self._check(getattr(self.lib, k.read)(self.h, C.c_int32(handle), _fp(out) if sums else None, _fp(totals)))
         return out, totals
@@ -1016,6 +1093,17 @@ class Context:
     def fluence_time_read(self, handle, sums=True):
         """-> (raw sums float64 [frames][nz][ny][nx][3], or None with sums = False; totals float64 [12])"""
         return self._recorder_read("fluence_time", handle, sums)
+
+    def fluence_fd_create(self, res, bmin, bmax, wavenumbers):
+        """-> handle of a zeroed frequency-domain grid (mer_fluence_fd_create): the box of fluence_create and up to 8 wavenumbers k >= 0 in
+        radians per unit of optical path length (2 pi f / c0; 0: the steady state).  fluence_clear, fluence_destroy and render_fluence take it
+        like any other fluence handle."""
+        return self._recorder_create("fluence_fd", res, bmin, bmax, wavenumbers)
+
+    def fluence_fd_read(self, handle, sums=True):
+        """-> (raw float64 sums [n_freq][2][nz][ny][nx][3] -- real and imaginary plane per wavenumber -- or None, totals float64 [8]:
+        capi.FLUENCE_TOTALS).  complex fluence = sums / (paths x cell volume)"""
+        return self._recorder_read("fluence_fd", handle, sums)
 
     def _fluence_box(self, scene, bmin, bmax):
         """the box of a fluence map: the caller's, or the bounding box of the medium shape"""
@@ -1089,6 +1177,16 @@ class Context:
     def exitance_read(self, handle, sums=True):
         """-> (raw sums float64 [frames][faces][res_v][res_u][3], or None with sums = False; totals float64 [16])"""
         return self._recorder_read("exitance", handle, sums)
+
+    def exitance_fd_create(self, boundary, res, wavenumbers, cos_min=0.0):
+        """-> handle of a zeroed frequency-domain map (mer_exitance_fd_create): the raster and cone of exitance_create and up to 8
+        wavenumbers.  exitance_clear, exitance_destroy and render_exitance take it like any other exitance handle."""
+        return self._recorder_create("exitance_fd", boundary, res, wavenumbers, cos_min)
+
+    def exitance_fd_read(self, handle, sums=True):
+        """-> (raw float64 sums [n_freq][2][faces][res_v][res_u][3] or None, totals float64 [16]: capi.EXITANCE_TOTALS; `late` stays 0).
+        complex exitance = sums / (paths x cell area)"""
+        return self._recorder_read("exitance_fd", handle, sums)
 
     def exitance(self, scene, res, spp_count, frames=1, t_min=0.0, t_bin=0.0, cos_min=0.0, seed=0, spp_begin=0):
         """One exitance map of the scene (integrator = ptracer) over the boundary of its medium shape: (raw sums float64

@@ -10,6 +10,9 @@
 // With the null boundary and a convex shape a path leaves at most once, so a lane keeps its one (key, w) in registers and the wave deposits
 // ONCE, after the event loop, with all 64 lanes converged (wave_deposit).  The event loop itself needs no wave-uniform trip count for the
 // deposit; it keeps K_fluence's form.
+//
+// FD (a handle of mer_exitance_fd_create): the same exit, deposited as w (cos, sin)(k_j l) into the 2 n_freq planes of the map
+// (wave_deposit_fd, mer_lightpath.hpp) at the same site.  The cone applies; there is no window.
 #pragma once
 #include "mer_lightpath.hpp"
 
@@ -23,6 +26,10 @@ struct ExitanceMap {
     float t_min, t_bin, cos_min;
     __host__ __device__ uint64_t n_keys() const { return (uint64_t) frames * (uint64_t) faces * (uint64_t) res_v * (uint64_t) res_u; }
 };
+
+// A frequency-domain handle: sums = double[n_freq][2][faces][res_v][res_u][3], frames = 2 n_freq planes, t_bin = 0, and the wavenumbers
+// lie behind the 16 totals, as FluenceGrid has it (mer_fluence.hpp)
+__device__ __forceinline__ const double *exitance_wavenumbers(const ExitanceMap &M) { return M.totals + 16; }
 
 // floor(f * res) clamped into 0 ... res - 1 (a NaN ends as 0): the point is on the boundary by construction, so it is never dropped
 __device__ __forceinline__ uint32_t exitance_index(float f, int32_t res) {
@@ -55,7 +62,7 @@ __device__ __forceinline__ uint32_t exitance_cell(const mer_scene_desc &S, const
 }
 
 // K_exitance
-template <bool CURVED, int RIF, int STEPPER, int SIGMA>
+template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool FD = false>
 __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, const ExitanceMap M, uint64_t first, uint32_t count) {
     const mer_scene_desc &S = P.sc;
     LaneCounters C; C.clear();
@@ -118,14 +125,15 @@ __global__ void __launch_bounds__(PT_BLOCK) exitance_kernel(const Params P, cons
         dep = true;
         if (M.cos_min > 0.0f && dot(de, shape_normal(S, xe)) < M.cos_min) {
             dep = false; rejected[0] = (double) escaped.x; rejected[1] = (double) escaped.y; rejected[2] = (double) escaped.z;
-        } else if (M.t_bin > 0.0f) {
+        } else if (!FD && M.t_bin > 0.0f) {
             const float b = floorf((plen - M.t_min) / M.t_bin);
             if (b >= 0.0f && b < (float) M.frames) key = (uint32_t) b * (uint32_t) (M.faces * M.res_v * M.res_u);      // the key stays below 2^27
             else { dep = false; late[0] = (double) escaped.x; late[1] = (double) escaped.y; late[2] = (double) escaped.z; }
         }
         if (dep) key += exitance_cell(S, M, xe);
     }
-    wave_deposit(M.sums, M.chk, CHK_EXITANCE, M.n_keys(), dep, key, escaped);
+    if constexpr (FD) wave_deposit_fd(M.sums, M.chk, CHK_EXITANCE, (uint32_t) (M.faces * M.res_v * M.res_u), exitance_wavenumbers(M), M.frames >> 1, dep, key, escaped, plen);
+    else wave_deposit(M.sums, M.chk, CHK_EXITANCE, M.n_keys(), dep, key, escaped);
 
     // totals and counters: one wave-aggregated flush each
     const double tot[15] = {(double) wave_sum(C.paths), wave_sum_f64((double) escaped.x), wave_sum_f64((double) escaped.y), wave_sum_f64((double) escaped.z),

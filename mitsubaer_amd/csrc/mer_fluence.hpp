@@ -12,6 +12,9 @@
 // TIMED (a handle of mer_fluence_time_create): the same walk, which also carries the light tracer's optical path length `plen`
 // (float32: the exterior leg at index 1, then m.opticalLength or m.t * rif_const per free flight) and bins every deposit by it:
 // frame = floorf((plen - t_min) / t_bin), key = frame * n_cells + cell.  The window is the handle's own; the film fields stay ignored.
+//
+// FD (a handle of mer_fluence_fd_create): the same walk and the same plen, and every deposit goes, as w (cos, sin)(k_j plen), into the
+// 2 n_freq planes of the grid (wave_deposit_fd, mer_lightpath.hpp) at the same wave-converged site.  There is no window.
 #pragma once
 #include "mer_lightpath.hpp"
 
@@ -30,6 +33,12 @@ struct FluenceGrid {
     float t_min, t_bin;
     __host__ __device__ uint64_t n_keys() const { return (uint64_t) frames * n_cells; }
 };
+// A frequency-domain handle: sums = double[n_freq][2][nz][ny][nx][3], frames = 2 n_freq planes, totals = double[8], and behind the totals
+// the wavenumbers, float64[MER_MAX_FREQUENCIES], in the recorder's own buffer.  No kernel argument is added for them: the plane loop
+// indexes them with a scalar, eight doubles by value would be 16 kernel-argument SGPRs, and even a pointer and a count beside the grid --
+// three SGPRs that the compiler loads at the kernel's entry and keeps across the event loop -- cost the straight gridded instance of
+// K_exitance 36 bytes of scratch
+__device__ __forceinline__ const double *fluence_wavenumbers(const FluenceGrid &G) { return G.totals + 8; }
 
 // the cell of p: per axis floor((p - bmin) / (bmax - bmin) * res), half-open; false outside the box (and for a p that is not a number)
 __device__ __forceinline__ bool fluence_cell(const FluenceGrid &G, f3 p, uint32_t &cell) {
@@ -42,8 +51,9 @@ __device__ __forceinline__ bool fluence_cell(const FluenceGrid &G, f3 p, uint32_
     return true;
 }
 
-// K_fluence.  The deposit's key is the cell; TIMED: frame * n_cells + cell, and the extent is the time-resolved grid's.
-template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool TIMED>
+// K_fluence.  The deposit's key is the cell; TIMED: frame * n_cells + cell, and the extent is the time-resolved grid's; FD: the cell in
+// each of the 2 n_freq planes.  TIMED and FD exclude each other.
+template <bool CURVED, int RIF, int STEPPER, int SIGMA, bool TIMED, bool FD = false>
 __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const FluenceGrid G, uint64_t first, uint32_t count) {
     const mer_scene_desc &S = P.sc;
     LaneCounters C; C.clear();
@@ -52,11 +62,11 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
     float dexit = -1.0f;                                     // ... after a flight of this length that reached the boundary (LightPath::weigh_exit)
     double dropped[3] = {0.0, 0.0, 0.0};
     uint32_t ended = 0;
-    float plen = 0.0f;                                       // TIMED: the optical path length, accumulated in float32 as K_ptracer does under a TRANSIENT film
+    float plen = 0.0f;                                       // TIMED, FD: the optical path length, accumulated in float32 as K_ptracer does under a TRANSIENT film
     double late[3] = {0.0, 0.0, 0.0};                        // TIMED: the weight of deposits inside the box but outside the time window
     int x, y; float tIn;
     const int how = lp.decode(P, C, first, count, x, y) ? lp.emit(P, tIn) : LP_DEAD;
-    if (how == LP_ENTERED) { if (TIMED) plen += tIn; }
+    if (how == LP_ENTERED) { if (TIMED || FD) plen += tIn; }
     else if (how == LP_MISSED) escaped = lp.power;
 
     Walk<CURVED, RIF, STEPPER, SIGMA> W;
@@ -79,8 +89,8 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                             w = lp.T * lp.power * (m.transmittance / m.pdfSuccess);
                             dep = fluence_cell(G, m.p, cell);
                             if (!dep) { dropped[0] += (double) w.x; dropped[1] += (double) w.y; dropped[2] += (double) w.z; }
+                            if (TIMED || FD) plen += CURVED ? m.opticalLength : m.t * S.rif_const;
                             if (TIMED) {
-                                plen += CURVED ? m.opticalLength : m.t * S.rif_const;
                                 if (dep) {
                                     const float b = floorf((plen - G.t_min) / G.t_bin);                  // film_contribute's bin
                                     if (b >= 0.0f && b < (float) G.frames) cell += (uint32_t) b * (uint32_t) G.n_cells;      // the key, below 2^27
@@ -94,7 +104,8 @@ __global__ void __launch_bounds__(PT_BLOCK) fluence_kernel(const Params P, const
                 }
             }
         }
-        wave_deposit(G.sums, G.chk, CHK_FLUENCE, TIMED ? G.n_keys() : G.n_cells, dep, cell, w);
+        if constexpr (FD) wave_deposit_fd(G.sums, G.chk, CHK_FLUENCE, (uint32_t) G.n_cells, fluence_wavenumbers(G), G.frames >> 1, dep, cell, w, plen);
+        else wave_deposit(G.sums, G.chk, CHK_FLUENCE, TIMED ? G.n_keys() : G.n_cells, dep, cell, w);
     }
     if (lp.alive) ended++;                                   // PT_MAX_EVENTS
     lp.weigh_exit(P, dexit, escaped);

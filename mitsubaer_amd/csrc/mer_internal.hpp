@@ -66,10 +66,13 @@ struct EnvMap {
 // the family decides which entry points know a handle (the other two families refuse it as unknown), the kind which kernel a fluence handle renders with.
 //   fluence      sums [frames][nz][ny][nx][3] over `box`, 8 totals; timed: frames > 0 bins of det.t_bin from det.t_min on, 12 totals; track: K_fluence_track
 //   exitance     sums [frames][faces][res_v][res_u][3], 16 totals: det holds the boundary, raster, window and cone
+//   REC_FD       a fluence grid or an exitance map with 2 x n_freq planes in place of the frames (real, imaginary per frequency), no window, the totals
+//                of its steady sibling; the wavenumbers, float64[MER_MAX_FREQUENCIES], lie behind the totals, where the kernels read them (a
+//                clear leaves them alone)
 //   sensitivity  sums [1 + scatter][gates][ndv][ndu][nz][ny][nx][3] over `box`, 16 totals, then n_meas = gates x ndv x ndu measurements of 8 float64:
 //                det is the raster, window, cone and first gate; one detector is bin_u x bin_v cells of the window (mer_sensitivity_create: all of it)
 enum { REC_FLUENCE = 0, REC_EXITANCE = 1, REC_SENSITIVITY = 2 };      // Recorder::family
-enum { REC_COLLISION = 0, REC_TRACK = 1, REC_TIMED = 2 };             // Recorder::kind (fluence; the other families have the first only)
+enum { REC_COLLISION = 0, REC_TRACK = 1, REC_TIMED = 2, REC_FD = 3 };  // Recorder::kind (fluence: all four; exitance: the first -- steady or gated -- and REC_FD; sensitivity: the first)
 struct Recorder {
     int32_t family = REC_FLUENCE, kind = REC_COLLISION;
     mer_fluence_desc box{};
@@ -80,14 +83,18 @@ struct Recorder {
     int32_t n_totals = 0;                        // as allocated: 8 or 12 (timed) for fluence, 16 for the others
     int32_t bin_u = 0, bin_v = 0, gates = 1, scatter = 0;      // sensitivity
     uint64_t n_meas = 0;                         // sensitivity: the measurements, 8 float64 each behind the totals
+    int32_t n_freq = 0; double wavenumber[MER_MAX_FREQUENCIES] = {};     // REC_FD: the wavenumbers (the host's copy)
     bool timed() const { return kind == REC_TIMED; }
+    bool fd() const { return kind == REC_FD; }
     bool track() const { return kind == REC_TRACK; }
     uint64_t n_cells() const { return (uint64_t) box.res[0] * (uint64_t) box.res[1] * (uint64_t) box.res[2]; }
     int32_t faces() const { return det.boundary == MER_BOUNDARY_SPHERE ? 1 : 6; }
     double *sums() const { return dev.as<double>(); }
     double *totals() const { return sums() + n_keys * 3; }
     double *meas() const { return totals() + n_totals; }
-    size_t bytes() const { return (n_keys * 3 + (uint64_t) n_totals + n_meas * 8) * sizeof(double); }
+    double *wavenumbers() const { return totals() + n_totals; }        // REC_FD (which has no measurements)
+    size_t cleared_bytes() const { return (n_keys * 3 + (uint64_t) n_totals + n_meas * 8) * sizeof(double); }      // what a clear zeroes
+    size_t bytes() const { return cleared_bytes() + (fd() ? sizeof(wavenumber) : 0); }
 };
 
 #define MER_MAX_PIPES 4

@@ -108,6 +108,23 @@ static inline int check_raster(mer_context *ctx, const std::string &at, const ch
     return 0;
 }
 
+// The wavenumbers of a frequency-domain recorder (mer_fluence_fd_create, mer_exitance_fd_create) and the reserved words beside them
+static inline int check_frequencies(mer_context *ctx, const std::string &at, int32_t n_freq, const double wavenumber[MER_MAX_FREQUENCIES], const int32_t *reserved, int n_reserved) {
+    if (n_freq < 1 || n_freq > MER_MAX_FREQUENCIES) return fail(ctx, at + "n_freq must lie in 1 ... 8");
+    for (int j = 0; j < n_freq; j++)
+        if (!std::isfinite(wavenumber[j]) || wavenumber[j] < 0) return fail(ctx, at + "a wavenumber must be finite and at least 0");
+    for (int j = n_freq; j < MER_MAX_FREQUENCIES; j++)
+        if (!(wavenumber[j] == 0)) return fail(ctx, at + "the entries of wavenumber past n_freq must be 0");
+    for (int q = 0; q < n_reserved; q++)
+        if (reserved[q] != 0) return fail(ctx, at + "reserved must be 0");
+    return 0;
+}
+// ... into the recorder; alloc_sums puts them behind the totals on the device
+static inline void set_frequencies(Recorder &v, int32_t n_freq, const double wavenumber[MER_MAX_FREQUENCIES]) {
+    v.kind = REC_FD; v.n_freq = n_freq;
+    for (int j = 0; j < MER_MAX_FREQUENCIES; j++) v.wavenumber[j] = wavenumber[j];
+}
+
 // ---- The Recorder behind a handle (mer_internal.hpp).  Every entry point opens with one of these two: false / nullptr means return 1 (the
 // message is set unless ctx is null).  create_args: the arguments of a *_create.
 static inline bool create_args(mer_context *ctx, const void *desc, int *out, const char *who) {
@@ -133,6 +150,7 @@ static inline int alloc_sums(mer_context *ctx, Recorder &v, const std::string &c
     if (v.dev.alloc(ctx, v.bytes())) return 1;
     if (hipMemsetAsync(v.dev.p, 0, v.bytes(), ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
         return fail(ctx, clearing_failed);
+    if (v.fd()) HIP_CHECK(ctx, hipMemcpy(v.wavenumbers(), v.wavenumber, sizeof(v.wavenumber), hipMemcpyHostToDevice));
     const int h = ctx->next_handle++;
     ctx->recorders[h] = std::move(v);
     *out = h;
@@ -140,7 +158,7 @@ static inline int alloc_sums(mer_context *ctx, Recorder &v, const std::string &c
 }
 static inline int clear_sums(mer_context *ctx, const Recorder *v) {
     if (!v) return 1;
-    HIP_CHECK(ctx, hipMemsetAsync(v->dev.p, 0, v->bytes(), ctx->stream));
+    HIP_CHECK(ctx, hipMemsetAsync(v->dev.p, 0, v->cleared_bytes(), ctx->stream));
     HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -158,12 +176,12 @@ static inline int read_sums(mer_context *ctx, const Recorder &v, double *sums, d
     HIP_CHECK(ctx, hipMemcpy(totals, v.totals(), (size_t) v.n_totals * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
-// the voxel grid K_fluence, K_fluence_track and K_replay deposit into: the recorder's box, and the time bins of a timed fluence grid
+// the voxel grid K_fluence, K_fluence_track and K_replay deposit into: the recorder's box, and the time bins of a timed fluence grid or the planes of a frequency-domain one
 // (Grid = FluenceGrid, mer_fluence.hpp, which only the translation units of those kernels include)
 template <class Grid> static Grid fluence_grid(const mer_context *ctx, const Recorder &R) {
     Grid G;
     G.sums = R.sums(); G.totals = R.totals(); G.chk = ctx->chk; G.n_cells = R.n_cells();
-    G.frames = R.timed() ? R.frames : 0; G.t_min = R.timed() ? R.det.t_min : 0; G.t_bin = R.timed() ? R.det.t_bin : 0;
+    G.frames = R.timed() ? R.frames : R.fd() ? 2 * R.n_freq : 0; G.t_min = R.timed() ? R.det.t_min : 0; G.t_bin = R.timed() ? R.det.t_bin : 0;
     for (int a = 0; a < 3; a++) { G.res[a] = R.box.res[a]; G.bmin[a] = R.box.bmin[a]; G.bmax[a] = R.box.bmax[a]; }
     return G;
 }

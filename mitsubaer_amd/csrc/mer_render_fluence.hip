@@ -1,7 +1,7 @@
 // mer_render_fluence.hip -- the fluence grid recorded from light paths: instantiations of K_fluence (mer_fluence.hpp), its launch and the
 // mer_fluence_* entry points, over the Recorder of family REC_FLUENCE and what mer_lightpath_host.hpp shares.  A time-resolved grid
 // (mer_fluence_time_create) renders with the TIMED instantiations, a track-length grid (mer_fluence_track_create) with K_fluence_track
-// (mer_render_fluence_track.hip).
+// (mer_render_fluence_track.hip), a frequency-domain grid (mer_fluence_fd_create) with the FD instantiations (mer_render_fluence_fd.hip).
 #include "mer_lightpath_host.hpp"
 #include "mer_fluence.hpp"
 
@@ -15,6 +15,8 @@ typedef FluenceFamily<false>::Kernel FluenceKernel;
 
 // mer_render_fluence_track.hip: the same 14 combinations of K_fluence_track, for a handle of mer_fluence_track_create
 FluenceKernel pick_fluence_track(const mer_scene_desc *sc);
+// mer_render_fluence_fd.hip: ... and of the frequency-domain kind of K_fluence, for a handle of mer_fluence_fd_create
+FluenceKernel pick_fluence_fd(const mer_scene_desc *sc);
 
 // the box checks of mer_fluence_create, then the window's
 static int check_fluence_time_desc(mer_context *ctx, const mer_fluence_time_desc *d) {
@@ -30,14 +32,16 @@ static int check_fluence_time_desc(mer_context *ctx, const mer_fluence_time_desc
 }
 
 // the grid of a checked box (and window: frames > 0), zeroed, and its handle
+// wavenumber (n_freq > 0): a frequency-domain grid, 2 n_freq planes and no window
 static int alloc_fluence(mer_context *ctx, const char *who, int kind, const int32_t res[3], const float bmin[3], const float bmax[3], int32_t frames,
-                         float t_min, float t_bin, mer_fluence *out) {
+                         float t_min, float t_bin, mer_fluence *out, int32_t n_freq = 0, const double *wavenumber = nullptr) {
     Recorder F;
     F.family = REC_FLUENCE; F.kind = kind;
     for (int a = 0; a < 3; a++) { F.box.res[a] = res[a]; F.box.bmin[a] = bmin[a]; F.box.bmax[a] = bmax[a]; }
     F.frames = frames; F.det.t_min = t_min; F.det.t_bin = t_bin;
-    F.n_keys = F.n_cells() * (uint64_t) (frames > 0 ? frames : 1);
+    F.n_keys = F.n_cells() * (uint64_t) (n_freq > 0 ? 2 * n_freq : frames > 0 ? frames : 1);
     F.n_totals = frames > 0 ? 12 : 8;
+    if (n_freq > 0) set_frequencies(F, n_freq, wavenumber);
     return alloc_sums(ctx, F, std::string(who) + ": clearing the grid failed", out);
 }
 
@@ -52,7 +56,7 @@ static int launch_fluence(mer_context *ctx, const mer_scene_desc *scene, const m
         if (scene->strategy == MER_STRATEGY_BALANCE && !(P.sigT.x == P.sigT.y && P.sigT.y == P.sigT.z))
             return fail(ctx, at + "strategy balance with a channel-dependent sigma_t samples a mixture of exponentials");
     }
-    const FluenceKernel kernel = F.track() ? pick_fluence_track(scene) : F.timed() ? pick_light_kernel<FluenceFamily<true>>(scene) : pick_light_kernel<FluenceFamily<false>>(scene);
+    const FluenceKernel kernel = F.fd() ? pick_fluence_fd(scene) : F.track() ? pick_fluence_track(scene) : F.timed() ? pick_light_kernel<FluenceFamily<true>>(scene) : pick_light_kernel<FluenceFamily<false>>(scene);
     return launch_light_paths(ctx, scene, P, seed, nullptr, 0, kernel, fluence_grid<FluenceGrid>(ctx, F));
 }
 
@@ -77,6 +81,15 @@ int mer_fluence_time_create(mer_context *ctx, const mer_fluence_time_desc *d, me
     return alloc_fluence(ctx, "mer_fluence_time_create", REC_TIMED, d->res, d->bmin, d->bmax, d->frames, d->t_min, d->t_bin, out);
 }
 
+int mer_fluence_fd_create(mer_context *ctx, const mer_fluence_fd_desc *d, mer_fluence *out) {
+    const std::string at = "mer_fluence_fd_create: ";
+    if (!create_args(ctx, d, out, "mer_fluence_fd_create") || check_box(ctx, at, d->res, d->bmin, d->bmax) ||
+        check_frequencies(ctx, at, d->n_freq, d->wavenumber, d->reserved, 2)) return 1;
+    if ((uint64_t) d->res[0] * (uint64_t) d->res[1] * (uint64_t) d->res[2] * (uint64_t) (2 * d->n_freq) > ((uint64_t) 1 << 27))
+        return fail(ctx, at + "more than 2^27 cells x 2 x n_freq");
+    return alloc_fluence(ctx, "mer_fluence_fd_create", REC_FD, d->res, d->bmin, d->bmax, 0, 0, 0, out, d->n_freq, d->wavenumber);
+}
+
 int mer_fluence_clear(mer_context *ctx, mer_fluence h) { return clear_sums(ctx, find_recorder(ctx, h, REC_FLUENCE, "mer_fluence_clear")); }
 
 int mer_fluence_destroy(mer_context *ctx, mer_fluence h) { return destroy_sums(ctx, h, find_recorder(ctx, h, REC_FLUENCE, "mer_fluence_destroy")); }
@@ -90,14 +103,24 @@ int mer_fluence_read(mer_context *ctx, mer_fluence h, double *sums, double total
     const Recorder *F = find_recorder(ctx, h, REC_FLUENCE, "mer_fluence_read");
     if (!F) return 1;
     if (F->timed()) return fail(ctx, "mer_fluence_read: time-resolved grid: use mer_fluence_time_read");
+    if (F->fd()) return fail(ctx, "mer_fluence_read: frequency-domain grid: use mer_fluence_fd_read");
     return read_sums(ctx, *F, sums, totals, "mer_fluence_read");
 }
 
 int mer_fluence_time_read(mer_context *ctx, mer_fluence h, double *sums, double totals[12]) {
     const Recorder *F = find_recorder(ctx, h, REC_FLUENCE, "mer_fluence_time_read");
     if (!F) return 1;
+    if (F->fd()) return fail(ctx, "mer_fluence_time_read: frequency-domain grid: use mer_fluence_fd_read");
     if (!F->timed()) return fail(ctx, "mer_fluence_time_read: steady-state grid: use mer_fluence_read");
     return read_sums(ctx, *F, sums, totals, "mer_fluence_time_read");       // [11] is never written: 0
+}
+
+int mer_fluence_fd_read(mer_context *ctx, mer_fluence h, double *sums, double totals[8]) {
+    const Recorder *F = find_recorder(ctx, h, REC_FLUENCE, "mer_fluence_fd_read");
+    if (!F) return 1;
+    if (F->timed()) return fail(ctx, "mer_fluence_fd_read: time-resolved grid: use mer_fluence_time_read");
+    if (!F->fd()) return fail(ctx, "mer_fluence_fd_read: steady-state grid: use mer_fluence_read");
+    return read_sums(ctx, *F, sums, totals, "mer_fluence_fd_read");
 }
 
 }

@@ -1172,6 +1172,26 @@ Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, co
     if (frames > 0 ? mer_fluence_time_read(s.ctx, f, out.sums.data(), out.totals) : mer_fluence_read(s.ctx, f, out.sums.data(), out.totals)) s.fail();
     return out;
 }
+// The frequency-domain grid: 2 planes per wavenumber, no window
+Integrator::Fluence Integrator::renderFluence(const Scene &scene, int device, const int res[3], const std::vector<double> &wavenumbers, int spp, unsigned long long seed) const {
+    LightPathSession s(*this, scene, device, spp, "the fluence grid is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    Fluence out;
+    s.boundingBox(out.bmin, out.bmax);
+    mer_fluence_fd_desc fd;
+    std::memset(&fd, 0, sizeof(fd));
+    for (int a = 0; a < 3; a++) { fd.res[a] = out.res[a] = res[a]; fd.bmin[a] = out.bmin[a]; fd.bmax[a] = out.bmax[a]; }
+    if (wavenumbers.empty() || wavenumbers.size() > MER_MAX_FREQUENCIES) Log_EError("a frequency-domain grid takes 1 ... 8 wavenumbers");
+    fd.n_freq = (int32_t) wavenumbers.size();
+    for (size_t j = 0; j < wavenumbers.size(); j++) fd.wavenumber[j] = wavenumbers[j];
+    out.wavenumbers = wavenumbers;
+    mer_fluence f = 0;
+    if (mer_fluence_fd_create(s.ctx, &fd, &f)) s.fail();
+    if (mer_render_fluence(s.ctx, &s.d, &s.whole, seed, f)) s.fail();
+    out.sums.resize(wavenumbers.size() * 2 * res[0] * res[1] * res[2] * 3);
+    for (int q = 8; q < 12; q++) out.totals[q] = 0.0;
+    if (mer_fluence_fd_read(s.ctx, f, out.sums.data(), out.totals)) s.fail();
+    return out;
+}
 std::vector<float> Integrator::Fluence::phi() const {
     double volume = 1.0;
     for (int a = 0; a < 3; a++) volume *= ((double) bmax[a] - (double) bmin[a]) / res[a];
@@ -1198,6 +1218,23 @@ static bool parseCounts(const std::string &value, int n, int lo, int hi, int *v)
 bool parseFluenceRes(const std::string &value, int res[3]) {
     return parseCounts(value, 3, 1, 1024, res) && (long long) res[0] * res[1] * res[2] <= (1LL << 27);
 }
+int parseFrequencies(const std::string &value, std::vector<double> &k) {
+    k.clear();
+    bool bad = false;
+    for (size_t p = 0; p <= value.size();) {
+        size_t e = value.find(',', p);
+        if (e == std::string::npos) e = value.size();
+        const std::string tok = value.substr(p, e - p);
+        char *end = NULL;
+        const double v = std::strtod(tok.c_str(), &end);
+        if (tok.empty() || end != tok.c_str() + tok.size() || std::isspace((unsigned char) tok[0])) return 1;
+        if (!std::isfinite(v) || v < 0) bad = true;
+        k.push_back(v);
+        p = e + 1;
+    }
+    if (k.size() > MER_MAX_FREQUENCIES) return 2;
+    return bad ? 3 : 0;
+}
 
 // The exitance map of a `ptracer` scene: one map over the medium shape's boundary
 Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const {
@@ -1219,6 +1256,34 @@ Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, 
     if (mer_render_exitance(s.ctx, &d, &s.whole, seed, e)) s.fail();
     out.sums.resize((size_t) frames * out.faces * res[1] * res[0] * 3);
     if (mer_exitance_read(s.ctx, e, out.sums.data(), out.totals)) s.fail();
+    return out;
+}
+// The frequency-domain map: 2 planes per wavenumber in place of the frames, no window
+Integrator::Exitance Integrator::renderExitance(const Scene &scene, int device, const int res[2], const std::vector<double> &wavenumbers, float cosMin, int spp, unsigned long long seed) const {
+    LightPathSession s(*this, scene, device, spp, "the exitance map is recorded from light paths: the scene's integrator must be \"ptracer\"");
+    const mer_scene_desc &d = s.d;
+    Exitance out;
+    mer_exitance_fd_desc ed;
+    std::memset(&ed, 0, sizeof(ed));
+    ed.boundary = out.boundary = d.boundary;
+    ed.res[0] = out.resU = res[0]; ed.res[1] = out.resV = res[1];
+    ed.cos_min = out.cosMin = cosMin;
+    if (wavenumbers.empty() || wavenumbers.size() > MER_MAX_FREQUENCIES) Log_EError("a frequency-domain map takes 1 ... 8 wavenumbers");
+    ed.n_freq = (int32_t) wavenumbers.size();
+    for (size_t j = 0; j < wavenumbers.size(); j++) ed.wavenumber[j] = wavenumbers[j];
+    out.wavenumbers = wavenumbers;
+    out.frames = 2 * ed.n_freq;                  // the planes, in the place of the frames: exitance() finds the face of a value by it
+    out.faces = d.boundary == MER_BOUNDARY_SPHERE ? 1 : 6;
+    for (int f = 0; f < 6; f++) {
+        const int axis = f / 2, ua = (axis + 1) % 3, va = (axis + 2) % 3;
+        out.cellArea[f] = d.boundary == MER_BOUNDARY_SPHERE ? 4.0 * M_PI * (double) d.sph_radius * (double) d.sph_radius / ((double) res[0] * res[1])
+                                                            : ((double) d.bmax[ua] - (double) d.bmin[ua]) * ((double) d.bmax[va] - (double) d.bmin[va]) / ((double) res[0] * res[1]);
+    }
+    mer_exitance e = 0;
+    if (mer_exitance_fd_create(s.ctx, &ed, &e)) s.fail();
+    if (mer_render_exitance(s.ctx, &d, &s.whole, seed, e)) s.fail();
+    out.sums.resize((size_t) out.frames * out.faces * res[1] * res[0] * 3);
+    if (mer_exitance_fd_read(s.ctx, e, out.sums.data(), out.totals)) s.fail();
     return out;
 }
 std::vector<float> Integrator::Exitance::exitance() const {

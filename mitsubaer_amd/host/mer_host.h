@@ -234,9 +234,11 @@ public:
     struct Fluence {
         int res[3]; float bmin[3], bmax[3];
         int frames = 0; float tMin = 0.0f, tBin = 0.0f;   ///< the time-resolved form: frames > 0 bins of width tBin from tMin on in optical path length
-        std::vector<double> sums;               ///< raw sums [nz][ny][nx][3]; time-resolved: [frames][nz][ny][nx][3]
+        std::vector<double> wavenumbers;        ///< the frequency-domain form: not empty, k >= 0 in radians per unit of optical path length
+        std::vector<double> sums;               ///< raw sums [nz][ny][nx][3]; time-resolved: [frames][nz][ny][nx][3]; frequency-domain: [n_freq][2][nz][ny][nx][3]
         double totals[12];                      ///< paths, escaped x 3, dropped x 3, ended (mer_fluence_read); time-resolved: then out-of-window x 3 and 0 (mer_fluence_time_read)
-        /// sums / (paths x cell volume), float32 [nz][ny][nx][3]; time-resolved: sums / (paths x cell volume x tBin), [frames][nz][ny][nx][3]
+        /// sums / (paths x cell volume), float32 [nz][ny][nx][3]; time-resolved: sums / (paths x cell volume x tBin), [frames][nz][ny][nx][3];
+        /// frequency-domain: sums / (paths x cell volume), [n_freq][2][nz][ny][nx][3]
         std::vector<float> phi() const;
     };
     /// trackLength: the track-length estimator (mer_fluence_track_create): every free flight deposits along its path, voids included; the scene's
@@ -245,11 +247,15 @@ public:
     /// the time-resolved form (mer_fluence_time_create): every deposit also binned by the optical path length at which it happens.  The window is
     /// the caller's; the scene's film is not read.  frames = 0: the steady-state grid.  A time-resolved track-length grid does not exist
     Fluence renderFluence(const Scene &scene, int device, const int res[3], int frames, float tMin, float tBin, int spp, unsigned long long seed, bool trackLength = false) const;
+    /// the frequency-domain form (mer_fluence_fd_create): every deposit as w (cos, sin)(k l) into a real and an imaginary plane per wavenumber
+    /// k (1 ... MER_MAX_FREQUENCIES of them, >= 0, radians per unit of optical path length; 0: the steady state)
+    Fluence renderFluence(const Scene &scene, int device, const int res[3], const std::vector<double> &wavenumbers, int spp, unsigned long long seed) const;
     /// where and when the light paths of a `ptracer` scene leave the medium: a map of resU x resV cells on every face of the medium shape's
     /// boundary (mer_render_exitance: a grid of the reference's `irradiancemeter` probes on the shape), width x height x spp paths on one device
     struct Exitance {
         int boundary = 0, faces = 6, resU = 1, resV = 1;
         int frames = 1; float tMin = 0.0f, tBin = 0.0f, cosMin = 0.0f;   ///< a steady map: frames 1, tBin 0
+        std::vector<double> wavenumbers;        ///< the frequency-domain form: not empty; sums then are [n_freq][2][faces][resV][resU][3]
         double cellArea[6];                     ///< per face: cube u-extent x v-extent / (resU x resV); sphere 4 pi r^2 / (resU x resV)
         std::vector<double> sums;               ///< raw sums [frames][faces][resV][resU][3]
         double totals[16];                      ///< paths, escaped x 3, missed x 3, ended, late x 3, rejected x 3, exits binned, 0 (mer_exitance_read)
@@ -258,6 +264,8 @@ public:
     };
     /// frames = 1 and tBin = 0: the steady map.  The window is the caller's; the scene's film is not read
     Exitance renderExitance(const Scene &scene, int device, const int res[2], int frames, float tMin, float tBin, float cosMin, int spp, unsigned long long seed) const;
+    /// the frequency-domain form (mer_exitance_fd_create): the one exit of a path as w (cos, sin)(k l) per wavenumber; no window
+    Exitance renderExitance(const Scene &scene, int device, const int res[2], const std::vector<double> &wavenumbers, float cosMin, int spp, unsigned long long seed) const;
     /// which part of the medium the light that reached a detector travelled through: the absorption sensitivity (Jacobian) of a detector on the
     /// boundary of the medium shape, on a grid of res[0] x res[1] x res[2] cells over the shape's bounding box (mer_render_sensitivity: the
     /// detected light paths of a `ptracer` scene are walked a second time and deposit w x length), width x height x spp paths on one device
@@ -319,6 +327,9 @@ void writeVol(const std::string &path, const float *data, int nx, int ny, int nz
 bool parseFluenceRes(const std::string &value, int res[3]);
 /// `mer_render --exitance=NU,NV`: two counts between 1 and 4096; false for anything else
 bool parseExitanceRes(const std::string &value, int res[2]);
+/// `mer_render --frequencies=K1[,K2,...]`: 1 ... MER_MAX_FREQUENCIES comma-separated wavenumbers, each finite and at least 0.  0: parsed;
+/// 1: the list is empty or an entry is no number; 2: more than MER_MAX_FREQUENCIES entries; 3: an entry is negative or not finite
+int parseFrequencies(const std::string &value, std::vector<double> &k);
 /// `mer_render --detector=FACE,NU,NV,IU0,IU1,IV0,IV1`: a face 0 ... 5, two counts between 1 and 4096 and a window 0 <= IU0 < IU1 <= NU,
 /// 0 <= IV0 < IV1 <= NV, into the face, res and window fields of det; false for anything else
 bool parseDetector(const std::string &value, mer_detector_desc &det);

@@ -1,4 +1,4 @@
-// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml
+// mer_render -- minimal driver over the C++ host mirror:  mer_render [-D key=value]... [-s spp] [-o out.npy] [--gpus N | --devices a,b,..] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--frequencies=K1[,K2,...]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml
 // (the reference's `mitsuba` CLI, src/mitsuba/mitsuba.cpp:154-246, reduced to what the hot path needs)
 #include "mer_host.h"
 #include <cmath>
@@ -30,6 +30,7 @@ int main(int argc, char **argv) {
     bool timeResolved = false;     // --time-resolved: that grid per frame of the film's transient window
     bool trackLength = false;      // --track-length: that grid from the track-length estimator (mer_fluence_track_create)
     int exitanceRes[2] = {0, 0}; bool exitance = false;                   // --exitance=NU,NV: the exitance map over the medium shape's boundary instead of the film
+    std::vector<double> frequencies; bool frequencyDomain = false;        // --frequencies=K1[,K2,...]: the frequency-domain form of --fluence / --exitance
     float acceptCos = 0.0f; bool acceptCosSet = false;                    // --accept-cos=C: the acceptance cone of that map
     int sensitivityRes[3] = {0, 0, 0}; bool sensitivity = false;          // --sensitivity=NX,NY,NZ: the sensitivity grid of a detector on the boundary instead of the film
     mer_detector_desc detector; std::memset(&detector, 0, sizeof(detector)); bool detectorSet = false, gateSet = false;   // --detector=..., --gate=TMIN,TBIN
@@ -93,9 +94,16 @@ int main(int argc, char **argv) {
             if (e == a.c_str() + 13 || *e || !(acceptCos >= 0.0f && acceptCos < 1.0f)) { std::fprintf(stderr, "--accept-cos=C expects a cosine with 0 <= C < 1\n"); return 2; }
             acceptCosSet = true;
         }
+        else if (a == "--frequencies" || a.rfind("--frequencies=", 0) == 0) {
+            const int bad = a.size() < 14 ? 1 : merhost::parseFrequencies(a.substr(14), frequencies);
+            if (bad == 1) { std::fprintf(stderr, "--frequencies=K1[,K2,...] expects a comma-separated list of wavenumbers (radians per unit of optical path length)\n"); return 2; }
+            if (bad == 2) { std::fprintf(stderr, "--frequencies takes at most 8 wavenumbers\n"); return 2; }
+            if (bad == 3) { std::fprintf(stderr, "--frequencies: a wavenumber must be finite and at least 0\n"); return 2; }
+            frequencyDomain = true;
+        }
         else if (a == "--time-resolved") timeResolved = true;
         else if (a == "--track-length") trackLength = true;
-        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml\n"
+        else if (a == "-h" || a == "--help") { std::printf("usage: mer_render [-D key=value]... [-s spp] [-o out.npy|out.pfm|out.exr] [--raw] [--dense|--cell8] [--device n | --gpus N | --devices a,b,...] [--tiles] [--mesh-sdf[=N]] [--ordered] [--fluence=NX,NY,NZ [--time-resolved | --track-length]] [--exitance=NU,NV [--time-resolved] [--accept-cos=C]] [--frequencies=K1[,K2,...]] [--sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1 [--accept-cos=C] [--gate=TMIN,TBIN] [--detector-bins=BU,BV] [--gates=N] [--scatter]] scene.xml\n"
                                                          "  --mesh-sdf[=N]: a heterogeneousrefractive medium in an obj shape without an sdf child: build the signed-distance grid of the faces on the GPU\n"
                                                          "  and render with it as the boundary; grid = the rif volume's box and resolution, or with N the mesh's box + 5 %% with N nodes on its longest axis\n"
                                                          "  --ordered: one render per sample index, the films added in index order: the film does not depend on the order of its float atomics across\n"
@@ -115,6 +123,11 @@ int main(int argc, char **argv) {
                                                          "  shape's boundary (cube: 6 faces, sphere: 1 face of equal-area cells), from width x height x spp light paths on one GPU; -o names a float32\n"
                                                          "  .npy [frames][faces][nv][nu][3] = sums / (paths x cell area [x binWidth]); the 16 totals are printed.  --time-resolved takes the window\n"
                                                          "  from the film as for --fluence; --accept-cos=C bins only the exits within the cone cos >= C about the outward normal\n"
+                                                         "  --frequencies=K1[,K2,...] (with --fluence= or --exitance=; not with --time-resolved, --track-length): the frequency-domain form, the response\n"
+                                                         "  to an intensity-modulated source: up to 8 wavenumbers k = 2 pi f / c0 >= 0 in radians per unit of optical path length (0: the steady state);\n"
+                                                         "  every deposit goes as w (cos, sin)(k l) into a real and an imaginary plane per wavenumber.  -o names a float32 .npy\n"
+                                                         "  [n_freq][2][nz][ny][nx][3] = sums / (paths x cell volume) or [n_freq][2][faces][nv][nu][3] = sums / (paths x cell area); the totals and, per\n"
+                                                         "  wavenumber, the amplitude and phase of the summed planes are printed.  --accept-cos=C works with the map\n"
                                                          "  --sensitivity=NX,NY,NZ --detector=FACE,NU,NV,IU0,IU1,IV0,IV1: a `ptracer` scene: instead of the film, which part of the medium the light\n"
                                                          "  that reached a detector travelled through (the absorption Jacobian).  The detector is the cell window IU0 <= iu < IU1, IV0 <= iv < IV1 on\n"
                                                          "  face FACE of an --exitance raster of NU x NV cells; --accept-cos=C narrows it to a cone, --gate=TMIN,TBIN to the optical path lengths\n"
@@ -127,6 +140,17 @@ int main(int argc, char **argv) {
                                                          "  homogeneous sigma_s the derivative of a detector's signal by sigma_s is K / sigma_s - J).  -o names a float32 .npy\n"
                                                          "  [1 + scatter][gates][ndv][ndu][nz][ny][nx][3] = sums / paths; one line per measurement is printed: gate, dv, du, detected paths and weight\n"); return 0; }
         else scenePath = a;
+    }
+    if (frequencyDomain) {
+        if (sensitivity) { std::fprintf(stderr, "--frequencies belongs to --fluence / --exitance: a frequency-domain sensitivity grid is not built\n"); return 2; }
+        if (!fluence && !exitance) { std::fprintf(stderr, "--frequencies needs --fluence=NX,NY,NZ or --exitance=NU,NV\n"); return 2; }
+        if (timeResolved) { std::fprintf(stderr, "--frequencies and --time-resolved exclude each other: the frequency-domain form has no window\n"); return 2; }
+        if (trackLength) { std::fprintf(stderr, "--frequencies and --track-length exclude each other: a frequency-domain track-length grid is not built\n"); return 2; }
+        if (multi) { std::fprintf(stderr, "--frequencies runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
+        if (fluence && !exitance) {
+            if (out == "out.npy") out = "fluence_fd.npy";
+            if (!(out.size() > 4 && out.substr(out.size() - 4) == ".npy")) { std::fprintf(stderr, "--frequencies writes a .npy file ([n_freq][2][nz][ny][nx][3]): a VOL holds 1 or 3 channels\n"); return 2; }
+        }
     }
     if (exitance && fluence) { std::fprintf(stderr, "--exitance and --fluence exclude each other: one map per run\n"); return 2; }
     if (exitance && multi) { std::fprintf(stderr, "--exitance runs on one GPU (--device): --gpus / --devices are not built for it (raw sums of shards add; the reduction is left to the caller)\n"); return 2; }
@@ -160,6 +184,34 @@ int main(int argc, char **argv) {
     if (scenePath.empty()) { std::fprintf(stderr, "mer_render: no scene file given\n"); return 2; }
     try {
         auto scene = merhost::loadScene(scenePath, defines);
+        const auto printPlanes = [&](const std::vector<double> &sums, size_t perPlane) {      // per wavenumber: the planes summed over cells and channels
+            for (size_t j = 0; j < frequencies.size(); j++) {
+                double re = 0.0, im = 0.0;
+                for (size_t i = 0; i < perPlane; i++) { re += sums[(2 * j) * perPlane + i]; im += sums[(2 * j + 1) * perPlane + i]; }
+                std::printf("frequency %zu  k %.9g  amplitude %.9g  phase %.9g\n", j, frequencies[j], std::hypot(re, im), std::atan2(im, re));
+            }
+        };
+        if (exitance && frequencyDomain) {
+            const merhost::Integrator::Exitance x = scene->integrator->renderExitance(*scene, device, exitanceRes, frequencies, acceptCos, spp, seed);
+            const std::vector<float> m = x.exitance();
+            merhost::writeNpy(out, m.data(), std::vector<int>{(int) frequencies.size(), 2, x.faces, x.resV, x.resU, 3});
+            std::printf("paths %.0f  escaped %.9g %.9g %.9g  missed %.9g %.9g %.9g  ended %.0f  late %.9g %.9g %.9g  rejected %.9g %.9g %.9g  binned %.0f  %.0f\n",
+                        x.totals[0], x.totals[1], x.totals[2], x.totals[3], x.totals[4], x.totals[5], x.totals[6], x.totals[7], x.totals[8], x.totals[9], x.totals[10],
+                        x.totals[11], x.totals[12], x.totals[13], x.totals[14], x.totals[15]);
+            printPlanes(x.sums, (size_t) x.faces * x.resV * x.resU * 3);
+            std::printf("wrote %s (%zu frequencies of %d faces of %dx%d cells)\n", out.c_str(), frequencies.size(), x.faces, x.resU, x.resV);
+            return 0;
+        }
+        if (fluence && frequencyDomain) {
+            const merhost::Integrator::Fluence f = scene->integrator->renderFluence(*scene, device, fluenceRes, frequencies, spp, seed);
+            const std::vector<float> phi = f.phi();
+            merhost::writeNpy(out, phi.data(), std::vector<int>{(int) frequencies.size(), 2, f.res[2], f.res[1], f.res[0], 3});
+            std::printf("paths %.0f  escaped %.9g %.9g %.9g  dropped %.9g %.9g %.9g  ended %.0f\n", f.totals[0], f.totals[1], f.totals[2], f.totals[3],
+                        f.totals[4], f.totals[5], f.totals[6], f.totals[7]);
+            printPlanes(f.sums, (size_t) f.res[0] * f.res[1] * f.res[2] * 3);
+            std::printf("wrote %s (%zu frequencies of %dx%dx%d cells)\n", out.c_str(), frequencies.size(), f.res[0], f.res[1], f.res[2]);
+            return 0;
+        }
         if (exitance) {
             const Window w = timeResolved ? filmWindow(*scene) : Window{1, 0.0f, 0.0f};
             const merhost::Integrator::Exitance x = scene->integrator->renderExitance(*scene, device, exitanceRes, w.frames, w.tMin, w.tBin, acceptCos, spp, seed);
